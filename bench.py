@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- simulated-years/s of the GREB time-integration engine on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--members M] [--strict]
+  python bench.py --gpus N --steps K --warmup W [--members M] [--strict] [--dump-outputs DIR] [--full]
 
 A "step" is ONE SIMULATED MODEL-YEAR (730 model steps = 35 040 diffusion + 35 040 advection
 sweeps per member) for every ensemble member resident on the GPU.  Members are independent
@@ -11,12 +11,16 @@ hundreds of members -- SURVEY.md 0.6).  value = members x years / wall over all 
 (weak scaling: M per GPU fixed).  At N>1 the monthly means of every member are gathered to
 rank 0 over RCCL inside the timed region (north_star's only collective).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the JSON line; --dump-outputs DIR also writes the last timed
+step's output (dump_outputs).  --full then measures the extra objects (--no-cpu / --no-roofline / --no-g384 drop some):
+  single_member_years_per_s   one member alone (one CU busy)
+  host_delivered               up to 4 ensemble years again, the monthly means copied to host memory
   roofline      the standalone batched diffusion kernel (the kernel BASELINE's second metric is
                 defined on): algorithmic 12 B/point/sweep over its HIP-event-timed launches
   cpu_baseline  the reference Fortran itself (oracle/_ref/greb_ref, built from
                 /root/reference in the build container; "reference") or, if that binary is
                 absent, the C restatement ("port"), 1 core, bounded sample of the same workload
+  g384          BASELINE configs 3 and 5 at 384x192 and the diffusion sweep at that grid (g384_object)
 """
 import argparse
 import json
@@ -40,15 +44,23 @@ def parse_args(argv=None):
                     help="N > 1: members rank 0 integrates (default: --members).  Rank 0 also hosts the receive side of every "
                          "gather; if the per-rank report shows it as the straggler, give it a smaller share")
     ap.add_argument("--strict", action="store_true", help="reference operation order (bit-exact stencils)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-g384", action="store_true", help="skip the 384x192 object (BASELINE configs 3 and 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also measure the extra objects (single member, roofline, host delivery, "
+                         "CPU baselines, 384x192); a plain run measures only the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline object")
+    ap.add_argument("--no-g384", action="store_true", help="--full: skip the 384x192 object (BASELINE configs 3 and 5)")
     ap.add_argument("--roofline-batch", type=int, default=16384)
     ap.add_argument("--launch-timeout", type=float, default=3000.0,
                     help="seconds after which a self-launched multi-rank run is stopped (exit 124)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="bring the ranks up (gloo, no GPU call), print the member partition, exit")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(args, argv):
@@ -157,6 +169,25 @@ def gathered_valid(per_member, members, root_members):
     return np.concatenate([per_member[:root_members], per_member[members:]])
 
 
+DUMP_MEMBERS = 48  # 48 members x 1.1 MB of monthly means at 96x48: 51 MiB, under the 64 MB a dump may take
+
+
+def dump_outputs(out_dir, torch, last, rows, yearly_last):
+    """--dump-outputs: the last timed year as the engine delivered it.
+      monthly_last_step.npy  float32 [S, 12, 5, ny*nx]: monthly means in greb_engine_run's file-record order of a fixed
+                             sample of S = min(members, DUMP_MEMBERS) members, drawn with seed 0 from the global member
+                             indices and kept in ascending order
+      yearly_last_step.npy   float32 [members, 2]: the yearly console values greb_engine_run returns (global-mean Tsurf,
+                             Tsurf at ipx, ipy; deg C) of every member this process integrated
+    `last` is [rows, 12, 5, ny*nx] on the GPU; rows[i] is the row of global member i (rank 0 of an N > 1 run: its gather
+    buffer, padding skipped)."""
+    os.makedirs(out_dir, exist_ok=True)
+    pick = np.sort(np.random.default_rng(0).choice(len(rows), size=min(len(rows), DUMP_MEMBERS), replace=False))
+    sample = last[torch.as_tensor(rows[pick], device=last.device)].cpu().numpy()
+    np.save(os.path.join(out_dir, "monthly_last_step.npy"), sample.astype(np.float32, copy=False))
+    np.save(os.path.join(out_dir, "yearly_last_step.npy"), np.asarray(yearly_last, np.float32))
+
+
 def main():
     argv = sys.argv[1:]
     args = parse_args(argv)
@@ -210,14 +241,15 @@ def main():
     np_ = eng.np
     # (N > 1 writes each year into its own contiguous [M, 1, 12, 5, np] buffer below: no [M, K, ...] tensor there)
     monthly = torch.empty((M, K, 12, 5, np_), dtype=torch.float32, device="cuda") if world == 1 else None
-    gathered = None
+    gathered = yearly = None
     times = {"integrate": 0.0, "gather_wait": 0.0}
 
     def years_with_gather(n_years, bufs, g, clock=None):
         """n_years model years, one engine call per year; year y's gather (RCCL over xGMI) overlaps year y+1."""
+        nonlocal yearly
         for y in range(n_years):
             t = time.perf_counter()
-            eng.run(1, levels[:, None], monthly_dev_ptr=bufs[y].data_ptr())  # (rank 0 with R < M fills the first R members)
+            _, yearly = eng.run(1, levels[:, None], monthly_dev_ptr=bufs[y].data_ptr())  # (rank 0 with R < M fills the first R members)
             if clock is not None:
                 clock["integrate"] += time.perf_counter() - t
             g.submit(y, bufs[y][:, 0])
@@ -258,7 +290,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     if world == 1:
-        eng.run(K, np.repeat(levels[:, None], K, 1), monthly_dev_ptr=monthly.data_ptr())
+        _, yearly = eng.run(K, np.repeat(levels[:, None], K, 1), monthly_dev_ptr=monthly.data_ptr())
     else:
         gathered = years_with_gather(K, year_bufs, gather, times)
     torch.cuda.synchronize()
@@ -287,9 +319,13 @@ def main():
     mine = monthly if world == 1 else (gathered if gathered is not None else year_bufs[-1][:my_m])
     finite = bool(torch.isfinite(mine).all().item())
     tmean = float((monthly[:, -1, :, 0] if world == 1 else year_bufs[-1][:my_m, 0, :, 0]).mean().item())
+    if rank == 0 and args.dump_outputs:
+        last = monthly[:, -1] if world == 1 else gathered[:, -1]
+        rows = np.arange(total_members) if world == 1 else np.concatenate([np.arange(R), np.arange(M, world * M)])
+        dump_outputs(args.dump_outputs, torch, last, rows, yearly[:, -1])
 
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         # single-member latency figure (one member = one CU busy), for the configs with 1 member/GPU
         e1 = engine.Engine(inp, params, n_members=1, device=local_rank, strict=args.strict)
         e1.flux_correction(1)
@@ -298,16 +334,16 @@ def main():
         e1.close()
 
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         roof = roofline_diffusion(torch, engine, params, args.roofline_batch, args.strict)
     cpu = cpu_all = delivered = g384 = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         delivered = host_delivered(torch, eng, levels, M, min(K, 4))
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         cpu = cpu_baseline(inp)
         cpu_all = cpu_baseline_all_cores(inp)
 
-    if rank == 0 and world == 1 and not args.no_g384:
+    if rank == 0 and world == 1 and args.full and not args.no_g384:
         eng.close()  # the 384x192 ensemble wants the HBM (41 GB of per-member flux corrections at 64 members)
         del monthly
         torch.cuda.empty_cache()

@@ -89,3 +89,19 @@ def test_failing_rank_fails_the_launch():
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_plain_run_options():
+    """A plain run measures the headline only (--full is off by default); --steps must be a real count of timed steps."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    a = m.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (3, 2)
+    a = m.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, BENCH, *bad], env=_env(), capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--steps" in r.stderr, bad
+    assert m.DUMP_MEMBERS * 12 * 5 * 96 * 48 * 4 <= 64 * 2 ** 20  # the monthly sample of a dump stays within 64 MB

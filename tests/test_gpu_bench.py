@@ -6,17 +6,55 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from conftest import global_mean_fp64
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_two_ranks_on_one_card_over_gloo():
+def _check_dump(out_dir, n_members, yearly_rows):
+    """--dump-outputs: 48 members drawn with seed 0 from the global indices, each one's monthly means consistent with the
+    yearly global mean the engine returned for it (for the members whose yearly values this process holds)."""
+    monthly = np.load(os.path.join(out_dir, "monthly_last_step.npy"))
+    yearly = np.load(os.path.join(out_dir, "yearly_last_step.npy"))
+    assert sorted(os.listdir(out_dir)) == ["monthly_last_step.npy", "yearly_last_step.npy"]
+    assert monthly.dtype == np.float32 and monthly.shape == (48, 12, 5, 96 * 48) and np.isfinite(monthly).all()
+    assert yearly.dtype == np.float32 and yearly.shape == (yearly_rows, 2) and np.isfinite(yearly).all()
+    assert monthly.nbytes + yearly.nbytes <= 64 * 2 ** 20
+    pick = np.sort(np.random.default_rng(0).choice(n_members, size=48, replace=False))
+    checked = 0
+    for i, g in enumerate(pick):
+        if g < yearly_rows:
+            assert abs(global_mean_fp64(monthly[i]) - float(yearly[g, 0])) < 2.5e-4, (g, global_mean_fp64(monthly[i]), yearly[g, 0])
+            checked += 1
+    assert checked > 0
+
+
+def test_plain_run_measures_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line only, and --dump-outputs writes the last
+    timed year as the engine delivered it."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--members", "64",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "simulated-years/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["finite"] is True
+    assert d["steps"] == 2 and d["warmup"] == 1 and abs(d["value"] - 64 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"] + 0.02
+    for k in ("single_member_years_per_s", "roofline", "host_delivered", "cpu_baseline", "cpu_baseline_all_cores", "g384"):
+        assert k not in d, k  # measured with --full only
+    _check_dump(tmp_path / "out", 64, 64)
+
+
+def test_two_ranks_on_one_card_over_gloo(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GREB_BENCH_BACKEND="gloo", GREB_BENCH_DEVICE="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--members", "48",
-                        "--root-members", "16", "--no-cpu", "--no-roofline", "--no-g384"], env=env, capture_output=True, text=True, timeout=900)
+                        "--root-members", "16", "--no-cpu", "--no-roofline", "--no-g384", "--dump-outputs", str(tmp_path / "out")],
+                       env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]  # EVERY rank must exit cleanly, not only the one that prints
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -28,6 +66,7 @@ def test_two_ranks_on_one_card_over_gloo():
     assert set(pr) == {"integrate", "gather_wait", "total_before_barrier"}
     for v in pr.values():
         assert len(v["per_rank"]) == 2 and v["per_rank"][v["rank_of_max"]] == v["max"] >= v["min"] > 0
+    _check_dump(tmp_path / "out", 64, 16)  # rank 0 dumps: the sample over the gathered members, its own 16 members' yearly values
 
 
 @pytest.mark.parametrize("args", [["4", "--years", "2"], ["5", "--years", "1", "--members", "6"]])

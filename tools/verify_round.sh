@@ -13,15 +13,16 @@ python -c "import __graft_entry__ as g; g.build(); print('build ok')"
 if [ "$1" != profiles-only ] && [ -z "$SKIP_CPU" ]; then python -m pytest tests -x -q -m "not gpu" --deselect tests/test_profiles_cpu.py; fi
 [ "$1" = gpu ] || [ "$1" = profiles ] || [ "$1" = profiles-only ] || exit 0
 G=/usr/local/graft/bin/gpurun
+OUT=${OUT:-$(basename "$G")_out}  # where the GPU runner collects what a command writes (relative to the repository root)
 if [ "$1" != profiles-only ]; then
-$G --timeout 1190 -- 'python -m pytest tests -m gpu -x -q -s > gpurun_out/gputest_final.log 2>&1; tail -3 gpurun_out/gputest_final.log; python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1; python bench.py > gpurun_out/bench_final.log 2>&1; grep "^{" gpurun_out/bench_final.log | cut -c1-220'
+$G --timeout 1190 -- "python -m pytest tests -m gpu -x -q -s > $OUT/gputest_final.log 2>&1; tail -3 $OUT/gputest_final.log; python -c \"import __graft_entry__ as g; g.smoke()\" 2>&1 | tail -1; python bench.py --full > $OUT/bench_final.log 2>&1; grep \"^{\" $OUT/bench_final.log | cut -c1-220"
 grep '^{' gpurun_out/bench_final.log | tail -1 > profiles/${R}_bench_line.json
 grep -E "rms|zonal|passed|failed|global mean|members .* persistent" gpurun_out/gputest_final.log > profiles/${R}_gpu_parity_numbers.txt || true
 fi
 [ "$1" = profiles ] || [ "$1" = profiles-only ] || exit 0
 # (1) kernel trace of the bench command; the 96x48 roofline kernel's FETCH / WRITE passes; the fused member kernel's SQ passes
 #     (every --pmc pass on its own, never combined with a trace; the program directly after `--`)
-$G --timeout 1190 -- 'R=$GRAFT_REPO_ROOT; cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_round -o bench -- python3 $R/bench.py --no-cpu > $R/gpurun_out/prof_round_bench.log 2>&1; export WARM=20 REPS=1; rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/gpurun_out/pmc_round_fetch -o runc -- python3 $R/tools/microbench_dif.py 16384 > /dev/null 2>&1; rocprofv3 --pmc WRITE_SIZE --output-format csv -d $R/gpurun_out/pmc_round_write -o runc -- python3 $R/tools/microbench_dif.py 16384 > /dev/null 2>&1; rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAVES SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY --output-format csv -d $R/gpurun_out/pmc_round_sq -o runc -- python3 $R/bench.py --no-cpu --no-roofline --no-g384 --steps 2 > /dev/null 2>&1; rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d $R/gpurun_out/pmc_round_lds -o runc -- python3 $R/bench.py --no-cpu --no-roofline --no-g384 --steps 2 > /dev/null 2>&1; cd $R && python tools/stamp_member.py 512 2 > gpurun_out/stamp_round.log 2>&1; echo done'
+$G --timeout 1190 -- "R=\$(pwd); cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d \$R/$OUT/prof_round -o bench -- python3 \$R/bench.py --full --no-cpu > \$R/$OUT/prof_round_bench.log 2>&1; export WARM=20 REPS=1; rocprofv3 --pmc FETCH_SIZE --output-format csv -d \$R/$OUT/pmc_round_fetch -o runc -- python3 \$R/tools/microbench_dif.py 16384 > /dev/null 2>&1; rocprofv3 --pmc WRITE_SIZE --output-format csv -d \$R/$OUT/pmc_round_write -o runc -- python3 \$R/tools/microbench_dif.py 16384 > /dev/null 2>&1; rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAVES SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY --output-format csv -d \$R/$OUT/pmc_round_sq -o runc -- python3 \$R/bench.py --full --no-cpu --no-roofline --no-g384 --steps 2 > /dev/null 2>&1; rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d \$R/$OUT/pmc_round_lds -o runc -- python3 \$R/bench.py --full --no-cpu --no-roofline --no-g384 --steps 2 > /dev/null 2>&1; cd \$R && python tools/stamp_member.py 512 2 > $OUT/stamp_round.log 2>&1; echo done"
 # (2) the 384x192 diffusion sweep (row strips, release library; the band kernel it replaces through the tuning library's
 #     GREB_NO_ROWS); the engine's circulation kernels at 62 members; the one-launch call's per-task timeline; launch spread
 $G --timeout 1190 -- 'tools/prof_rows.sh rows > /dev/null 2>&1; GREB_TUNING_LIB=1 GREB_NO_ROWS=1 tools/prof_rows.sh band > /dev/null 2>&1; tools/prof_step.sh 62 > /dev/null 2>&1; for m in 1 24 62; do python tools/circ_timeline.py $m 2>&1 | grep -v amdgpu; echo; done > gpurun_out/circ_timeline_round.txt; python tools/launch_spread.py 96 48 16384 2>&1 | grep -v amdgpu > gpurun_out/spread_g96.txt; python tools/launch_spread.py 384 192 1024 2>&1 | grep -v amdgpu > gpurun_out/spread_g384.txt; echo done'
