@@ -26,11 +26,6 @@
 // wavefront slots it was given (launch_circulation_rows checks it again), the engine keeps a ledger of the slots of a
 // device (greb_engine.cpp), and every wait is bounded by kCircSpinTicks of the 100 MHz clock: a strip that gives up sets
 // a sticky abort word that every other wait sees, the launch drains, and the ABI call returns an error.
-#include <algorithm>
-#include <cstring>
-#include <vector>
-
-#include "greb_step_order.h"
 #include "greb_step_strip.h"
 
 namespace greb {
@@ -352,141 +347,6 @@ __global__ __launch_bounds__(64 * kTasksPerGroup, 2) void circ_rows_kernel(const
 }
 
 } // namespace
-
-// The tasks of one circulation call: per field the chain rows (one task each) and, between them, strips cut by the
-// cost model of greb_step_order.h -- at most n_slots tasks in all, ONE round (see step_rows_tasks for the reasoning:
-// the smallest S such that a SIMD's pair of tasks ends after S cycles), the tasks with the most issue alone on their
-// SIMD, the others paired dearest with cheapest.  Then every task's dependencies: the owners of the two rows below and
-// the two rows above its own.
-void circ_rows_tasks(const RowTables* tabs, const int* tab_index, int n_members, int ny, int n_slots,
-                     std::vector<CircTask>& tasks) {
-  struct T { int field, k0, k1; long long issue, wall; bool chain; };
-  static const int issue_pct = tuning_int("GREB_STEP_ISSUE_PCT", 54); // -DGREB_TUNING builds only
-  static const int wall_pct = tuning_int("GREB_STEP_WALL_PCT", 70);
-  static const int chain_min = tuning_int("GREB_CIRC_CHAIN_MIN", kChainTaskMinSweeps);
-  static const int c_alone = tuning_int("GREB_CIRC_CALONE", 0); // experiment: the dearest chain tasks never share a SIMD
-  const int n_simd = std::max(1, n_slots / 2);
-  auto is_chain = [&](const RowTables& t, int k) { return t.dif_time2[k] >= chain_min; };
-  // a chain task: its sweeps and set-up, the meridional part, no streaming
-  static const int chain_weight = tuning_int("GREB_CIRC_CHAIN_WEIGHT", 120); // per cent of the modelled cost: a chain task on a shared SIMD is the one that never waits (tools/circ_timeline.py), so it is dealt the cheaper partner
-  auto chain_cost = [&](const RowTables& t, int k) {
-    const RowCost c = step_row_cost(t, k);
-    return (long long)(c.issue - kRowIssue + 800) * chain_weight / 100;
-  };
-  long long total = 0, dearest = 0;
-  for (int m = 0; m < n_members; ++m)
-    for (int k = 0; k < ny; ++k) {
-      const RowTables& t = tabs[tab_index[m]];
-      const RowCost c = step_row_cost(t, k);
-      total += 2 * (is_chain(t, k) ? chain_cost(t, k) : c.issue);
-      dearest = std::max<long long>(dearest, is_chain(t, k) ? chain_cost(t, k) : c.wall + kFillWall);
-    }
-  long long S = std::max(total / n_simd, dearest);
-  std::vector<T> all;
-  tasks.clear();
-  for (int pass = 0; pass < 200; ++pass) {
-    const long long cap_issue = S * issue_pct / 100, cap_wall = S * wall_pct / 100;
-    all.clear();
-    for (int m = 0; m < n_members; ++m) {
-      const RowTables& t = tabs[tab_index[m]];
-      std::vector<T> mine;
-      int a = 0;
-      for (int k = 0; k <= ny; ++k) {
-        if (k < ny && !is_chain(t, k)) continue;
-        if (k > a) { // the rows between two chain rows
-          std::vector<Strip> seg;
-          cut_rows(t, a, k, cap_issue, cap_wall, seg);
-          for (const Strip& x : seg) mine.push_back({0, x.k0, x.k1, x.issue, x.wall, false});
-        }
-        if (k < ny) mine.push_back({0, k, k + 1, chain_cost(t, k), chain_cost(t, k), true});
-        a = k + 1;
-      }
-      for (int tr = 0; tr < 2; ++tr)
-        for (T x : mine) { x.field = 2 * m + tr; all.push_back(x); }
-    }
-    int n_dear = 0;
-    if (c_alone) for (const T& x : all) n_dear += x.chain && x.issue >= 25000;
-    if ((int)all.size() <= n_slots - n_dear) break;
-    S += S / 40;
-    if (pass == 199) return; // (cannot happen for ny <= 192: one strip per segment is reached long before) -- no tasks: no launch
-  }
-  if (c_alone) for (T& x : all) if (x.chain && x.issue >= 25000) x.issue += 1000000; // (sorted first: alone)
-  std::stable_sort(all.begin(), all.end(), [](const T& x, const T& y) { return x.issue > y.issue; });
-  if (c_alone) for (T& x : all) if (x.issue >= 1000000) x.issue -= 1000000;
-  const int n_all = (int)all.size();
-  if (n_all > n_simd) {
-    const int m = n_all - n_simd, alone = n_simd - m; // m SIMDs hold a pair
-    std::vector<T> order((size_t)n_all);
-    for (int j = 0; j < m; ++j) {
-      order[(size_t)j] = all[(size_t)(alone + j)];                // the dearer of pair j ...
-      order[(size_t)(n_simd + j)] = all[(size_t)(n_all - 1 - j)]; // ... and the cheapest left
-    }
-    for (int j = 0; j < alone; ++j) order[(size_t)(m + j)] = all[(size_t)j];
-    // ... as the hardware deals them: the wavefronts of the SECOND workgroup on a compute unit start one SIMD further on
-    // (observed, tools/circ_timeline.py: second-round wavefront w sits on SIMD (w + 1) mod 4, so task i shares its SIMD
-    // with task i + 1 023 or i + 1 027, never i + 1 024): the partner meant for SIMD w goes to wavefront (w + 3) mod 4
-    for (int c = 0; n_simd + 4 * c + 3 < n_all; ++c) {
-      const size_t b = (size_t)n_simd + 4 * (size_t)c;
-      const T t0 = order[b], t1 = order[b + 1], t2 = order[b + 2], t3 = order[b + 3];
-      order[b + 3] = t0; order[b] = t1; order[b + 1] = t2; order[b + 2] = t3;
-    }
-    all.swap(order);
-  }
-  // who owns which row of which field
-  std::vector<int> owner((size_t)2 * n_members * ny, -1);
-  for (int i = 0; i < n_all; ++i)
-    for (int k = all[(size_t)i].k0; k < all[(size_t)i].k1; ++k) owner[(size_t)all[(size_t)i].field * ny + k] = i;
-  tasks.reserve((size_t)n_all);
-  for (int i = 0; i < n_all; ++i) {
-    const T& x = all[(size_t)i];
-    CircTask c{x.field | (tab_index[x.field >> 1] << kStepFieldBits), x.k0 | (x.k1 << 8) | kRowsUp | (x.chain ? kCircChain : 0),
-               {-1, -1, -1, -1}, (int)std::min<long long>(x.issue, 0x7fffffff), 0};
-    int nd = 0;
-    const int near[4] = {x.k0 - 2, x.k0 - 1, x.k1, x.k1 + 1};
-    for (int j = 0; j < 4; ++j) {
-      if (near[j] < 0 || near[j] >= ny) continue;
-      const int o = owner[(size_t)x.field * ny + near[j]];
-      if (o == i) continue;
-      bool seen = false;
-      for (int q = 0; q < nd; ++q) seen = seen || c.dep[q] == o;
-      if (!seen) c.dep[nd++] = o;
-    }
-    tasks.push_back(c);
-  }
-}
-
-hipError_t circ_rows_make_order(const RowTables* tabs_host, const int* tab_index_host, int n_members, int ny, int n_slots,
-                                CircOrder* out) {
-  std::vector<CircTask> host;
-  circ_rows_tasks(tabs_host, tab_index_host, n_members, ny, n_slots, host);
-  *out = CircOrder{};
-  if (host.empty() || (int)host.size() > n_slots) return hipSuccess; // n == 0: the caller takes one launch per sub-step
-  hipError_t e = hipMalloc(&out->tasks, host.size() * sizeof(CircTask));
-  if (e == hipSuccess) e = hipMalloc(&out->flags, host.size() * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMalloc(&out->ctrl, 8 * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMemcpy(out->tasks, host.data(), host.size() * sizeof(CircTask), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(out->flags, 0, host.size() * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMemset(out->ctrl, 0, 8 * sizeof(unsigned));
-  if (e != hipSuccess) { circ_rows_free_order(out); return e; }
-  out->n = (int)host.size();
-  out->epoch = 0;
-  return hipSuccess;
-}
-
-void circ_rows_free_order(CircOrder* o) {
-  if (o->tasks) (void)hipFree(o->tasks);
-  if (o->flags) (void)hipFree(o->flags);
-  if (o->ctrl) (void)hipFree(o->ctrl);
-  *o = CircOrder{};
-}
-
-int circ_rows_status(const CircOrder& o, unsigned* diag5) {
-  unsigned h[8] = {0};
-  if (!o.ctrl) return 0;
-  if (hipMemcpy(h, o.ctrl, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -2;
-  if (diag5) std::memcpy(diag5, h + 1, 5 * sizeof(unsigned));
-  return h[0] ? -1 : 0;
-}
 
 #ifdef GREB_TUNING
 // diagnostic builds only: s_memrealtime at the start of each sub-step of task 0 of the last launch, and its end

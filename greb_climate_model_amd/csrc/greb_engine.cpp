@@ -98,6 +98,24 @@ Phys make_phys(const greb_params& p, const greb_member_overrides* o) {
 template <typename T>
 hipError_t dev_alloc(T** p, size_t n) { return hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)); }
 
+// How the row strips run the circulation of the first `nrun` members: the two launch orders and which form runs.
+struct StripPlan {
+  RowsTask* step_tasks = nullptr;        // one launch per sub-step (greb_step_rows.hip): the launch order on the device ...
+  int n_step = 0;
+  RowsTask head[kStepHeadTasks] = {};    // ... and its first tasks, passed by value
+  CircOrder circ;                        // one launch per call: tasks, flags, abort word (n == 0: not resident as a whole)
+  int form = 0;                          // 0 undecided, 1 one launch per sub-step, 2 one launch per call
+  float ms_substep = 0.f, ms_call = 0.f; // the trial: three model steps of each form
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+};
+
+void free_plan(StripPlan& p) {
+  if (p.step_tasks) (void)hipFree(p.step_tasks);
+  circ_rows_free_order(&p.circ);
+  for (hipEvent_t ev : p.ev) if (ev) (void)hipEventDestroy(ev);
+  p = StripPlan{};
+}
+
 } // namespace
 
 struct greb_engine {
@@ -127,18 +145,13 @@ struct greb_engine {
   // host copies needed later
   std::vector<RowTables> h_tabs;
   std::vector<int> h_tab_index;
-  bool step_rows = false;                                   // 384-wide grid: the row-strip sub-step (greb_step_rows.hip)
-  bool step_rows_always = false;                            // GREB_F_ROW_STRIPS
-  struct StepOrder { RowsTask* dev; int n; RowsTask head[kStepHeadTasks]; };
-  std::map<int, StepOrder> step_tasks;                      // its launch order, per number of members run
+  bool strips = false;                                      // 384- or 192-wide grid on the row strips (greb_step_strip.h)
+  enum { kCallNever, kCallTrial, kCallAlways } call = kCallNever; // the circulation call in ONE launch (greb_circ_rows.hip):
+                                                            // never (GREB_F_NO_PERSISTENT), where the trial finds it
+                                                            // faster, or wherever it can run (GREB_F_PERSISTENT)
   int cus = 0;                                              // compute units of the device (4 SIMDs each)
-  bool persistent = false;                                  // ... its circulation call in ONE launch (greb_circ_rows.hip)
-  std::map<int, CircOrder> circ_orders;                     // the tasks, flags and abort word of that launch, per members run
   int slots_granted = -1;                                   // wavefront slots of the device this engine may fill (-1: not asked yet)
-  bool persistent_always = false;                           // GREB_F_PERSISTENT: no trial, the one-launch form wherever it can run
-  struct FormTrial { int form = 0; float ms_substep = 0.f, ms_call = 0.f; }; // form: 0 undecided, 1 per sub-step, 2 per call
-  std::map<int, FormTrial> circ_form;                       // which of the two forms runs, per members run
-  hipEvent_t ev_trial[3] = {nullptr, nullptr, nullptr};
+  std::map<int, StripPlan> plans;                           // how the strips run, per number of members run
   std::vector<Phys> h_phys;
   // model clock
   long long it_flux = 0; // steps done in the flux phase
@@ -191,11 +204,11 @@ int ensure(greb_engine* e, float** buf, size_t* cap, size_t n) {
 // The wavefront slots of a device that one-launch circulation calls may fill, across the engines of this process.
 // Such a launch waits inside the kernel for its own tasks, so all of them must be resident at once; two engines driven
 // side by side (ensemble.run_beside: config 5's 62 + 2 members) share the device, and the sum of what they launch must fit.
-// Every 384-wide engine registers with its member count when it is created; an engine's grant is fixed the first time it
-// needs one: its share of the slots by members among the engines registered then, and never more than what the grants
-// already made leave.  An engine that gets too little for its tasks takes one launch per sub-step, which waits for
-// nothing.  (Another PROCESS on the same device is outside this ledger: there the bounded waits turn a launch that is
-// not co-resident into an error, never a hang.)
+// Every engine that may take the one-launch form registers with its member count when it is created; an engine's grant
+// is fixed the first time it needs one: its share of the slots by members among the engines registered then, and never
+// more than what the grants already made leave.  An engine that gets too little for its tasks takes one launch per
+// sub-step, which waits for nothing.  (Another PROCESS on the same device is outside this ledger: there the bounded
+// waits turn a launch that is not co-resident into an error, never a hang.)
 struct SlotLedger {
   std::mutex mu;
   struct Entry { greb_engine* e; int device, members, granted; };
@@ -228,9 +241,9 @@ int ledger_grant(greb_engine* e, int device_slots) {
 
 // after the stream has been synchronised: did a one-launch circulation call give up waiting?
 int check_circulation(greb_engine* e) {
-  for (auto& kv : e->circ_orders) {
+  for (auto& kv : e->plans) {
     unsigned d[5] = {0, 0, 0, 0, 0};
-    const int rc = circ_rows_status(kv.second, d);
+    const int rc = circ_rows_status(kv.second.circ, d);
     if (rc == -1) {
       char buf[384];
       std::snprintf(buf, sizeof(buf),
@@ -245,34 +258,47 @@ int check_circulation(greb_engine* e) {
   return 0;
 }
 
+// The row strips' plan for `nrun` members: both launch orders where the form is still to be measured, the one that runs
+// where it is not.  Made the first time a year of that many members runs; nothing of it is host work per model step.
+int make_strip_plan(greb_engine* e, int nrun, StripPlan& p) {
+  if (e->cus <= 0) HIP_TRY(e, hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, e->device));
+  // the whole circulation call (its nsub sub-steps) in ONE launch where every task of it can be resident at once ...
+  if (e->call != greb_engine::kCallNever) {
+    static const int slots_per_cu = tuning_int("GREB_CIRC_SLOTS_PER_CU", kStepRowsSlotsPerCu); // -DGREB_TUNING builds only (occupancy experiments: <= 8)
+    if (e->slots_granted < 0) e->slots_granted = ledger_grant(e, e->cus * std::min(slots_per_cu, kStepRowsSlotsPerCu));
+    HIP_TRY(e, circ_rows_make_order(e->h_tabs.data(), e->h_tab_index.data(), nrun, e->ny, e->slots_granted, &p.circ));
+  }
+  p.form = p.circ.n == 0 ? 1 : (e->call == greb_engine::kCallAlways ? 2 : 0); // (n == 0: the grant is too small for this many fields)
+  // ... else one launch per sub-step
+  if (p.form != 2) {
+    static const int step_slots = tuning_int("GREB_STEP_SLOTS_PER_CU", kStepRowsSlotsPerCu); // -DGREB_TUNING builds only (occupancy experiments)
+    HIP_TRY(e, step_rows_make_tasks(e->h_tabs.data(), e->h_tab_index.data(), nrun, e->ny, e->cus * step_slots, &p.step_tasks,
+                                    &p.n_step, p.head));
+  }
+  if (p.form == 0)
+    for (hipEvent_t& ev : p.ev) HIP_TRY(e, hipEventCreate(&ev));
+  return 0;
+}
+
 // One model year (730 steps) for the first `nrun` members, `a` describing that year.
 //   fused layout : one launch of the member kernel
 //   other grids  : 24 fused band sub-steps + 1 point-physics launch per model step
+//   row strips   : the 24 sub-steps in one launch or one launch each (StripPlan) + 1 point-physics launch per model step
 int run_year(greb_engine* e, const MemberArgs& a, int nrun) {
   if (e->fused) {
     HIP_TRY(e, launch_member_kernel(a, nrun, e->strict, e->stream));
     return 0;
   }
   const size_t np = (size_t)e->np;
-  // 384-wide grids, FAST: the row-strip sub-step (greb_step_rows.hip) at every member count -- us per launch against
-  // the band kernels it replaces (the scalar sweep_kernel<fused> below 28 members, a (Tair,q)-pair band kernel above, round
-  // 2): 1 member 23.2 / 25.1, 8: 27.8 / 28.8, 24: 30.0 / 30.5, 40: 35.6 / 35.2, 48: 39.6 / 40.5, 62: 40.8 / 48.0.
-  // STRICT keeps the band kernel (1 member 64.7 against 74.6 us: its two chains per row run one after the other in
-  // one wave here); GREB_F_ROW_STRIPS takes the strips there too.
-  const bool rows = e->step_rows && (e->step_rows_always || !e->strict);
-  // the whole circulation call (its nsub sub-steps) in ONE launch where every task of it can be resident at once ...
-  CircOrder* circ = nullptr;
-  if (rows && e->persistent && a.nsub > 0) {
-    if (e->cus <= 0) HIP_TRY(e, hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, e->device));
-    static const int slots_per_cu = tuning_int("GREB_CIRC_SLOTS_PER_CU", kStepRowsSlotsPerCu); // -DGREB_TUNING builds only (occupancy experiments: <= 8)
-    if (e->slots_granted < 0) e->slots_granted = ledger_grant(e, e->cus * std::min(slots_per_cu, kStepRowsSlotsPerCu));
-    auto it = e->circ_orders.find(nrun);
-    if (it == e->circ_orders.end()) {
-      CircOrder o;
-      HIP_TRY(e, circ_rows_make_order(e->h_tabs.data(), e->h_tab_index.data(), nrun, e->ny, e->slots_granted, &o));
-      it = e->circ_orders.emplace(nrun, o).first;
+  StripPlan* plan = nullptr;
+  if (e->strips && a.nsub > 0) {
+    auto it = e->plans.find(nrun);
+    if (it == e->plans.end()) {
+      StripPlan p;
+      if (int rc = make_strip_plan(e, nrun, p)) { free_plan(p); return rc; }
+      it = e->plans.emplace(nrun, p).first;
     }
-    if (it->second.n > 0) circ = &it->second; // (0: the grant is too small for this many fields)
+    plan = &it->second;
   }
   // Which of the two wins depends on how many fields there are and what shares a SIMD with what (one member: 15.1 against
   // 18.7 us per sub-step; 40 members: 29.6 against 25.8; 62: 36.0 against 38.7), and the two are bit-identical row by
@@ -280,31 +306,8 @@ int run_year(greb_engine* e, const MemberArgs& a, int nrun) {
   // steps, three timed steps of one form and three of the other between events on its own stream, and the faster form
   // runs from then on.  The results do not depend on the choice.
   static const int steps = tuning_int("GREB_DEBUG_NSTEPS", kNT); // -DGREB_TUNING builds only: a short stretch for counter passes
-  greb_engine::FormTrial* trial = nullptr;
-  int form = circ ? 2 : 1;
-  if (circ && !e->persistent_always) {
-    greb_engine::FormTrial& ft = e->circ_form[nrun];
-    if (ft.form == 0 && steps >= 16) {
-      trial = &ft;
-      for (hipEvent_t& ev : e->ev_trial) if (!ev) HIP_TRY(e, hipEventCreate(&ev));
-    } else if (ft.form) form = ft.form;
-  }
-  // ... else one launch per sub-step
-  const RowsTask *step_tasks = nullptr, *step_head = nullptr;
-  int n_step_tasks = 0;
-  if (rows && (form == 1 || trial)) {
-    auto it = e->step_tasks.find(nrun);
-    if (it == e->step_tasks.end()) {
-      RowsTask* dev = nullptr; int n = 0;
-      if (e->cus <= 0) HIP_TRY(e, hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, e->device));
-      greb_engine::StepOrder so{};
-      static const int step_slots = tuning_int("GREB_STEP_SLOTS_PER_CU", kStepRowsSlotsPerCu); // -DGREB_TUNING builds only (occupancy experiments)
-      HIP_TRY(e, step_rows_make_tasks(e->h_tabs.data(), e->h_tab_index.data(), nrun, e->ny, e->cus * step_slots, &dev, &n, so.head));
-      so.dev = dev; so.n = n;
-      it = e->step_tasks.emplace(nrun, so).first;
-    }
-    step_tasks = it->second.dev; n_step_tasks = it->second.n; step_head = it->second.head;
-  }
+  bool trial = plan && plan->form == 0 && steps >= 16;
+  int form = plan && plan->form != 1 ? 2 : 1; // (undecided without a trial: one launch per call)
   HIP_TRY(e, launch_pack_tracers(e->state, e->Xa, e->np, nrun, e->stream));
   for (int s = 0; s < steps; ++s) {
     const long long it = a.it0 + s;
@@ -312,24 +315,24 @@ int run_year(greb_engine* e, const MemberArgs& a, int nrun) {
     const size_t off = (size_t)(ityr - 1) * np;
     float *cur = e->Xa, *nxt = e->Xb;
     if (trial) { // steps 0-1 warm up, 2-4 one launch per sub-step, 5-7 one launch per call
-      if (s == 2 || s == 5 || s == 8) HIP_TRY(e, hipEventRecord(e->ev_trial[s == 2 ? 0 : (s == 5 ? 1 : 2)], e->stream));
+      if (s == 2 || s == 5 || s == 8) HIP_TRY(e, hipEventRecord(plan->ev[s == 2 ? 0 : (s == 5 ? 1 : 2)], e->stream));
       if (s == 8) {
-        HIP_TRY(e, hipEventSynchronize(e->ev_trial[2]));
-        HIP_TRY(e, hipEventElapsedTime(&trial->ms_substep, e->ev_trial[0], e->ev_trial[1]));
-        HIP_TRY(e, hipEventElapsedTime(&trial->ms_call, e->ev_trial[1], e->ev_trial[2]));
-        form = trial->form = trial->ms_call <= trial->ms_substep ? 2 : 1;
-        trial = nullptr;
+        HIP_TRY(e, hipEventSynchronize(plan->ev[2]));
+        HIP_TRY(e, hipEventElapsedTime(&plan->ms_substep, plan->ev[0], plan->ev[1]));
+        HIP_TRY(e, hipEventElapsedTime(&plan->ms_call, plan->ev[1], plan->ev[2]));
+        form = plan->form = plan->ms_call <= plan->ms_substep ? 2 : 1;
+        trial = false;
       } else form = (s >= 2 && s < 5) ? 1 : 2;
     }
     if (form == 2) {
-      HIP_TRY(e, launch_circulation_rows(e->Xa, e->Xb, e->W2, e->uclim + off, e->vclim + off, e->tabs, *circ, e->cus * 4, e->nx, e->ny,
+      HIP_TRY(e, launch_circulation_rows(e->Xa, e->Xb, e->W2, e->uclim + off, e->vclim + off, e->tabs, plan->circ, e->cus * 4, e->nx, e->ny,
                                          a.nsub, e->strict, e->stream, (e->xsw & GREB_X_VAPOR_DIFFUSION_ONLY) != 0));
       if (a.nsub & 1) cur = e->Xb;
     } else
     for (int tt = 0; tt < a.nsub; ++tt) {
-      if (rows)
-        HIP_TRY(e, launch_substep_rows(cur, e->W2, e->uclim + off, e->vclim + off, nxt, e->tabs, e->tab_index, step_tasks,
-                                       step_head, n_step_tasks, e->cus * 4, e->nx, e->ny, e->strict, e->stream, (e->xsw & GREB_X_VAPOR_DIFFUSION_ONLY) != 0));
+      if (plan)
+        HIP_TRY(e, launch_substep_rows(cur, e->W2, e->uclim + off, e->vclim + off, nxt, e->tabs, e->tab_index, plan->step_tasks,
+                                       plan->head, plan->n_step, e->cus * 4, e->nx, e->ny, e->strict, e->stream, (e->xsw & GREB_X_VAPOR_DIFFUSION_ONLY) != 0));
       else
         HIP_TRY(e, launch_substep_fused(cur, e->W2, e->uclim + off, e->vclim + off, nxt, e->tabs, e->tab_index, e->nx,
                                         e->ny, nrun, e->strict, e->stream, (e->xsw & GREB_X_VAPOR_DIFFUSION_ONLY) != 0));
@@ -505,14 +508,19 @@ int greb_engine_create(const greb_params* p, int nx, int ny, const greb_fields* 
     HIP_TRY(e, dev_alloc(&e->W2, 2 * np));
     HIP_TRY(e, hipMemcpy(e->W2, wz_air.data(), np * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(e, hipMemcpy(e->W2 + np, wz_vapor.data(), np * sizeof(float), hipMemcpyHostToDevice));
+    // 384- and 192-wide grids, FAST: the row strips at every member count -- us per launch of the per-sub-step form
+    // against the band kernels it replaces (the scalar sweep_kernel<fused> below 28 members, a (Tair,q)-pair band kernel
+    // above, round 2): 1 member 23.2 / 25.1, 8: 27.8 / 28.8, 24: 30.0 / 30.5, 40: 35.6 / 35.2, 48: 39.6 / 40.5, 62: 40.8 /
+    // 48.0.  STRICT keeps the band kernel (1 member 64.7 against 74.6 us: its two chains per row run one after the other
+    // in one wave here); GREB_F_ROW_STRIPS takes the strips there too.
     static const bool no_step_rows = tuning_int("GREB_NO_STEP_ROWS", 0) != 0; // -DGREB_TUNING builds only (A/B)
-    e->step_rows = !no_step_rows && n_members < (1 << (kStepFieldBits - 1)) && // (field and table index share a task word)
-                   step_rows_supported(e->h_tabs.data(), (int)e->h_tabs.size(), nx, ny);
-    e->step_rows_always = (flags & GREB_F_ROW_STRIPS) != 0;
-    static const bool no_persistent = tuning_int("GREB_NO_PERSISTENT", 0) != 0; // -DGREB_TUNING builds only (A/B)
-    e->persistent = e->step_rows && !no_persistent && !(flags & GREB_F_NO_PERSISTENT);
-    e->persistent_always = e->persistent && (flags & GREB_F_PERSISTENT) != 0;
-    if (e->persistent) ledger_register(e);
+    e->strips = !no_step_rows && (!e->strict || (flags & GREB_F_ROW_STRIPS)) &&
+                n_members < (1 << (kStepFieldBits - 1)) && // (field and table index share a task word)
+                step_rows_supported(e->h_tabs.data(), (int)e->h_tabs.size(), nx, ny);
+    if (e->strips && !(flags & GREB_F_NO_PERSISTENT)) {
+      e->call = (flags & GREB_F_PERSISTENT) ? greb_engine::kCallAlways : greb_engine::kCallTrial;
+      ledger_register(e);
+    }
   }
   return 0;
 }
@@ -525,10 +533,8 @@ int greb_engine_destroy(greb_engine* e) {
                   e->corr, e->corr_index, e->tab_index, e->tabs, e->phys, e->co2_dev, e->monthly_dev, e->yearly_dev,
                   e->Xa, e->Xb, e->red, e->W2};
   for (void* q : ptrs) if (q) (void)hipFree(q);
-  for (auto& kv : e->step_tasks) if (kv.second.dev) (void)hipFree(kv.second.dev);
-  for (auto& kv : e->circ_orders) circ_rows_free_order(&kv.second);
-  if (e->persistent) ledger_release(e);
-  for (hipEvent_t ev : e->ev_trial) if (ev) (void)hipEventDestroy(ev);
+  for (auto& kv : e->plans) free_plan(kv.second);
+  if (e->call != greb_engine::kCallNever) ledger_release(e);
   for (int i = 0; i < 2; ++i) {
     if (e->ev_done[i]) (void)hipEventDestroy(e->ev_done[i]);
     if (e->ev_free[i]) (void)hipEventDestroy(e->ev_free[i]);
@@ -653,19 +659,18 @@ const char* greb_engine_describe(greb_engine* e) {
   if (!e) { s = "{}"; return s.c_str(); }
   char buf[256];
   std::snprintf(buf, sizeof(buf), "{\"grid\": [%d, %d], \"members\": %d, \"arithmetic\": \"%s\", \"engine\": \"%s\"", e->nx, e->ny, e->nm,
-                e->strict ? "strict" : "fast", e->fused ? "fused member kernel" : (e->step_rows ? "row strips" : "latitude bands"));
+                e->strict ? "strict" : "fast", e->fused ? "fused member kernel" : (e->strips ? "row strips" : "latitude bands"));
   s = buf;
-  if (e->persistent) {
+  if (e->call != greb_engine::kCallNever) {
     std::snprintf(buf, sizeof(buf), ", \"wavefront_slots_granted\": %d, \"circulation\": [", e->slots_granted);
     s += buf;
     bool first = true;
-    for (const auto& kv : e->circ_orders) {
-      const auto ft = e->circ_form.find(kv.first);
-      const int form = e->persistent_always ? 2 : (ft == e->circ_form.end() ? 0 : ft->second.form);
+    for (const auto& kv : e->plans) {
+      const StripPlan& p = kv.second;
       std::snprintf(buf, sizeof(buf), "%s{\"members_run\": %d, \"tasks_of_one_launch_per_call\": %d, \"form\": \"%s\", \"trial_ms_per_3_steps\": [%.4f, %.4f]}",
-                    first ? "" : ", ", kv.first, kv.second.n,
-                    kv.second.n == 0 ? "one launch per sub-step (slots)" : (form == 2 ? "one launch per call" : (form == 1 ? "one launch per sub-step" : "undecided")),
-                    ft == e->circ_form.end() ? 0.f : ft->second.ms_substep, ft == e->circ_form.end() ? 0.f : ft->second.ms_call);
+                    first ? "" : ", ", kv.first, p.circ.n,
+                    p.circ.n == 0 ? "one launch per sub-step (slots)" : (p.form == 2 ? "one launch per call" : (p.form == 1 ? "one launch per sub-step" : "undecided")),
+                    p.ms_substep, p.ms_call);
       s += buf;
       first = false;
     }

@@ -79,7 +79,9 @@ hipError_t launch_circulation_g96(const float* X, const float* wz, const float* 
 // tab_host: the same table on the host (the 384-wide row-strip kernel takes its row constants by value)
 hipError_t launch_diffusion(const float* T1, const float* wz, float* dX, const RowTables* tab_dev,
                             const RowTables& tab_host, int nx, int ny, int batch, bool strict, hipStream_t s);
-// greb_rows.hip: the diffusion sweep of a 384-wide grid as wavefront-sized row strips (FAST and STRICT)
+// greb_rows.hip: the diffusion sweep of a 384-wide grid as wavefront-sized row strips (FAST and STRICT).
+// The launch orders of the row-strip kernels (rows_tasks, step_rows_tasks, circ_rows_tasks) are host code of their own:
+// greb_strip_order.cpp.
 bool rows_supported(const RowTables& t, int nx, int ny);
 struct RowsTask { int field, rows; }; // rows = k0 | k1 << 8 | kRowsUp: the task updates rows [k0, k1); field < 0: no task
 constexpr int kRowsUp = 1 << 20;       // the strip walks south to north (else north to south)

@@ -7,8 +7,8 @@
 // bytes (profiles/r03_g384_diffusion_pmc.txt).  Here nothing waits for anything but its own data:
 //   * one WAVEFRONT = one task = a strip of consecutive rows of one field; no workgroup barrier anywhere.  The dependent
 //     chains -- which issue one instruction per ~5 cycles whatever they share a SIMD with -- run beside streaming strips
-//     (rows_tasks below decides the launch order: chain strips interleaved with streaming strips, ever shorter strips
-//     for the fields launched last);
+//     (greb_strip_order.cpp: rows_tasks decides the launch order: chain strips interleaved with streaming strips, ever
+//     shorter strips for the fields launched last);
 //   * a lane owns 6 consecutive longitudes of a row (64 x 6 = 384), the layout of the register-resident chains
 //     (greb_chain6.h): the zonal halo is a wave rotate (DPP), never memory;
 //   * a row travels HBM -> LDS by LDS-DMA (global_load_lds_dwordx4: coalesced 16-byte lanes, no VGPRs, three rows ahead
@@ -24,7 +24,6 @@
 // Measured (MI355X, batch 1 024, settled clocks): 0.168-0.176 ms per launch = 5.2-5.4 TB/s = 0.65-0.67 of HBM peak
 // (band kernel: 0.29), the chains hidden completely (0.165-0.18 with every row forced to a single sweep); 57 400 vector
 // instructions per field; HBM-side traffic 1.03 x algorithmic; STRICT 0.42 ms (band kernel: 0.90).
-#include <algorithm>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -196,7 +195,7 @@ __global__ __launch_bounds__(64) void dif_rows_kernel(const float* __restrict__ 
                                                        float* __restrict__ dX, const RowsArgs a,
                                                        const RowsTask* __restrict__ tasks, int batch, int ny, int dbg) {
   extern __shared__ __align__(16) float lds_raw[];
-  // the launch order is a table (rows_tasks below): block i does task i
+  // the launch order is a table (rows_tasks, greb_strip_order.cpp): block i does task i
   const RowsTask task = tasks[blockIdx.x];
   const int b = task.field;
   if (b < 0) return; // padding of an incomplete group of eight fields
@@ -235,85 +234,6 @@ __global__ __launch_bounds__(64) void dif_rows_kernel(const float* __restrict__ 
   }
 }
 
-int strip_cost(int time2) { return time2 > 1 ? 130 + 36 * time2 : 120; }
-
-struct Strip { int k0, k1, cost, up; };
-
-// contiguous strips of about `target` instructions over rows [ka, kb), never splitting a row; a strip is closed when
-// the next row would take it over the target, unless it is still tiny
-void cut_strips(const RowTables& t, int ka, int kb, int target, std::vector<Strip>& out) {
-  int acc = 0, start = ka;
-  for (int k = ka; k < kb; ++k) {
-    const int cst = strip_cost(t.dif_time2[k]);
-    if (acc > 0 && acc + cst > target && acc >= 600) { out.push_back({start, k, acc, 0}); start = k; acc = 0; }
-    acc += cst;
-  }
-  if (kb > ka) out.push_back({start, kb, acc, 0});
-}
-
-} // namespace
-
-// The launch order.  Two kinds of task: CHAIN strips (the rows next to the poles that iterate: arithmetic, a lone
-// wavefront issuing one instruction per ~5 cycles) and STREAMING strips (the single-sweep rows between the caps: memory).
-//   * they are interleaved, the chain strips spread evenly over the first `chain_span` per cent of the launch: at any
-//     moment a SIMD holds about one chain wave beside streaming ones, so the arithmetic hides under the traffic
-//     (dearest-first order ran the chains first and the traffic after them: 0.210 ms against 0.190);
-//   * the streaming region is cut into few long strips for most fields (halo rows re-read: 2 per strip) and into ever
-//     shorter ones for the fields launched last (levels below): when the last task starts, what is still running is
-//     small, so the launch does not end on a handful of wavefronts each streaming at its own latency-bound ~3 GB/s;
-//   * tasks come in groups of eight (the same strip of eight consecutive fields): blocks are dealt to the eight XCDs in
-//     turn, so all strips of a field run on one XCD, and neighbouring strips walk away from their common border (one
-//     down, one up): the halo rows both read are requested together and the second reader finds them in that XCD's L2.
-// Speed only: any order gives the same result bit for bit, every row is written by exactly one task.
-void rows_tasks(const RowTables& t, int ny, int batch, const RowsTuning& tu, std::vector<RowsTask>& tasks) {
-  // the streaming region: the run of single-sweep rows around the equator
-  int ks = ny / 2, ke = ny / 2;
-  while (ks > 0 && t.dif_time2[ks - 1] == 1) --ks;
-  while (ke < ny && t.dif_time2[ke] == 1) ++ke;
-  if (t.dif_time2[ny / 2] != 1) ks = ke = ny / 2; // (no such run: everything is a chain strip)
-  std::vector<Strip> caps;
-  cut_strips(t, 0, ks, tu.chain_target, caps);
-  cut_strips(t, ke, ny, tu.chain_target, caps);
-  for (size_t i = 0; i < caps.size(); ++i) caps[i].up = (int)(i & 1);
-  std::stable_sort(caps.begin(), caps.end(), [](const Strip& x, const Strip& y) { return x.cost > y.cost; });
-  const int G = (batch + 7) / 8, len = ke - ks;
-  // levels of the streaming cut, coarse to fine; the finer levels take the LAST groups of fields
-  int parts[4], first[5];
-  for (int l = 0; l < 4; ++l) parts[l] = std::max(1, std::min(len, tu.parts[l]));
-  first[4] = G;
-  for (int l = 3; l >= 1; --l) {
-    const int groups = len > 0 ? (tu.level_tasks[l] + 8 * parts[l] - 1) / (8 * parts[l]) : 0;
-    first[l] = std::max(0, first[l + 1] - groups);
-  }
-  first[0] = 0;
-  struct Oct { double pos; int group, k0, k1, up; };
-  std::vector<Oct> so, co;
-  double sw = 0, cw = 0;
-  if (len > 0)
-    for (int l = 0; l < 4; ++l)
-      for (int g = first[l]; g < first[l + 1]; ++g)
-        for (int i = 0; i < parts[l]; ++i) {
-          const int a0 = ks + (int)((long long)len * i / parts[l]), a1 = ks + (int)((long long)len * (i + 1) / parts[l]);
-          so.push_back({sw, g, a0, a1, i & 1});
-          sw += a1 - a0 + 2;
-        }
-  for (int g = 0; g < G; ++g)
-    for (const Strip& c : caps) { co.push_back({cw, g, c.k0, c.k1, c.up}); cw += c.cost; }
-  for (Oct& o : so) o.pos /= sw > 0 ? sw : 1;
-  const double span = so.empty() ? 1.0 : tu.chain_span * 0.01;
-  for (Oct& o : co) o.pos *= span / (cw > 0 ? cw : 1);
-  std::vector<Oct> all(so.size() + co.size());
-  std::merge(co.begin(), co.end(), so.begin(), so.end(), all.begin(), [](const Oct& x, const Oct& y) { return x.pos < y.pos; });
-  tasks.clear();
-  tasks.reserve(all.size() * 8);
-  for (const Oct& o : all)
-    for (int f = 0; f < 8; ++f) {
-      const int field = 8 * o.group + f;
-      tasks.push_back({field < batch ? field : -1, o.k0 | (o.k1 << 8) | (o.up ? kRowsUp : 0)});
-    }
-}
-
-namespace {
 // device copies of launch orders: immutable once made (a call in flight never sees its table change), freed only by
 // rows_release_cache()
 struct TaskTable {

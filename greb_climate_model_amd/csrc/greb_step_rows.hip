@@ -10,14 +10,11 @@
 // cycles per sweep, greb_chain6.h) plus everything in front of it -- arguments, task, the first rows from memory another
 // XCD wrote: 18.6-18.8 us per launch for one member (the one-launch call: 15.3 us per sub-step; round 2's band kernels:
 // 25.1).  With many fields it is bound by instruction issue (one vector instruction per SIMD every 4 cycles) and by how
-// evenly the SIMDs are loaded: step_rows_tasks below builds the launch order, ONE round of at most as many tasks as the
-// chip has wavefront slots.
+// evenly the SIMDs are loaded: step_rows_tasks (greb_strip_order.cpp) builds the launch order, ONE round of at most as
+// many tasks as the chip has wavefront slots.
 // STRICT keeps the reference's expression trees (bit-exact), FAST the re-associated ones of the other kernels.
-#include <algorithm>
 #include <cstring>
-#include <vector>
 
-#include "greb_step_order.h"
 #include "greb_step_strip.h"
 
 namespace greb {
@@ -100,87 +97,6 @@ __global__ __launch_bounds__(64, GREB_STEP_WAVES) void step_rows_kernel(const St
 }
 
 } // namespace
-
-bool step_rows_supported(const RowTables* tabs, int n_tabs, int nx, int ny) {
-  if ((nx != rows::kNx && 2 * nx != rows::kNx) || ny < 5 || ny > kMaxNy) return false; // 384 longitudes, or 192 laid twice round the wavefront
-  for (int t = 0; t < n_tabs; ++t)
-    for (int k = 0; k < ny; ++k)
-      if (!tabs[t].subcycled[k] || tabs[t].dif_time2[k] < 1 || tabs[t].adv_time2[k] < 1) return false;
-  return true;
-}
-
-// The launch order of one sub-step.  The chip has slots / 2 SIMDs with two wavefront slots each (187 VGPRs, 19.5 KB of
-// LDS per wavefront); workgroup i of a launch lands on SIMD i mod (slots / 2), so tasks i and i + slots / 2 share one.
-// A launch is as long as its longest SIMD, and a task started late -- because there are more tasks than slots -- runs
-// its full length after the others are done (62 members as 2 388 tasks for 2 048 slots: 40 us, 13 of them for the 340
-// late strips).  So ONE round: the rows of all fields are cut into at most `n_slots` strips such that a SIMD's pair ends
-// after S cycles -- each strip at most S / 2 of issue and S of wall (RowCost) -- with S the smallest that fits, but no
-// less than the dearest row's wall (the 232-sweep polar row: few fields gain nothing from strips that end before it).
-// With n tasks for n_simd SIMDs, n - n_simd SIMDs hold a pair: the strips with the most issue run alone, the others are
-// paired dearest with cheapest (two chain strips on one SIMD -- both issue without a pause -- take twice as long each).
-void step_rows_tasks(const RowTables* tabs, const int* tab_index, int n_members, int ny, int n_slots,
-                     std::vector<RowsTask>& tasks) {
-  typedef Strip T;
-  static const int forced = tuning_int("GREB_STEP_TARGET", 0);        // -DGREB_TUNING builds only: S in cycles
-  static const int issue_pct = tuning_int("GREB_STEP_ISSUE_PCT", 54); // ... a strip's share of S in issue
-  static const int wall_pct = tuning_int("GREB_STEP_WALL_PCT", 70);   // ... and in wall time (measured: 1 member 19.1 us per launch at 85-100, 18.5 at 60-70)
-  const int n_simd = std::max(1, n_slots / 2);
-  long long total = 0, dearest = 0;
-  for (int m = 0; m < n_members; ++m)
-    for (int k = 0; k < ny; ++k) {
-      const RowCost c = step_row_cost(tabs[tab_index[m]], k);
-      total += 2 * c.issue;
-      dearest = std::max<long long>(dearest, c.wall);
-    }
-  long long S = std::max(total / n_simd, dearest + kFillWall);
-  if (forced) S = forced;
-  std::vector<T> all;
-  for (int pass = 0; pass < 96; ++pass) {
-    const long long cap_issue = S * issue_pct / 100, cap_wall = S * wall_pct / 100;
-    all.clear();
-    for (int m = 0; m < n_members; ++m) {
-      const RowTables& t = tabs[tab_index[m]];
-      std::vector<T> mine;
-      cut_rows(t, 0, ny, cap_issue, cap_wall, mine);
-      for (int tr = 0; tr < 2; ++tr)
-        for (T x : mine) { x.field = 2 * m + tr; all.push_back(x); }
-    }
-    if (forced || (int)all.size() <= 2 * n_simd) break;
-    S += S / 40;
-  }
-  std::stable_sort(all.begin(), all.end(), [](const T& x, const T& y) { return x.issue > y.issue; });
-  const int n_all = (int)all.size();
-  if (n_all > n_simd && n_all <= 2 * n_simd) {
-    const int m = n_all - n_simd, alone = n_simd - m; // m SIMDs hold a pair
-    std::vector<T> order((size_t)n_all);
-    for (int j = 0; j < m; ++j) {
-      order[(size_t)j] = all[(size_t)(alone + j)];                // the dearer of pair j ...
-      order[(size_t)(n_simd + j)] = all[(size_t)(n_all - 1 - j)]; // ... and the cheapest left
-    }
-    for (int j = 0; j < alone; ++j) order[(size_t)(m + j)] = all[(size_t)j];
-    all.swap(order);
-  }
-  tasks.clear();
-  tasks.reserve(all.size());
-  for (const T& x : all) tasks.push_back({x.field | (tab_index[x.field >> 1] << kStepFieldBits), x.k0 | (x.k1 << 8) | kRowsUp});
-}
-
-// the launch order on the device (owned by the caller: the engine keeps one per member count and frees it with itself)
-hipError_t step_rows_make_tasks(const RowTables* tabs_host, const int* tab_index_host, int n_members, int ny,
-                                int n_slots, RowsTask** dev, int* n, RowsTask* head) {
-  std::vector<RowsTask> host;
-  step_rows_tasks(tabs_host, tab_index_host, n_members, ny, n_slots, host);
-  for (int i = 0; i < kStepHeadTasks; ++i) head[i] = i < (int)host.size() ? host[(size_t)i] : RowsTask{0, 0};
-  hipError_t e = hipMalloc(dev, host.size() * sizeof(RowsTask));
-  if (e != hipSuccess) return e;
-  if ((e = hipMemcpy(*dev, host.data(), host.size() * sizeof(RowsTask), hipMemcpyHostToDevice)) != hipSuccess) {
-    (void)hipFree(*dev);
-    *dev = nullptr;
-    return e;
-  }
-  *n = (int)host.size();
-  return hipSuccess;
-}
 
 #ifdef GREB_TUNING
 // diagnostic builds only: six s_memtime stamps of the dearest task of the last launch (tools/stamp_step_rows.py):

@@ -672,12 +672,13 @@ def test_run_without_flux_correction_vs_reference(eng_mod, params, inputs, stric
     yearly_close(yr[0], g["yearly"], strict)
 
 
-def test_engine_g192_vs_reference(eng_mod, oracle_lib):
+def test_engine_g192_vs_reference_on_the_engine_it_names(eng_mod, oracle_lib):
     """A grid that is neither of the two BASELINE ones (runtime grid sizes): 192x96, bilinear-upsampled
     inputs, every row sub-cycled, 10 rows iterating (up to 129 sweeps).  Against the REFERENCE compiled at that grid
     (tests/golden/routine_g192.npz, g192_short.npz; oracle/Makefile ref192): batched STRICT stencils bit-exact against
     the reference's own subroutines, FAST within the re-association tolerance, and a 1+1-yr run in both arithmetic
-    modes against the reference program's output (any-grid multi-launch engine)."""
+    modes against the reference program's output (any-grid multi-launch engine).  Each engine names the kernels it runs:
+    STRICT keeps the latitude bands unless GREB_F_ROW_STRIPS asks for the strips."""
     import json
     from greb_climate_model_amd import abi, workload
     g, gs = load_golden("routine_g192.npz"), load_golden("g192_short.npz")
@@ -708,7 +709,7 @@ def test_engine_g192_vs_reference(eng_mod, oracle_lib):
                       ("strict strips, one launch per sub-step", dict(strict=True, row_strips=True, persistent=False))):
         e = eng_mod.Engine(inp, p, **kw)
         d = e.describe()
-        assert d["engine"] == "row strips", d  # this grid takes the strips (STRICT without row_strips keeps its bands at run time)
+        assert d["engine"] == ("latitude bands" if label == "strict bands" else "row strips"), d
         yf = e.flux_correction(1)
         mon, yr = e.run(1, 680.0)
         d = e.describe()
@@ -751,13 +752,14 @@ def test_engine_g192_members_are_independent(eng_mod):
 
 
 @pytest.mark.parametrize("nx,ny", [(384, 96), (192, 192), (192, 48), (384, 48)])
-def test_row_strips_on_other_384_and_192_wide_grids(eng_mod, nx, ny):
+def test_row_strips_on_other_384_and_192_wide_grids_against_the_bands(eng_mod, nx, ny):
     """The row-strip kernels take any grid 384 or 192 longitudes wide (src/greb.f90:36 is all that fixes the grid in the
     reference): other latitude counts put the iterating rows, the chain tasks and the strip cuts elsewhere.  No reference
     build exists at these grids, so this is a consistency pin, not a parity pin: STRICT on the strips -- one launch per
     circulation call -- against STRICT on the latitude bands (which the three reference-pinned grids hold to the reference),
     bit for bit over a flux-correction year and a scenario year with two members; FAST stays within the whole-run
-    tolerances of the STRICT result."""
+    tolerances of the STRICT result.  The STRICT engine on the bands names them, and -- it waits for nothing -- takes no
+    wavefront slots from an engine on the strips beside it."""
     from greb_climate_model_amd import abi, workload
     inp = workload.make_inputs(nx, ny)
     p = abi.default_params(ipx=nx - 3, ipy=max(2, (3 * ny) // 4))
@@ -765,7 +767,7 @@ def test_row_strips_on_other_384_and_192_wide_grids(eng_mod, nx, ny):
     out = {}
     for label, kw in (("bands", dict(strict=True)), ("strips", dict(strict=True, row_strips=True, persistent=True)), ("fast", dict())):
         e = eng_mod.Engine(inp, p, n_members=2, **kw)
-        assert e.describe()["engine"] == "row strips"
+        assert e.describe()["engine"] == ("latitude bands" if label == "bands" else "row strips")
         yf = e.flux_correction(1)
         mon, yr = e.run(1, co2)
         e.close()
@@ -775,3 +777,14 @@ def test_row_strips_on_other_384_and_192_wide_grids(eng_mod, nx, ny):
         assert np.array_equal(a, b)
     _check_run(out["fast"][0][1, 0], out["bands"][0][1, 0].astype(np.float64), f"{nx}x{ny} fast vs strict")
     assert rms(out["fast"][0][0, 0, 11, 0], out["fast"][0][1, 0, 11, 0]) > 1e-2  # the members differ (CO2)
+    granted = []
+    for beside in (False, True):  # an engine on the strips alone, and beside a STRICT engine on the bands
+        bands = eng_mod.Engine(inp, p, n_members=2, strict=True) if beside else None
+        strips = eng_mod.Engine(inp, p, n_members=2)
+        strips.flux_correction(1)
+        granted.append(strips.describe()["wavefront_slots_granted"])
+        strips.close()
+        if bands:
+            assert "wavefront_slots_granted" not in bands.describe(), bands.describe()
+            bands.close()
+    assert granted[0] == granted[1] > 0, granted

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_workgroup_i_and_i_plus_n_simd_share_a_simd_on_an_idle_device():
     """step_rows_tasks / circ_rows_tasks pair the two tasks of a SIMD ("dearest with cheapest") on the OBSERVATION that
     workgroup i of a launch of single-wavefront workgroups lands on SIMD i mod n_simd when the device is otherwise idle
-    (greb_step_rows.hip).  Performance only, never correctness -- but if the dispatcher stops doing it the pairing is
+    (greb_strip_order.cpp: deal_strips).  Performance only, never correctness -- but if the dispatcher stops doing it the pairing is
     dealt blind and nothing else would say so.  Read from HW_REG_HW_ID / XCC_ID per task (tools/step_timeline.py)."""
     from greb_climate_model_amd import build
     if not os.path.exists(build.LIB_TUNING):
@@ -67,10 +67,10 @@ print("closed")
 
 
 def test_the_one_launch_circulation_pairs_the_tasks_its_order_means_to_pair():
-    """circ_rows_tasks pairs the two tasks of a SIMD ("dearest with cheapest").  The one-launch kernel runs four tasks per
-    workgroup, one per SIMD of the workgroup's compute unit; what was OBSERVED and is relied on for speed only: the second
-    workgroup on a compute unit starts one SIMD further on, so task 4c + w shares its SIMD with task n_simd + 4c + (w + 3)
-    mod 4 -- the order is built for exactly that.  Read from HW_REG_HW_ID / XCC_ID per task (tools/circ_timeline.py)."""
+    """circ_rows_tasks (greb_strip_order.cpp) pairs the two tasks of a SIMD ("dearest with cheapest").  The one-launch
+    kernel runs four tasks per workgroup, one per SIMD of the workgroup's compute unit; what was OBSERVED and is relied on
+    for speed only: the second workgroup on a compute unit starts one SIMD further on, so task 4c + w shares its SIMD with
+    task n_simd + 4c + (w + 3) mod 4 -- the order is built for exactly that.  Read from HW_REG_HW_ID / XCC_ID per task (tools/circ_timeline.py)."""
     from greb_climate_model_amd import build
     if not os.path.exists(build.LIB_TUNING):
         pytest.skip("no tuning library in this tree")

@@ -1,4 +1,4 @@
-"""The launch order of the 384-wide diffusion sweep (greb_rows.hip: rows_tasks) is a SPEED choice -- interleaved chain
+"""The launch order of the 384-wide diffusion sweep (greb_strip_order.cpp: rows_tasks) is a SPEED choice -- interleaved chain
 and streaming strips, ever shorter strips for the fields launched last -- but it must be a partition: every latitude
 row of every field is written by exactly one task.  Host-only entry point, no GPU needed."""
 import numpy as np
@@ -48,7 +48,7 @@ def test_other_grids_keep_the_band_kernel():
 
 @pytest.mark.parametrize("n_members", [1, 3, 8, 40, 62])
 def test_substep_order_is_a_partition_in_one_round(n_members):
-    """The engine's row-strip sub-step (greb_step_rows.hip: step_rows_tasks): every row of every (member, tracer) field
+    """The engine's row-strip sub-step (greb_strip_order.cpp: step_rows_tasks): every row of every (member, tracer) field
     exactly once -- with per-member diffusivities, i.e. different sub-cycle tables per member --, never more tasks than
     the chip has wavefront slots (2 048: a task started late ends the launch late), and the two tasks that share a SIMD
     (i and i + 1 024) never both hold a 232-sweep polar row; with a SIMD per task the dearest strips lead the launch."""
@@ -75,7 +75,7 @@ def test_substep_order_is_a_partition_in_one_round(n_members):
 
 @pytest.mark.parametrize("n_members,slots", [(1, 2048), (3, 2048), (8, 2048), (40, 2048), (62, 2048), (62, 1984), (2, 64), (5, 200)])
 def test_circulation_plan_is_a_partition_with_every_dependency_in_it(n_members, slots):
-    """The one-launch circulation call (greb_circ_rows.hip: circ_rows_tasks; src/greb.f90:546-550): every row of every
+    """The one-launch circulation call (greb_strip_order.cpp: circ_rows_tasks; src/greb.f90:546-550): every row of every
     field is owned by exactly one task; there are never more tasks than the wavefront slots given (the launch waits inside
     the kernel for its own tasks: all of them must be resident at once); rows with >= 64 dependent diffusion sweeps are
     chain tasks of one row; and the dependency table is complete and minimal: a task lists exactly the owners of the rows
