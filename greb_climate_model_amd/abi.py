@@ -44,6 +44,15 @@ class GrebMemberOverrides(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("da_ice", "a_no_ice", "a_cloud", "kappa")]
 
 
+class GrebMemberConfig(C.Structure):
+    """struct greb_member_config: a member as a full namelist plus its GREB_X_* switches."""
+    _fields_ = [("p", GrebParams), ("switches", C.c_uint32)]
+
+
+# what a member may NOT change (it feeds data every member shares): greb_engine_create_members rejects a difference
+MEMBER_SHARED = ("pi", "z_air", "z_vapor", "dt", "dt_crcl", "ipx", "ipy", "year0")
+
+
 def default_params(**over) -> GrebParams:
     """Reference defaults (src/greb.f90:49-53,68-104), constants folded in fp32 like the compiler."""
     f = np.float32

@@ -77,13 +77,11 @@ void compute_row_tables(const greb_params& p, float kappa, int nx, int ny, RowTa
   }
 }
 
-Phys make_phys(const greb_params& p, const greb_member_overrides* o) {
+// a member's namelist (greb_member_config::p) -> what the kernels read
+Phys make_phys(const greb_params& p) {
   Phys P;
-  auto pick = [](float base, float ov) { return std::isnan(ov) ? base : ov; };
   P.sig = p.sig; P.ct_sens = p.ct_sens;
-  P.da_ice = o ? pick(p.da_ice, o->da_ice) : p.da_ice;
-  P.a_no_ice = o ? pick(p.a_no_ice, o->a_no_ice) : p.a_no_ice;
-  P.a_cloud = o ? pick(p.a_cloud, o->a_cloud) : p.a_cloud;
+  P.da_ice = p.da_ice; P.a_no_ice = p.a_no_ice; P.a_cloud = p.a_cloud;
   P.Tl_ice1 = p.Tl_ice1; P.Tl_ice2 = p.Tl_ice2; P.To_ice1 = p.To_ice1; P.To_ice2 = p.To_ice2;
   P.co_turb = p.co_turb; P.ce = p.ce; P.cq_latent = p.cq_latent; P.cq_rain = p.cq_rain;
   P.z_air = p.z_air; P.r_qviwv = p.r_qviwv; P.rho_air = p.rho_air;
@@ -122,8 +120,13 @@ struct greb_engine {
   greb_params p{};
   int nx = 0, ny = 0, np = 0, nm = 0, device = 0;
   bool strict = false;
-  unsigned xsw = 0; // sensitivity-experiment switches (GREB_X_*)
-  bool shared_corr = true; // all members share physics -> one flux-correction set
+  unsigned xsw = 0; // sensitivity-experiment switches (GREB_X_*) of every member, where they are uniform
+  std::vector<unsigned> h_xsw;    // [nm] each member's switches
+  bool xsw_uniform = true;        // all equal: the kernels take `xsw`; else the per-member words on the device
+  unsigned* xsw_dev = nullptr;    // [nm], current whenever !xsw_uniform
+  float* co2_flux_dev = nullptr;  // [nm] flux-phase CO2 where a member's differs from the engine-wide value (else null)
+  int n_phys_sets = 1;            // distinct physics parameter sets among the members (describe)
+  bool shared_corr = true; // all members alike (physics, kappa, co2_flux, switches) -> one flux-correction set
   bool fused = true;       // every member has the 96x48 default sub-cycling layout -> fused member kernel
   float *Xa = nullptr, *Xb = nullptr, *red = nullptr, *W2 = nullptr; // any-grid (multi-launch) engine work arrays
   hipStream_t stream = nullptr;
@@ -185,11 +188,58 @@ MemberArgs base_args(greb_engine* e) {
   a.nsub = tuning_int("GREB_DEBUG_NSUB", a.nsub); // -DGREB_TUNING builds only
   a.co2_flux = e->p.co2_flux;
   a.ipx = e->p.ipx; a.ipy = e->p.ipy;
-  a.xsw = e->xsw;
+  a.xsw = e->xsw_uniform ? e->xsw : 0u;
+  a.xsw_m = e->xsw_uniform ? nullptr : e->xsw_dev;
+  a.co2_flux_m = e->co2_flux_dev;
   a.stamps = e->stamps;
   a.dbg = tuning_int("GREB_DEBUG_PHYS", 0);
-  if (e->xsw & GREB_X_NO_CIRCULATION) a.nsub = 0; // no transport at all: the tracers come back unchanged
+  // no transport at all where EVERY member is without circulation: the tracers come back unchanged.  A member without
+  // it beside members with it does zero sub-steps of its own (fused kernel) or drops its increments (point physics).
+  unsigned all = GREB_X_NO_CIRCULATION;
+  for (unsigned x : e->h_xsw) all &= x;
+  if (all) a.nsub = 0;
   return a;
+}
+
+// vapour diffused but not advected (GREB_X_VAPOR_DIFFUSION_ONLY): on the any-grid engine a property of the launch, so
+// every member has it or none (checked where switches are set)
+bool calm_vapor(const greb_engine* e) { return (e->h_xsw[0] & GREB_X_VAPOR_DIFFUSION_ONLY) != 0; }
+
+// the transport kernels of the any-grid engine run all members of a launch alike
+int check_transport_switches(greb_engine* e, const char* who, bool fused, const unsigned* sw, int n) {
+  if (fused) return 0;
+  for (int m = 1; m < n; ++m)
+    if ((sw[m] ^ sw[0]) & GREB_X_VAPOR_DIFFUSION_ONLY)
+      return fail(e, GREB_E_UNSUPPORTED,
+                  std::string(who) + ": member " + std::to_string(m) + " differs from member 0 in GREB_X_VAPOR_DIFFUSION_ONLY, "
+                  "which the any-grid engine applies to a whole launch -- run the two groups as two engines beside each "
+                  "other (ensemble.run_beside)");
+  return 0;
+}
+
+bool all_equal(const unsigned* sw, int n) {
+  for (int m = 1; m < n; ++m) if (sw[m] != sw[0]) return false;
+  return true;
+}
+
+// the greb_params fields that feed data shared by every member (row-table geometry, wz_air / wz_vapor, the clock)
+int check_member_config(const char* who, const greb_params& p, const greb_member_config& c, int m) {
+  const char* bad = nullptr;
+  auto differ = [](float a, float b) { return std::memcmp(&a, &b, sizeof(float)) != 0; }; // (bitwise: a NaN equals itself)
+  if (differ(c.p.pi, p.pi)) bad = "pi";
+  else if (differ(c.p.z_air, p.z_air)) bad = "z_air";
+  else if (differ(c.p.z_vapor, p.z_vapor)) bad = "z_vapor";
+  else if (c.p.dt != p.dt) bad = "dt";
+  else if (c.p.dt_crcl != p.dt_crcl) bad = "dt_crcl";
+  else if (c.p.ipx != p.ipx) bad = "ipx";
+  else if (c.p.ipy != p.ipy) bad = "ipy";
+  else if (c.p.year0 != p.year0) bad = "year0";
+  if (bad)
+    return fail(nullptr, GREB_E_INVALID, std::string(who) + ": member " + std::to_string(m) + ": " + bad +
+                                             " differs from the engine-wide greb_params (it feeds data every member shares)");
+  if (c.switches & ~0xffu)
+    return fail(nullptr, GREB_E_INVALID, std::string(who) + ": member " + std::to_string(m) + ": unknown switch bits");
+  return 0;
 }
 
 int ensure(greb_engine* e, float** buf, size_t* cap, size_t n) {
@@ -326,16 +376,16 @@ int run_year(greb_engine* e, const MemberArgs& a, int nrun) {
     }
     if (form == 2) {
       HIP_TRY(e, launch_circulation_rows(e->Xa, e->Xb, e->W2, e->uclim + off, e->vclim + off, e->tabs, plan->circ, e->cus * 4, e->nx, e->ny,
-                                         a.nsub, e->strict, e->stream, (e->xsw & GREB_X_VAPOR_DIFFUSION_ONLY) != 0));
+                                         a.nsub, e->strict, e->stream, calm_vapor(e)));
       if (a.nsub & 1) cur = e->Xb;
     } else
     for (int tt = 0; tt < a.nsub; ++tt) {
       if (plan)
         HIP_TRY(e, launch_substep_rows(cur, e->W2, e->uclim + off, e->vclim + off, nxt, e->tabs, e->tab_index, plan->step_tasks,
-                                       plan->head, plan->n_step, e->cus * 4, e->nx, e->ny, e->strict, e->stream, (e->xsw & GREB_X_VAPOR_DIFFUSION_ONLY) != 0));
+                                       plan->head, plan->n_step, e->cus * 4, e->nx, e->ny, e->strict, e->stream, calm_vapor(e)));
       else
         HIP_TRY(e, launch_substep_fused(cur, e->W2, e->uclim + off, e->vclim + off, nxt, e->tabs, e->tab_index, e->nx,
-                                        e->ny, nrun, e->strict, e->stream, (e->xsw & GREB_X_VAPOR_DIFFUSION_ONLY) != 0));
+                                        e->ny, nrun, e->strict, e->stream, calm_vapor(e)));
       float* t = cur; cur = nxt; nxt = t;
     }
     MemberArgs b = a;
@@ -389,27 +439,39 @@ const char* greb_device_info(int device) {
   return s.c_str();
 }
 
-int greb_engine_create(const greb_params* p, int nx, int ny, const greb_fields* f, int n_members,
-                       const greb_member_overrides* overrides, int device, unsigned flags, greb_engine** out) {
-  if (!p || !f || !out || n_members < 1 || nx < 12 || (nx & 3) || ny < 5 || ny > kMaxNy)
-    return fail(nullptr, GREB_E_INVALID, "greb_engine_create: bad argument");
+} // extern "C"
+
+namespace {
+// greb_engine_create_members, and greb_engine_create through it (`who` names the entry in messages)
+int create_engine(const char* who, const greb_params* p, int nx, int ny, const greb_fields* f, int n_members,
+                  const greb_member_config* members, int device, unsigned flags, greb_engine** out) {
+  if (!p || !f || !out || !members || n_members < 1 || nx < 12 || (nx & 3) || ny < 5 || ny > kMaxNy)
+    return fail(nullptr, GREB_E_INVALID, std::string(who) + ": bad argument");
+  for (int m = 0; m < n_members; ++m)
+    if (int rc = check_member_config(who, *p, members[m], m)) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
-    return fail(nullptr, GREB_E_NOGPU, "greb_engine_create: no HIP device (the engine has no CPU path)");
+    return fail(nullptr, GREB_E_NOGPU, std::string(who) + ": no HIP device (the engine has no CPU path)");
   bool fused = true;
+  std::vector<unsigned> switches((size_t)n_members);
   for (int m = 0; m < n_members; ++m) {
-    const float kap = (overrides && !std::isnan(overrides[m].kappa)) ? overrides[m].kappa : p->kappa;
-    RowTables t; compute_row_tables(*p, kap, nx, ny, t);
+    RowTables t; compute_row_tables(*p, members[m].p.kappa, nx, ny, t);
     fused = fused && member_layout_supported(t, nx, ny);
+    switches[(size_t)m] = members[m].switches;
   }
+  fused = fused && !(flags & GREB_F_MULTILAUNCH);
   if (p->ipx < 1 || p->ipx > nx || p->ipy < 1 || p->ipy > ny)
-    return fail(nullptr, GREB_E_INVALID, "greb_engine_create: ipx/ipy outside the grid");
+    return fail(nullptr, GREB_E_INVALID, std::string(who) + ": ipx/ipy outside the grid");
+  if (int rc = check_transport_switches(nullptr, who, fused, switches.data(), n_members)) return rc;
   greb_engine* e = new (std::nothrow) greb_engine();
   if (!e) return fail(nullptr, GREB_E_INVALID, "out of host memory");
   *out = e; // returned even on failure so last_error can be read; caller destroys
   e->p = *p; e->nx = nx; e->ny = ny; e->np = nx * ny; e->nm = n_members; e->device = device;
   e->strict = (flags & GREB_F_STRICT) != 0;
-  e->fused = fused && !(flags & GREB_F_MULTILAUNCH);
+  e->fused = fused;
+  e->h_xsw = switches;
+  e->xsw_uniform = all_equal(switches.data(), n_members);
+  e->xsw = e->xsw_uniform ? switches[0] : 0u;
   const size_t np = (size_t)e->np, n3 = np * kNT, nm = (size_t)n_members;
   HIP_TRY(e, hipSetDevice(device));
   HIP_TRY(e, hipStreamCreate(&e->stream));
@@ -454,10 +516,17 @@ int greb_engine_create(const greb_params* p, int nx, int ny, const greb_fields* 
   std::vector<int> tab_index(nm), corr_index(nm);
   std::vector<float> kappas;
   e->shared_corr = true;
+  std::vector<float> co2_flux(nm);
+  bool own_co2_flux = false;
+  std::vector<size_t> phys_sets; // first member of every distinct physics set
   for (size_t m = 0; m < nm; ++m) {
-    const greb_member_overrides* o = overrides ? overrides + m : nullptr;
-    e->h_phys[m] = make_phys(*p, o);
-    const float kap = (o && !std::isnan(o->kappa)) ? o->kappa : p->kappa;
+    e->h_phys[m] = make_phys(members[m].p);
+    const float kap = members[m].p.kappa;
+    co2_flux[m] = members[m].p.co2_flux;
+    own_co2_flux = own_co2_flux || !(co2_flux[m] == p->co2_flux);
+    size_t ps = 0;
+    for (; ps < phys_sets.size(); ++ps) if (!std::memcmp(&e->h_phys[phys_sets[ps]], &e->h_phys[m], sizeof(Phys))) break;
+    if (ps == phys_sets.size()) phys_sets.push_back(m);
     size_t ti = 0;
     for (; ti < kappas.size(); ++ti) if (kappas[ti] == kap) break;
     if (ti == kappas.size()) {
@@ -466,8 +535,16 @@ int greb_engine_create(const greb_params* p, int nx, int ny, const greb_fields* 
       e->h_tabs.push_back(t);
     }
     tab_index[m] = (int)ti;
-    if (o && !(std::isnan(o->da_ice) && std::isnan(o->a_no_ice) && std::isnan(o->a_cloud) && std::isnan(o->kappa)))
-      e->shared_corr = false;
+    if (ps != 0 || ti != 0 || !(co2_flux[m] == co2_flux[0]) || switches[m] != switches[0]) e->shared_corr = false;
+  }
+  e->n_phys_sets = (int)phys_sets.size();
+  if (own_co2_flux) {
+    HIP_TRY(e, dev_alloc(&e->co2_flux_dev, nm));
+    HIP_TRY(e, hipMemcpy(e->co2_flux_dev, co2_flux.data(), nm * sizeof(float), hipMemcpyHostToDevice));
+  }
+  if (!e->xsw_uniform) {
+    HIP_TRY(e, dev_alloc(&e->xsw_dev, nm));
+    HIP_TRY(e, hipMemcpy(e->xsw_dev, switches.data(), nm * sizeof(unsigned), hipMemcpyHostToDevice));
   }
   for (size_t m = 0; m < nm; ++m) corr_index[m] = e->shared_corr ? 0 : (int)m;
   HIP_TRY(e, dev_alloc(&e->phys, nm));
@@ -524,6 +601,32 @@ int greb_engine_create(const greb_params* p, int nx, int ny, const greb_fields* 
   }
   return 0;
 }
+} // namespace
+
+extern "C" {
+
+int greb_engine_create_members(const greb_params* p, int nx, int ny, const greb_fields* f, int n_members,
+                               const greb_member_config* members, int device, unsigned flags, greb_engine** out) {
+  return create_engine("greb_engine_create_members", p, nx, ny, f, n_members, members, device, flags, out);
+}
+
+// the four override slots expanded into full member configurations: NaN keeps the engine-wide value, no switches
+int greb_engine_create(const greb_params* p, int nx, int ny, const greb_fields* f, int n_members,
+                       const greb_member_overrides* overrides, int device, unsigned flags, greb_engine** out) {
+  if (!p || n_members < 1) return fail(nullptr, GREB_E_INVALID, "greb_engine_create: bad argument");
+  std::vector<greb_member_config> members((size_t)n_members);
+  auto pick = [](float base, float ov) { return std::isnan(ov) ? base : ov; };
+  for (int m = 0; m < n_members; ++m) {
+    greb_member_config& c = members[(size_t)m];
+    c.p = *p; c.switches = 0;
+    if (!overrides) continue;
+    c.p.da_ice = pick(p->da_ice, overrides[m].da_ice);
+    c.p.a_no_ice = pick(p->a_no_ice, overrides[m].a_no_ice);
+    c.p.a_cloud = pick(p->a_cloud, overrides[m].a_cloud);
+    c.p.kappa = pick(p->kappa, overrides[m].kappa);
+  }
+  return create_engine("greb_engine_create", p, nx, ny, f, n_members, members.data(), device, flags, out);
+}
 
 int greb_engine_destroy(greb_engine* e) {
   if (!e) return 0;
@@ -531,7 +634,7 @@ int greb_engine_destroy(greb_engine* e) {
   void* ptrs[] = {e->z_topo, e->glacier, e->sw_solar, e->tclim, e->qclim, e->uclim, e->vclim, e->mldclim,
                   e->cldclim, e->swetclim, e->toclim, e->z_ocean, e->wz_air, e->wz_vapor, e->state, e->acc,
                   e->corr, e->corr_index, e->tab_index, e->tabs, e->phys, e->co2_dev, e->monthly_dev, e->yearly_dev,
-                  e->Xa, e->Xb, e->red, e->W2};
+                  e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev};
   for (void* q : ptrs) if (q) (void)hipFree(q);
   for (auto& kv : e->plans) free_plan(kv.second);
   if (e->call != greb_engine::kCallNever) ledger_release(e);
@@ -661,6 +764,9 @@ const char* greb_engine_describe(greb_engine* e) {
   std::snprintf(buf, sizeof(buf), "{\"grid\": [%d, %d], \"members\": %d, \"arithmetic\": \"%s\", \"engine\": \"%s\"", e->nx, e->ny, e->nm,
                 e->strict ? "strict" : "fast", e->fused ? "fused member kernel" : (e->strips ? "row strips" : "latitude bands"));
   s = buf;
+  std::snprintf(buf, sizeof(buf), ", \"member_switches\": \"%s\", \"correction_sets\": %d, \"physics_sets\": %d",
+                e->xsw_uniform ? "uniform" : "per member", e->shared_corr ? 1 : e->nm, e->n_phys_sets);
+  s += buf;
   if (e->call != greb_engine::kCallNever) {
     std::snprintf(buf, sizeof(buf), ", \"wavefront_slots_granted\": %d, \"circulation\": [", e->slots_granted);
     s += buf;
@@ -718,6 +824,57 @@ unsigned greb_log_exp_switches(int le) {
 int greb_engine_set_experiment(greb_engine* e, unsigned switches) {
   if (!e || (switches & ~0xffu)) return fail(e, GREB_E_INVALID, "set_experiment: unknown switch bits");
   e->xsw = switches;
+  e->h_xsw.assign((size_t)e->nm, switches);
+  e->xsw_uniform = true; // (the correction sets stay as they are: shared or one per member)
+  return 0;
+}
+
+int greb_engine_set_member_experiments(greb_engine* e, const uint32_t* switches) {
+  if (!e || !switches) return fail(e, GREB_E_INVALID, "set_member_experiments: bad argument");
+  const size_t nm = (size_t)e->nm;
+  for (size_t m = 0; m < nm; ++m)
+    if (switches[m] & ~0xffu)
+      return fail(e, GREB_E_INVALID, "set_member_experiments: member " + std::to_string(m) + ": unknown switch bits");
+  std::vector<unsigned> sw(switches, switches + nm);
+  if (int rc = check_transport_switches(e, "set_member_experiments", e->fused, sw.data(), e->nm)) return rc;
+  const bool uniform = all_equal(sw.data(), e->nm);
+  HIP_TRY(e, hipSetDevice(e->device));
+  // Everything that can fail is done on NEW buffers; the engine changes only once they are complete (its correction
+  // index, one small copy, is the last step that can fail).
+  unsigned* xsw_dev = nullptr;
+  float* corr = nullptr;
+  const size_t set = (size_t)3 * kNT * e->np;
+  auto step = [&](hipError_t err, const char* what) -> int {
+    if (err == hipSuccess) return 0;
+    if (corr) (void)hipFree(corr);
+    if (xsw_dev) (void)hipFree(xsw_dev);
+    return fail(e, (int)err, std::string("set_member_experiments: ") + what + ": " + hipGetErrorString(err));
+  };
+  if (!uniform) {
+    if (int rc = step(dev_alloc(&xsw_dev, nm), "hipMalloc")) return rc;
+    if (int rc = step(hipMemcpy(xsw_dev, sw.data(), nm * sizeof(unsigned), hipMemcpyHostToDevice), "hipMemcpy")) return rc;
+    if (e->shared_corr && nm > 1) { // members that now differ need a correction set each: copies of the shared one
+      if (int rc = step(hipStreamSynchronize(e->stream), "hipStreamSynchronize")) return rc;
+      if (int rc = step(dev_alloc(&corr, nm * set), "hipMalloc of the members' correction sets")) return rc;
+      for (size_t m = 0; m < nm; ++m)
+        if (int rc = step(hipMemcpy(corr + m * set, e->corr, set * sizeof(float), hipMemcpyDeviceToDevice), "hipMemcpy")) return rc;
+      std::vector<int> corr_index(nm);
+      for (size_t m = 0; m < nm; ++m) corr_index[m] = (int)m;
+      if (int rc = step(hipMemcpy(e->corr_index, corr_index.data(), nm * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy")) return rc;
+    }
+  }
+  if (corr) {
+    (void)hipFree(e->corr);
+    e->corr = corr;
+    e->shared_corr = false;
+  }
+  if (xsw_dev) {
+    if (e->xsw_dev) (void)hipFree(e->xsw_dev);
+    e->xsw_dev = xsw_dev;
+  }
+  e->h_xsw = sw;
+  e->xsw_uniform = uniform;
+  e->xsw = uniform ? sw[0] : 0u;
   return 0;
 }
 
@@ -953,7 +1110,7 @@ int greb_engine_point_physics(greb_engine* e, int ityr, float co2, const float* 
   a.z_topo = e->z_topo; a.glacier = e->glacier; a.sw_solar = e->sw_solar; a.tclim = e->tclim;
   a.uclim = e->uclim; a.vclim = e->vclim; a.mldclim = e->mldclim; a.cldclim = e->cldclim; a.swetclim = e->swetclim;
   a.z_ocean = e->z_ocean; a.wz_air = e->wz_air; a.phys = e->h_phys[0]; a.in5 = in.p; a.out15 = out.p;
-  a.xsw = e->xsw; a.qclim = e->qclim;
+  a.xsw = e->h_xsw[0]; a.qclim = e->qclim; // (member 0's physics and switches)
   HIP_TRY(e, launch_point_physics(a, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   HIP_TRY(e, hipMemcpy(out15, out.p, 15 * np * 4, hipMemcpyDeviceToHost));

@@ -66,7 +66,11 @@ struct MemberArgs {
   unsigned long long* stamps;
   int dbg;               // -DGREB_TUNING builds only: timing experiments (results wrong): bit 0 point physics without the
                          // accumulators, bit 1 without the state write-back, bit 2 a single pass instead of three
+  // per-member experiment control (read by the switch-aware instantiations only; greb_physics_step.h: member_switches)
+  const unsigned* xsw_m;   // [nm] experiment switches of each member; null: xsw applies to all
+  const float* co2_flux_m; // [nm] flux-phase CO2 of each member; null: co2_flux applies to all
 };
+
 
 // fused engine (greb_member.hip): 96x48 with the default sub-cycling layout -- rows 0-9 and 38-47
 // sub-cycled, only the two polar rows iterating; whole member resident in one CU

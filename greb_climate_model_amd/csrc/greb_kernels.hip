@@ -408,13 +408,13 @@ __global__ __launch_bounds__(256) void physics_step_kernel(MemberArgs a, const f
   if (qd >= np / 4) return;
   const StepClock ck = step_clock<FLUX>(a, a.it0, np);
   const Phys P = a.phys[m];
-  const float co2 = FLUX ? a.co2_flux : a.co2[(size_t)m * a.co2_stride + a.co2_year0];
+  const float co2 = FLUX ? (a.co2_flux_m ? a.co2_flux_m[m] : a.co2_flux) : a.co2[(size_t)m * a.co2_stride + a.co2_year0];
   float* state = a.state + (size_t)m * 5 * np;
   float* acc = a.acc + (size_t)m * 6 * np;
   float* corr = a.corr + (size_t)a.corr_index[m] * 3 * kNT * np;
   const f4 xTa = ld4(X + ((size_t)m * 2) * np + 4 * qd), xq = ld4(X + ((size_t)m * 2 + 1) * np + 4 * qd);
   f4 oTa, oq, tsm;
-  physics_quad<STRICT, FLUX, EXP>(a, P, m, qd, ck, co2, state, acc, corr, xTa, xq, oTa, oq, tsm);
+  physics_quad<STRICT, FLUX, EXP>(a, P, m, qd, ck, co2, state, acc, corr, xTa, xq, oTa, oq, tsm, EXP ? member_switches(a, m) : 0u);
   st4(Xout + ((size_t)m * 2) * np + 4 * qd, oTa);
   st4(Xout + ((size_t)m * 2 + 1) * np + 4 * qd, oq);
   if (ck.ityr == kNT) st4(red + (size_t)m * np + 4 * qd, tsm);
@@ -423,7 +423,7 @@ __global__ __launch_bounds__(256) void physics_step_kernel(MemberArgs a, const f
 hipError_t launch_physics_step(const MemberArgs& a, const float* X, float* Xout, float* red, int n_members,
                                bool strict, hipStream_t s) {
   void (*kern)(MemberArgs, const float*, float*, float*);
-  if (a.xsw) {
+  if (a.xsw || a.xsw_m) {
     if (a.flux_phase) kern = strict ? physics_step_kernel<true, true, true> : physics_step_kernel<false, true, true>;
     else kern = strict ? physics_step_kernel<true, false, true> : physics_step_kernel<false, false, true>;
   } else if (a.flux_phase) kern = strict ? physics_step_kernel<true, true, false> : physics_step_kernel<false, true, false>;

@@ -783,7 +783,11 @@ hipError_t launch_circulation_g96(const float* X, const float* wz, const float* 
 // ---------------------------------------------------------------------------------------------
 // the member kernel
 // ---------------------------------------------------------------------------------------------
-// EXP: honour the sensitivity-experiment switches a.xsw; the default instantiation has none of it
+// EXP: honour the member's sensitivity-experiment switches (a.xsw, or a.xsw_m[m] where the members of a
+// launch differ); the default instantiation has none of it.  The switch word is read once and is block-uniform: it drives
+// the point physics, the vapour-diffusion-only form of the sub-steps and the member's OWN sub-step count -- a member
+// without circulation does none while its neighbours do 24 (every wave of a workgroup runs the same count, so the
+// barriers inside Circ::substeps stay matched).
 template <bool STRICT, bool FLUX, bool EXP>
 __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
   extern __shared__ __align__(16) float lds_raw[];
@@ -804,6 +808,10 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
   for (int i = tid; i < NP / 4; i += kThreads)
     st8(lds + kOffX + (i / NQ) * RS, i % NQ, zip(ld4(state + NP + 4 * i), ld4(state + 3 * NP + 4 * i))); // (Tair, q)
   int cur = 0;
+  const unsigned xsw = EXP ? member_switches(a, m) : 0u;
+  const int nsub = (EXP && (xsw & kXNoCirc)) ? 0 : a.nsub;
+  // the flux-phase CO2 (:104) may be the member's own; read here, so that the step loop reads nothing new
+  const float co2_flux = FLUX ? (a.co2_flux_m ? a.co2_flux_m[m] : a.co2_flux) : 0.f;
   __syncthreads();
 #ifdef GREB_TUNING
   // diagnostic stamps (tools/stamp_member.py): shader-clock cycles this wave spent in each phase of the launch, its
@@ -831,16 +839,16 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 
     // ---- circulation of Tair and q: 24 sub-steps (:543-550)
 #ifdef GREB_TUNING
-    circ.substeps(lds, cur, a.nsub, 0, EXP && (a.xsw & kXQDiffOnly), stamp, &st_busy);
+    circ.substeps(lds, cur, nsub, 0, EXP && (xsw & kXQDiffOnly), stamp, &st_busy);
 #else
-    circ.substeps(lds, cur, a.nsub, 0, EXP && (a.xsw & kXQDiffOnly));
+    circ.substeps(lds, cur, nsub, 0, EXP && (xsw & kXQDiffOnly));
 #endif
-    cur ^= a.nsub & 1;
+    cur ^= nsub & 1;
     GREB_STAMP(t_c);
 
     // ---- point physics on the OLD state + Euler update (:254-268 / :328-361)
     const Phys P = a.phys[m];
-    const float co2 = FLUX ? a.co2_flux : a.co2[(size_t)m * a.co2_stride + a.co2_year0 + yr_rel]; // :924
+    const float co2 = FLUX ? co2_flux : a.co2[(size_t)m * a.co2_stride + a.co2_year0 + yr_rel]; // :924
     lfloat* Xf = lds + kOffX + cur * XB;       // the tracers after the 24 sub-steps
     lfloat* red = lds + kOffX + (cur ^ 1) * XB; // idle buffer: annual-mean reduction scratch
     // Each thread takes whole quads (4 consecutive longitudes): every load/store of the ~26
@@ -865,7 +873,7 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 #endif
       const q8 xpair = ld8(Xf + (qd / NQ) * RS, qd % NQ);
       f4 oTa, oq, tsm;
-      physics_quad<STRICT, FLUX, EXP>(a, P, m, qd, ck, co2, state, acc, corr, comp(xpair, 0), comp(xpair, 1), oTa, oq, tsm);
+      physics_quad<STRICT, FLUX, EXP>(a, P, m, qd, ck, co2, state, acc, corr, comp(xpair, 0), comp(xpair, 1), oTa, oq, tsm, xsw);
       st8(Xf + (qd / NQ) * RS, qd % NQ, zip(oTa, oq));
       if (ityr == kNT) st4(red + 4 * qd, tsm);
     }
@@ -909,7 +917,7 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
   if (stamp && (tid & 63) == 0) {
     unsigned long long* o = a.stamps + ((size_t)m * (kThreads / 64) + (tid >> 6)) * 8;
     o[0] = __builtin_amdgcn_s_memtime() - st_c0; o[1] = __builtin_amdgcn_s_memrealtime() - st_r0;
-    o[2] = st_wind; o[3] = st_circ; o[4] = st_busy; o[5] = st_phys; o[6] = (unsigned long long)a.nsteps; o[7] = (unsigned long long)a.nsub;
+    o[2] = st_wind; o[3] = st_circ; o[4] = st_busy; o[5] = st_phys; o[6] = (unsigned long long)a.nsteps; o[7] = (unsigned long long)nsub;
   }
 #endif
   // all five state fields were written back every step
@@ -918,7 +926,7 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 hipError_t launch_member_kernel(const MemberArgs& a, int n_members, bool strict, hipStream_t s) {
   if (a.nx != NX || a.ny != NY) return hipErrorInvalidValue;
   void (*kern)(MemberArgs);
-  if (a.xsw) { // sensitivity experiment: the switch-aware instantiation
+  if (a.xsw || a.xsw_m) { // sensitivity experiment (of every member or of some): the switch-aware instantiation
     if (a.flux_phase) kern = strict ? member_kernel<true, true, true> : member_kernel<false, true, true>;
     else kern = strict ? member_kernel<true, false, true> : member_kernel<false, false, true>;
   } else if (a.flux_phase) kern = strict ? member_kernel<true, true, false> : member_kernel<false, true, false>;

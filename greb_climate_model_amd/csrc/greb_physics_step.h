@@ -29,10 +29,17 @@ __device__ __forceinline__ StepClock step_clock(const MemberArgs& a, long long i
   return c;
 }
 
+// The experiment switches of member m (block-uniform): its own word where the launch carries one per member, else the
+// launch's.
+__device__ __forceinline__ unsigned member_switches(const MemberArgs& a, int m) {
+  return (unsigned)__builtin_amdgcn_readfirstlane((int)(a.xsw_m ? a.xsw_m[m] : a.xsw));
+}
+
 // One quad in three pieces -- load, compute, store -- so that a caller with several quads per thread can request the
 // next quad's operands BETWEEN the arithmetic of the current one and its stores (vector-memory operations retire in
 // order: loads issued behind a quad's stores wait for those stores as well).
-// EXP: the sensitivity-experiment switches a.xsw are honoured; false compiles them out.
+// EXP: the member's sensitivity-experiment switches `xsw` (member_switches) are honoured; false
+// compiles them out.
 struct PhysIn {
   f4 Ts, Ta, To, q, cap;                      // state
   f4 zt, gl, zo, ez;                          // static fields
@@ -49,10 +56,10 @@ struct PhysOut { // everything the stores need: the inputs are dead once this ex
 
 template <bool FLUX, bool EXP>
 __device__ __forceinline__ PhysIn physics_load(const MemberArgs& a, int qd, const StepClock& ck, const float* __restrict__ state,
-                                               const float* __restrict__ acc, const float* __restrict__ corr) {
+                                               const float* __restrict__ acc, const float* __restrict__ corr, unsigned xsw_member) {
   const int nx = a.nx, ny = a.ny, np = a.np, p0 = 4 * qd;
   const size_t off = ck.off, offm = ck.offm;
-  const unsigned xsw = EXP ? a.xsw : 0u;
+  const unsigned xsw = EXP ? xsw_member : 0u;
   PhysIn i;
   i.Ts = ld4(state + p0); i.Ta = ld4(state + np + p0); i.To = ld4(state + 2 * np + p0); i.q = ld4(state + 3 * np + p0);
   i.cap = ld4(state + 4 * np + p0);
@@ -84,8 +91,8 @@ __device__ __forceinline__ PhysIn physics_load(const MemberArgs& a, int qd, cons
 // xTa, xq: the tracers after the 24 circulation sub-steps
 template <bool STRICT, bool FLUX, bool EXP>
 __device__ __forceinline__ PhysOut physics_compute(const MemberArgs& a, const Phys& P, const PhysIn& in, float co2, const f4& xTa,
-                                                   const f4& xq) {
-  const unsigned xsw = EXP ? a.xsw : 0u;
+                                                   const f4& xq, unsigned xsw_member) {
+  const unsigned xsw = EXP ? xsw_member : 0u;
   PhysOut o;
   o.TF = o.qF = o.ToF = zero4();
 #pragma unroll
@@ -95,8 +102,12 @@ __device__ __forceinline__ PhysOut physics_compute(const MemberArgs& a, const Ph
     const float Ta1 = in.Ta.v[e], To1 = in.To.v[e], q1 = in.q.v[e], cap = in.cap.v[e];
     const float zt = in.zt.v[e], gl = in.gl.v[e], ez = in.ez.v[e], tcl = in.tcl.v[e], cld = in.cld.v[e], mld = in.mld.v[e];
     if (EXP && !FLUX && (xsw & kXSstPlus1) && zt < 0.0f) Ts1 = in.tclp.v[e] + 1.0f; // greb.original.model.f90:226
-    const float dTa_crcl = xTa.v[e] - Ta1; // :551
-    const float dq_crcl = (EXP && (xsw & kXNoQTransport)) ? 0.f : xq.v[e] - q1; // greb.original.model.f90:554-555
+    // A member without circulation (greb.original.model.f90:553) whose launch transported it with the others -- the band
+    // and strip kernels run every member alike -- drops both increments here: +0, which is what its own zero sub-steps
+    // give (xTa == Ta1 bit for bit).
+    const bool calm = EXP && (xsw & kXNoCirc);
+    const float dTa_crcl = calm ? 0.f : xTa.v[e] - Ta1; // :551
+    const float dq_crcl = (calm || (EXP && (xsw & kXNoQTransport))) ? 0.f : xq.v[e] - q1; // greb.original.model.f90:554-555
     float albedo, sw, LWsurf, LWdown, em, Qlat, Qlat_air, dq_eva, dq_rain, dT_ocean, dTo;
     sw_radiation<STRICT>(P, Ts1, zt, gl, cld, in.solar, albedo, sw, xsw);
     lw_radiation<STRICT>(P, Ts1, Ta1, q1, co2, ez, cld, tcl, LWsurf, LWdown, em, xsw, in.qcl.v[e]);
@@ -191,9 +202,9 @@ template <bool STRICT, bool FLUX, bool EXP = false>
 __device__ __forceinline__ void physics_quad(const MemberArgs& a, const Phys& P, int m, int qd, const StepClock& ck,
                                              float co2, float* __restrict__ state, float* __restrict__ acc,
                                              float* __restrict__ corr, const f4& xTa, const f4& xq, f4& oTa_out,
-                                             f4& oq_out, f4& tsmn_mean) {
-  const PhysIn in = physics_load<FLUX, EXP>(a, qd, ck, state, acc, corr);
-  const PhysOut o = physics_compute<STRICT, FLUX, EXP>(a, P, in, co2, xTa, xq);
+                                             f4& oq_out, f4& tsmn_mean, unsigned xsw = 0u) {
+  const PhysIn in = physics_load<FLUX, EXP>(a, qd, ck, state, acc, corr, xsw);
+  const PhysOut o = physics_compute<STRICT, FLUX, EXP>(a, P, in, co2, xTa, xq, xsw);
   physics_store<FLUX>(a, m, qd, ck, o, state, acc, corr, tsmn_mean);
   oTa_out = o.Ta; oq_out = o.q;
 }

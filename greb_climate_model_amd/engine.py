@@ -55,7 +55,8 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_advection_batched", "greb_circulation_batched", "greb_diffusion_batched_dev",
            "greb_engine_point_physics", "greb_log_exp_switches", "greb_engine_set_experiment",
            "greb_ensemble_moments_dev", "greb_ensemble_quantiles_dev", "greb_engine_set_state", "greb_release_caches", "greb_diffusion_launch_order",
-           "greb_substep_launch_order", "greb_circulation_launch_plan", "greb_engine_describe"]
+           "greb_substep_launch_order", "greb_circulation_launch_plan", "greb_engine_describe",
+           "greb_engine_create_members", "greb_engine_set_member_experiments"]
 
 
 def _check(rc: int, h=None):
@@ -75,6 +76,33 @@ def log_exp_switches(log_exp: int) -> int:
     return int(f(int(log_exp)))
 
 
+def member_configs(params: abi.GrebParams, members):
+    """A list of dicts -> (greb_member_config * n).  Keys: any float field of greb_params (p_emi: ten values), plus
+    `switches` (GREB_X_* bits) or `log_exp` (mapped through log_exp_switches); missing keys take the engine-wide value."""
+    floats = set(abi.GrebParams.PHYSICS_NAMES) | {"co2_flux"}
+    arr = (abi.GrebMemberConfig * len(members))()
+    for c, d in zip(arr, members):
+        C.memmove(C.byref(c.p), C.byref(params), C.sizeof(abi.GrebParams))
+        c.switches = 0
+        if "switches" in d and "log_exp" in d:
+            raise GrebError(-1, "members: give `switches` or `log_exp`, not both")
+        for k, v in d.items():
+            if k == "switches":
+                c.switches = int(v)
+            elif k == "log_exp":
+                c.switches = log_exp_switches(int(v))
+            elif k == "p_emi":
+                if len(v) != 10:
+                    raise GrebError(-1, "members: p_emi takes ten values")
+                for i, x in enumerate(v):
+                    c.p.p_emi[i] = float(x)
+            elif k in floats:
+                setattr(c.p, k, float(v))
+            else:
+                raise GrebError(-1, f"members: unknown key {k!r}")
+    return arr
+
+
 def params_default() -> abi.GrebParams:
     p = abi.GrebParams()
     lib().greb_params_default(C.byref(p))
@@ -87,11 +115,18 @@ class Engine:
 
     def __init__(self, inp: workload.Inputs, params: abi.GrebParams | None = None, n_members: int = 1,
                  overrides=None, device: int = 0, strict: bool = False, multilaunch: bool = False,
-                 row_strips: bool = False, persistent: bool | None = None):
-        """persistent (384-wide grids): True = the circulation call as one launch (GREB_F_PERSISTENT), False = one launch per
+                 row_strips: bool = False, persistent: bool | None = None, members=None):
+        """members: one dict per member (member_configs: any float field of greb_params, `switches` or `log_exp`), for
+        ensembles whose members differ in more than the four `overrides` slots; mutually exclusive with `overrides`.
+        persistent (384-wide grids): True = the circulation call as one launch (GREB_F_PERSISTENT), False = one launch per
         sub-step (GREB_F_NO_PERSISTENT), None = the engine times both and keeps the faster."""
         L = lib()
         self.params = params or params_default()
+        if members is not None:
+            if overrides is not None:
+                raise GrebError(-1, "Engine: give `members` or `overrides`, not both")
+            members = list(members)
+            n_members = len(members)
         self.nx, self.ny, self.np, self.nm = inp.nx, inp.ny, inp.nx * inp.ny, n_members
         fields, self._keep = abi.make_fields(inp)
         ov = None
@@ -101,11 +136,15 @@ class Engine:
                 for k in ("da_ice", "a_no_ice", "a_cloud", "kappa"):
                     setattr(ov[i], k, float(o.get(k, float("nan"))))
         self.h = C.c_void_p()
-        rc = L.greb_engine_create(C.byref(self.params), inp.nx, inp.ny, C.byref(fields), n_members, ov, device,
-                                  (abi.F_STRICT if strict else 0) | (abi.F_MULTILAUNCH if multilaunch else 0) |
-                                 (abi.F_ROW_STRIPS if row_strips else 0) |
-                                  (0 if persistent is None else (abi.F_PERSISTENT if persistent else abi.F_NO_PERSISTENT)),
-                                  C.byref(self.h))
+        flags = ((abi.F_STRICT if strict else 0) | (abi.F_MULTILAUNCH if multilaunch else 0) |
+                 (abi.F_ROW_STRIPS if row_strips else 0) |
+                 (0 if persistent is None else (abi.F_PERSISTENT if persistent else abi.F_NO_PERSISTENT)))
+        if members is not None:
+            rc = L.greb_engine_create_members(C.byref(self.params), inp.nx, inp.ny, C.byref(fields), n_members,
+                                              member_configs(self.params, members), device, flags, C.byref(self.h))
+        else:
+            rc = L.greb_engine_create(C.byref(self.params), inp.nx, inp.ny, C.byref(fields), n_members, ov, device, flags,
+                                      C.byref(self.h))
         if rc != 0:
             msg = L.greb_engine_last_error(self.h).decode()
             if self.h:
@@ -177,6 +216,14 @@ class Engine:
     def set_experiment(self, switches: int):
         """Sensitivity-experiment switches (abi.X_*; log_exp_switches() maps the original's log_exp)."""
         _check(lib().greb_engine_set_experiment(self.h, C.c_uint(int(switches))), self.h)
+
+    def set_member_experiments(self, switches):
+        """One switch word per member.  Members that shared one flux-correction set and now differ each get a copy of
+        it (spin up once under the complete model, then let the members diverge)."""
+        sw = np.ascontiguousarray(switches, np.uint32)
+        if sw.shape != (self.nm,):
+            raise GrebError(-1, f"set_member_experiments: {self.nm} switch words expected")
+        _check(lib().greb_engine_set_member_experiments(self.h, sw.ctypes.data_as(C.POINTER(C.c_uint32))), self.h)
 
     def point_physics(self, ityr: int, co2: float, in5) -> np.ndarray:
         in5 = np.ascontiguousarray(in5, np.float32)

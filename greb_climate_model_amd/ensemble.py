@@ -33,14 +33,27 @@ def splitmix64(seed: int, n: int) -> np.ndarray:
 PERTURBED = ("da_ice", "a_no_ice", "a_cloud", "kappa")
 
 
-def perturbed_physics(n_members: int, params, seed: int = 20261004, spread: float = 0.1) -> np.ndarray:
+def perturbed_physics(n_members: int, params, seed: int = 20261004, spread: float = 0.1, names=PERTURBED) -> np.ndarray:
     """BASELINE config 5's members: albedo (da_ice, a_no_ice, a_cloud) and diffusivity (kappa) drawn uniformly within
     +-`spread` of the namelist value, member index as the stream position.  Returns float32
-    [n_members][4] in the order of greb_member_overrides -- what N separate `ens_id` processes with N different
-    &PHYSICS_PAR groups are in the reference (src/greb.f90:128-132,153)."""
-    u = splitmix64(seed, 4 * n_members).reshape(n_members, 4)
-    base = np.asarray([getattr(params, k) for k in PERTURBED], np.float64)
+    [n_members][len(names)]; with the default names that is the order of greb_member_overrides -- what N separate
+    `ens_id` processes with N different &PHYSICS_PAR groups are in the reference (src/greb.f90:128-132,153).  `names`: any
+    tuple of float fields of greb_params (engine.Engine(members=...) takes them all per member); member i draws the
+    stream positions len(names) * i ... of the same SplitMix64 stream."""
+    names = tuple(names)
+    u = splitmix64(seed, len(names) * n_members).reshape(n_members, len(names))
+    base = np.asarray([getattr(params, k) for k in names], np.float64)
     return (base[None] * (1.0 - spread + 2.0 * spread * u)).astype(np.float32)
+
+
+def switch_factorial(bits: int = 0xff) -> np.ndarray:
+    """Every combination of the experiment switches in `bits` (abi.X_*), ascending, uint32: the deconstruction of the
+    climate response by switching processes off as ONE ensemble -- 256 members for all eight switches, one per compute
+    unit of an MI355X (engine.Engine(members=[{"switches": s} for s in switch_factorial()]))."""
+    bits = int(bits)
+    if bits & ~0xff:
+        raise ValueError("switch_factorial: unknown switch bits")
+    return np.asarray([s for s in range(256) if not (s & ~bits)], np.uint32)
 
 
 def max_chain_sweeps(kappa: float, nx: int, ny: int, dt_crcl: float = 1800.0, pi: float = 3.1416) -> int:

@@ -18,6 +18,13 @@ module greb_c_api
      real(c_float) :: da_ice, a_no_ice, a_cloud, kappa
   end type greb_member_overrides
 
+  ! a member as a full namelist plus its GREB_X_* switches (greb_engine_create_members); pi, z_air, z_vapor, dt, dt_crcl,
+  ! ipx, ipy, year0 must equal the engine-wide greb_params
+  type, bind(C) :: greb_member_config
+     type(greb_params) :: p
+     integer(c_int32_t) :: switches
+  end type greb_member_config
+
   type, bind(C) :: greb_fields
      type(c_ptr) :: z_topo, glacier, sw_solar, tclim, qclim, uclim, vclim, mldclim, cldclim, swetclim
   end type greb_fields
@@ -34,6 +41,15 @@ module greb_c_api
        integer(c_int), value :: nx, ny, n_members, device, flags
        type(greb_fields), intent(in) :: f
        type(c_ptr), value :: overrides
+       type(c_ptr), intent(out) :: eng
+     end function
+     integer(c_int) function greb_engine_create_members(p, nx, ny, f, n_members, members, device, flags, eng) &
+          bind(C, name="greb_engine_create_members")
+       import :: greb_params, greb_fields, greb_member_config, c_int, c_ptr
+       type(greb_params), intent(in) :: p
+       integer(c_int), value :: nx, ny, n_members, device, flags
+       type(greb_fields), intent(in) :: f
+       type(greb_member_config), intent(in) :: members(*)
        type(c_ptr), intent(out) :: eng
      end function
      integer(c_int) function greb_engine_flux_correction(eng, years, yearly) bind(C, name="greb_engine_flux_correction")
@@ -71,6 +87,12 @@ module greb_c_api
        import :: c_int, c_ptr
        type(c_ptr), value :: eng
        integer(c_int), value :: switches
+     end function
+     integer(c_int) function greb_engine_set_member_experiments(eng, switches) &
+          bind(C, name="greb_engine_set_member_experiments")
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: eng
+       integer(c_int32_t), intent(in) :: switches(*)
      end function
      integer(c_int) function greb_engine_get_state(eng, member, state5) bind(C, name="greb_engine_get_state")
        import :: c_int, c_ptr, c_float

@@ -75,6 +75,18 @@ typedef struct greb_member_overrides {
   float da_ice, a_no_ice, a_cloud, kappa;
 } greb_member_overrides;
 
+/* A member as a full namelist plus its experiment switches (GREB_X_* below): everything a separate `ens_id` process of the
+ * reference -- or, with `switches`, of the upstream variant's log_exp -- can change.  Per member may differ
+ *   every field that reaches the point physics: sig, ct_sens, da_ice, a_no_ice, a_cloud, Tl_ice1/2, To_ice1/2, co_turb,
+ *     ce, cq_latent, cq_rain, r_qviwv, p_emi[10], and rho_*, cp_*, d_land, d_air through the heat capacities;
+ *   kappa (the member gets its own row tables); co2_flux; switches.
+ * pi, z_air, z_vapor, dt, dt_crcl, ipx, ipy, year0 feed data every member shares (row-table geometry, wz_air / wz_vapor,
+ * the clock) and must equal the engine-wide greb_params: GREB_E_INVALID otherwise, the message names field and member. */
+typedef struct greb_member_config {
+  greb_params p;
+  uint32_t switches;
+} greb_member_config;
+
 /* engine flags */
 #define GREB_F_STRICT 1u /* reference operation order, IEEE division, no FMA contraction
                             (bit-exact stencils; default is the restructured fast arithmetic) */
@@ -115,6 +127,15 @@ int greb_engine_create(const greb_params* p, int nx, int ny, const greb_fields* 
                        const greb_member_overrides* overrides, int device, unsigned flags,
                        greb_engine** out);
 
+/* The same with one greb_member_config per member (greb_engine_create is this with the four override slots expanded and
+ * no switches).  Members that are alike in physics, kappa, co2_flux and switches share ONE flux-correction set
+ * (3 x 730 fields) and are integrated once in the flux-correction phase; otherwise every member has its own.
+ * On the any-grid engine the transport kernels run all members of a launch alike: members that differ in
+ * GREB_X_VAPOR_DIFFUSION_ONLY are GREB_E_UNSUPPORTED there (run the two groups as two engines beside each other); a member
+ * with GREB_X_NO_CIRCULATION beside members without it is transported with the rest and drops its increments. */
+int greb_engine_create_members(const greb_params* p, int nx, int ny, const greb_fields* f, int n_members,
+                               const greb_member_config* members, int device, unsigned flags, greb_engine** out);
+
 /* qflux_correction (src/greb.f90:311-364): `years`*730 steps at co2_flux; leaves the
  * correction arrays, cap_surf and the spun-up state in the engine.
  * yearly may be NULL, else [n_members][years][2] = {global-mean Tsurf, Tsurf(ipx,ipy)} in
@@ -154,8 +175,13 @@ int greb_engine_run(greb_engine* e, int years, const float* co2_ppm, float* mont
                                               not applied in the flux-correction phase.  The host clears it for
                                               the control run and passes CO2 = CO2_ctrl (:225) */
 unsigned greb_log_exp_switches(int log_exp);
-/* Takes effect from the next flux_correction / run call. */
+/* Takes effect from the next flux_correction / run call; every member gets `switches`. */
 int greb_engine_set_experiment(greb_engine* e, unsigned switches);
+/* One switch word per member, switches[n_members]; takes effect from the next call.  An engine whose members share one
+ * flux-correction set gives every member a copy of it when the switches now differ (n_members sets; spin up once under
+ * the complete model, then let the members diverge); if that allocation fails the HIP error is returned and the engine
+ * is as it was.  greb_engine_set_experiment never does this. */
+int greb_engine_set_member_experiments(greb_engine* e, const uint32_t* switches);
 
 /* Flux-correction cache: TF/qF/ToF_correct [3][730][ny][nx] + cap_surf +
  * the four state fields Ts,Ta,To,q [5][ny][nx] of one member. */
