@@ -14,6 +14,9 @@ F_ROW_STRIPS = 4
 F_NO_PERSISTENT = 8
 F_PERSISTENT = 16
 RUN_DEVICE_OUT = 1
+D_REGIONS, D_ZONAL, D_ANNUAL = 1, 2, 4  # reduced-output products, GREB_D_* of include/greb_engine.h
+D_MAX_REGIONS = 15
+JDAY_MON = (31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31)  # src/greb.f90:42
 # sensitivity-experiment switches, GREB_X_* of include/greb_engine.h
 X_NO_ICE, X_NO_HYDRO, X_NO_DEEP_OCEAN, X_LW_LINEAR_VAPOR = 1, 2, 4, 8
 X_NO_CIRCULATION, X_NO_VAPOR_TRANSPORT, X_VAPOR_DIFFUSION_ONLY, X_SST_PLUS1 = 16, 32, 64, 128

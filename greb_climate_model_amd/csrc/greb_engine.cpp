@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "greb_kernels.h"
+#include "greb_diag.h"
 
 using namespace greb;
 
@@ -145,6 +146,8 @@ struct greb_engine {
   float* co2_dev = nullptr; size_t co2_cap = 0;
   float* monthly_dev = nullptr; size_t monthly_cap = 0;
   float* yearly_dev = nullptr; size_t yearly_cap = 0;
+  float* diag_out = nullptr; size_t diag_out_cap = 0; // run_diag: zonal means and annual maps of two years (one per staging slot)
+  float* diag_reg = nullptr; size_t diag_reg_cap = 0; // run_diag: the region series of the whole call
   // host copies needed later
   std::vector<RowTables> h_tabs;
   std::vector<int> h_tab_index;
@@ -634,7 +637,7 @@ int greb_engine_destroy(greb_engine* e) {
   void* ptrs[] = {e->z_topo, e->glacier, e->sw_solar, e->tclim, e->qclim, e->uclim, e->vclim, e->mldclim,
                   e->cldclim, e->swetclim, e->toclim, e->z_ocean, e->wz_air, e->wz_vapor, e->state, e->acc,
                   e->corr, e->corr_index, e->tab_index, e->tabs, e->phys, e->co2_dev, e->monthly_dev, e->yearly_dev,
-                  e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev};
+                  e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev, e->diag_out, e->diag_reg};
   for (void* q : ptrs) if (q) (void)hipFree(q);
   for (auto& kv : e->plans) free_plan(kv.second);
   if (e->call != greb_engine::kCallNever) ledger_release(e);
@@ -753,6 +756,237 @@ int greb_engine_run(greb_engine* e, int years, const float* co2_ppm, float* mont
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   if (int rc = check_circulation(e)) return rc;
   e->it_scnr += (long long)years * kNT;
+  if (yearly) HIP_TRY(e, hipMemcpy(yearly, e->yearly_dev, nm * years * 2 * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- reduced output (greb_diag.hip)
+// A plan is host data only: the combined weights w_r * cos(lat_j) of the globe and the caller's regions and the
+// reciprocals of their sums, made once in double.  Their device copies (and the scratch array of the per-band partial
+// sums) are made per device the first time the plan reduces something there.
+struct greb_diag {
+  int nx = 0, ny = 0, nr = 0;  // nr = 1 + n_regions
+  std::vector<double> w;       // [nr][ny][nx]
+  std::vector<double> inv_sum; // [nr]
+  struct Dev { int device; double* w; double* inv_sum; double* partials; size_t partials_cap; };
+  std::vector<Dev> devs;
+};
+
+namespace {
+// the plan's tables on `device` (current), with room for the partial sums of `n_members` when regions are reduced
+int diag_on_device(greb_diag* d, int device, int n_members, bool regions, greb_diag::Dev** out) {
+  greb_diag::Dev* dv = nullptr;
+  for (auto& x : d->devs) if (x.device == device) dv = &x;
+  if (!dv) {
+    greb_diag::Dev n{device, nullptr, nullptr, nullptr, 0};
+    HIP_TRY(nullptr, dev_alloc(&n.w, d->w.size()));
+    hipError_t err = dev_alloc(&n.inv_sum, d->inv_sum.size());
+    if (err == hipSuccess) err = hipMemcpy(n.w, d->w.data(), d->w.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(n.inv_sum, d->inv_sum.data(), d->inv_sum.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+      (void)hipFree(n.w);
+      if (n.inv_sum) (void)hipFree(n.inv_sum);
+      HIP_TRY(nullptr, err);
+    }
+    d->devs.push_back(n);
+    dv = &d->devs.back();
+  }
+  const size_t need = regions ? diag_partials(d->nx, d->ny, n_members, d->nr) : 0;
+  if (dv->partials_cap < need) { // (a larger batch than before: an earlier reduction may still read the old array)
+    if (dv->partials) {
+      HIP_TRY(nullptr, hipDeviceSynchronize());
+      HIP_TRY(nullptr, hipFree(dv->partials));
+      dv->partials = nullptr; dv->partials_cap = 0;
+    }
+    HIP_TRY(nullptr, dev_alloc(&dv->partials, need));
+    dv->partials_cap = need;
+  }
+  *out = dv;
+  return 0;
+}
+
+DiagArgs diag_args(const greb_diag* d, const greb_diag::Dev* dv, const float* monthly, float* regions, size_t regions_stride,
+                   float* zonal, float* annual) {
+  DiagArgs a{};
+  a.monthly = monthly; a.nx = d->nx; a.ny = d->ny; a.nr = d->nr;
+  a.w = dv->w; a.inv_sum = dv->inv_sum; a.partials = dv->partials;
+  a.regions = regions; a.regions_stride = regions_stride; a.zonal = zonal; a.annual = annual;
+  return a;
+}
+} // namespace
+
+extern "C" {
+
+int greb_diag_create(int nx, int ny, const float* region_w, int n_regions, greb_diag** out) {
+  if (!out) return fail(nullptr, GREB_E_INVALID, "diag_create: `out` is NULL");
+  *out = nullptr;
+  if (nx < 12 || (nx & 3) || ny < 5 || ny > kMaxNy)
+    return fail(nullptr, GREB_E_INVALID, "diag_create: grid " + std::to_string(nx) + " x " + std::to_string(ny) +
+                                             " (nx % 4 == 0, nx >= 12, 5 <= ny <= " + std::to_string(kMaxNy) + ")");
+  if (n_regions < 0 || n_regions > kDiagMaxRegions)
+    return fail(nullptr, GREB_E_INVALID, "diag_create: n_regions = " + std::to_string(n_regions) + " (0 ... " +
+                                             std::to_string(kDiagMaxRegions) + "; the globe is region 0 on top of them)");
+  if (n_regions > 0 && !region_w) return fail(nullptr, GREB_E_INVALID, "diag_create: region_w is NULL with n_regions > 0");
+  const size_t np = (size_t)nx * ny;
+  for (int k = 0; k < n_regions; ++k)
+    for (size_t i = 0; i < np; ++i) {
+      const float v = region_w[(size_t)k * np + i];
+      if (!(v >= 0.f && v <= 1.f)) { // (a NaN fails both comparisons)
+        char buf[160];
+        std::snprintf(buf, sizeof(buf), "diag_create: region %d: weight %g at row %zu, column %zu is not in [0, 1]", k + 1,
+                      (double)v, i / (size_t)nx, i % (size_t)nx);
+        return fail(nullptr, GREB_E_INVALID, buf);
+      }
+    }
+  greb_diag* d = new (std::nothrow) greb_diag();
+  if (!d) return fail(nullptr, GREB_E_INVALID, "out of host memory");
+  d->nx = nx; d->ny = ny; d->nr = 1 + n_regions;
+  d->w.resize((size_t)d->nr * np);
+  d->inv_sum.resize((size_t)d->nr);
+  const double pi = 3.14159265358979323846; // the true pi: the area of a grid cell, not the model's constant
+  for (int r = 0; r < d->nr; ++r) {
+    double sum = 0.0;
+    for (int j = 0; j < ny; ++j) {
+      const double c = std::cos(((j + 0.5) * 180.0 / ny - 90.0) * pi / 180.0);
+      for (int i = 0; i < nx; ++i) {
+        const size_t q = (size_t)j * nx + i;
+        const double w = r == 0 ? c : (double)region_w[(size_t)(r - 1) * np + q] * c;
+        d->w[(size_t)r * np + q] = w;
+        sum += w;
+      }
+    }
+    if (!(sum > 0.0)) {
+      delete d;
+      return fail(nullptr, GREB_E_INVALID, "diag_create: region " + std::to_string(r) + " has zero weight everywhere");
+    }
+    d->inv_sum[(size_t)r] = 1.0 / sum;
+  }
+  *out = d;
+  return 0;
+}
+
+int greb_diag_destroy(greb_diag* d) {
+  if (!d) return 0;
+  int prev = 0;
+  const bool have_prev = !d->devs.empty() && hipGetDevice(&prev) == hipSuccess;
+  for (auto& x : d->devs)
+    if (hipSetDevice(x.device) == hipSuccess) {
+      (void)hipDeviceSynchronize(); // a reduction in flight may still read the tables
+      (void)hipFree(x.w); (void)hipFree(x.inv_sum);
+      if (x.partials) (void)hipFree(x.partials);
+    }
+  if (have_prev) (void)hipSetDevice(prev);
+  delete d;
+  return 0;
+}
+
+int greb_diag_reduce_dev(greb_diag* d, int device, const float* monthly_year_dev, int n_members, float* regions_dev,
+                         float* zonal_dev, float* annual_dev, void* stream) {
+  if (!d) return fail(nullptr, GREB_E_INVALID, "diag_reduce_dev: no plan (greb_diag is NULL)");
+  if (!monthly_year_dev) return fail(nullptr, GREB_E_INVALID, "diag_reduce_dev: monthly_year_dev is NULL");
+  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "diag_reduce_dev: n_members = " + std::to_string(n_members));
+  if (!regions_dev && !zonal_dev && !annual_dev)
+    return fail(nullptr, GREB_E_INVALID, "diag_reduce_dev: regions_dev, zonal_dev and annual_dev are all NULL");
+  if (reinterpret_cast<uintptr_t>(monthly_year_dev) & 15)
+    return fail(nullptr, GREB_E_INVALID, "diag_reduce_dev: monthly_year_dev is not 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(annual_dev) & 15)
+    return fail(nullptr, GREB_E_INVALID, "diag_reduce_dev: annual_dev is not 16-byte aligned");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
+    return fail(nullptr, GREB_E_NOGPU, "diag_reduce_dev: no HIP device (no CPU path)");
+  HIP_TRY(nullptr, hipSetDevice(device));
+  greb_diag::Dev* dv = nullptr;
+  if (int rc = diag_on_device(d, device, n_members, regions_dev != nullptr, &dv)) return rc;
+  const DiagArgs a = diag_args(d, dv, monthly_year_dev, regions_dev, (size_t)kDiagMonths * kDiagVars * d->nr, zonal_dev, annual_dev);
+  HIP_TRY(nullptr, launch_diag_year(a, n_members, (hipStream_t)stream));
+  return 0;
+}
+
+int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_diag* d, unsigned what, float* regions,
+                         float* zonal, float* annual, float* yearly) {
+  // argument errors first, before anything touches a device
+  if (!d) return fail(e, GREB_E_INVALID, "run_diag: no plan (greb_diag is NULL)");
+  if (what == 0 || (what & ~(GREB_D_REGIONS | GREB_D_ZONAL | GREB_D_ANNUAL)))
+    return fail(e, GREB_E_INVALID, "run_diag: `what` = " + std::to_string(what) + " selects no product or an unknown one");
+  if ((what & GREB_D_REGIONS) && !regions) return fail(e, GREB_E_INVALID, "run_diag: GREB_D_REGIONS selected but `regions` is NULL");
+  if ((what & GREB_D_ZONAL) && !zonal) return fail(e, GREB_E_INVALID, "run_diag: GREB_D_ZONAL selected but `zonal` is NULL");
+  if ((what & GREB_D_ANNUAL) && !annual) return fail(e, GREB_E_INVALID, "run_diag: GREB_D_ANNUAL selected but `annual` is NULL");
+  if (!e || years < 1 || !co2_ppm) return fail(e, GREB_E_INVALID, "run_diag: bad argument (engine, years or co2_ppm)");
+  if (d->nx != e->nx || d->ny != e->ny)
+    return fail(e, GREB_E_INVALID, "run_diag: the plan's grid " + std::to_string(d->nx) + " x " + std::to_string(d->ny) +
+                                       " differs from the engine's " + std::to_string(e->nx) + " x " + std::to_string(e->ny));
+  HIP_TRY(e, hipSetDevice(e->device));
+  const size_t np = (size_t)e->np, nm = (size_t)e->nm;
+  const size_t rec_year = 12 * 5 * np; // floats per member-year
+  const size_t slot = nm * rec_year;
+  const bool do_r = (what & GREB_D_REGIONS) != 0, do_z = (what & GREB_D_ZONAL) != 0, do_a = (what & GREB_D_ANNUAL) != 0;
+  const size_t reg_year = (size_t)12 * 5 * d->nr, zon_year = (size_t)12 * 5 * e->ny, ann_year = 5 * np; // floats per member-year
+  const size_t zon_slot = do_z ? nm * zon_year : 0, ann_slot = do_a ? nm * ann_year : 0, out_slot = zon_slot + ann_slot;
+  if (int rc = ensure(e, &e->co2_dev, &e->co2_cap, nm * years)) return rc;
+  HIP_TRY(e, hipMemcpyAsync(e->co2_dev, co2_ppm, nm * years * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  if (int rc = ensure(e, &e->yearly_dev, &e->yearly_cap, nm * years * 2)) return rc;
+  HIP_TRY(e, hipMemsetAsync(e->yearly_dev, 0, nm * years * 2 * sizeof(float), e->stream));
+  // On the device: the two one-year staging slots of greb_engine_run, the zonal means and annual maps of two years, and
+  // -- the only thing that grows with `years` besides the yearly scalars -- the region series.
+  if (int rc = ensure(e, &e->monthly_dev, &e->monthly_cap, 2 * slot)) return rc;
+  if (out_slot) if (int rc = ensure(e, &e->diag_out, &e->diag_out_cap, 2 * out_slot)) return rc;
+  if (do_r) if (int rc = ensure(e, &e->diag_reg, &e->diag_reg_cap, nm * years * reg_year)) return rc;
+  greb_diag::Dev* dv = nullptr;
+  if (int rc = diag_on_device(d, e->device, e->nm, do_r, &dv)) { e->last_error = g_last_error; return rc; }
+  if (!e->copy_stream) HIP_TRY(e, hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
+  for (int i = 0; i < 2; ++i) {
+    if (!e->ev_done[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_done[i], hipEventDisableTiming));
+    if (!e->ev_free[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_free[i], hipEventDisableTiming));
+  }
+  // year y's zonal means and annual maps leave on the copy stream while year y + 1 integrates, as the monthly records do
+  // in greb_engine_run; the host side is strided by the caller's [member][years] layout
+  auto deliver = [&](int y) -> int {
+    const int sl = y & 1;
+    float* out = e->diag_out + (size_t)sl * out_slot;
+    HIP_TRY(e, hipStreamWaitEvent(e->copy_stream, e->ev_done[sl], 0));
+    if (do_z)
+      HIP_TRY(e, hipMemcpy2DAsync(zonal + (size_t)y * zon_year, (size_t)years * zon_year * sizeof(float), out,
+                                  zon_year * sizeof(float), zon_year * sizeof(float), nm, hipMemcpyDeviceToHost, e->copy_stream));
+    if (do_a)
+      HIP_TRY(e, hipMemcpy2DAsync(annual + (size_t)y * ann_year, (size_t)years * ann_year * sizeof(float), out + zon_slot,
+                                  ann_year * sizeof(float), ann_year * sizeof(float), nm, hipMemcpyDeviceToHost, e->copy_stream));
+    HIP_TRY(e, hipEventRecord(e->ev_free[sl], e->copy_stream));
+    return 0;
+  };
+  // as in greb_engine_run: no return while copies into the CALLER's buffers are in flight
+  const int rc_years = [&]() -> int {
+    for (int y = 0; y < years; ++y) {
+      const int sl = y & 1;
+      MemberArgs a = base_args(e);
+      a.flux_phase = 0;
+      a.it0 = e->it_scnr + 1 + (long long)y * kNT; a.nsteps = kNT;
+      a.co2 = e->co2_dev; a.co2_stride = years; a.co2_year0 = y;
+      a.monthly = e->monthly_dev + (size_t)sl * slot; a.monthly_years = 1; a.year_out0 = 0;
+      a.yearly = e->yearly_dev; a.yearly_years = years; a.yearly_year0 = y;
+      if (int rc = run_year(e, a, e->nm)) return rc;
+      if (y >= 2) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_free[sl], 0)); // the slot's products of year y - 2 have left
+      float* out = out_slot ? e->diag_out + (size_t)sl * out_slot : nullptr;
+      const DiagArgs g = diag_args(d, dv, a.monthly, do_r ? e->diag_reg + (size_t)y * reg_year : nullptr, (size_t)years * reg_year,
+                                   do_z ? out : nullptr, do_a ? out + zon_slot : nullptr);
+      HIP_TRY(e, launch_diag_year(g, e->nm, e->stream));
+      HIP_TRY(e, hipEventRecord(e->ev_done[sl], e->stream));
+      if (y > 0) if (int rc = deliver(y - 1)) return rc;
+    }
+    if (int rc = deliver(years - 1)) return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->copy_stream));
+    return 0;
+  }();
+  if (rc_years) {
+    (void)hipStreamSynchronize(e->copy_stream);
+    (void)hipStreamSynchronize(e->stream);
+    return rc_years;
+  }
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  if (int rc = check_circulation(e)) return rc;
+  e->it_scnr += (long long)years * kNT;
+  if (do_r) HIP_TRY(e, hipMemcpy(regions, e->diag_reg, nm * years * reg_year * sizeof(float), hipMemcpyDeviceToHost));
   if (yearly) HIP_TRY(e, hipMemcpy(yearly, e->yearly_dev, nm * years * 2 * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }

@@ -56,7 +56,8 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_engine_point_physics", "greb_log_exp_switches", "greb_engine_set_experiment",
            "greb_ensemble_moments_dev", "greb_ensemble_quantiles_dev", "greb_engine_set_state", "greb_release_caches", "greb_diffusion_launch_order",
            "greb_substep_launch_order", "greb_circulation_launch_plan", "greb_engine_describe",
-           "greb_engine_create_members", "greb_engine_set_member_experiments"]
+           "greb_engine_create_members", "greb_engine_set_member_experiments", "greb_diag_create", "greb_diag_destroy",
+           "greb_diag_reduce_dev", "greb_engine_run_diag"]
 
 
 def _check(rc: int, h=None):
@@ -194,6 +195,23 @@ class Engine:
         _check(lib().greb_engine_run(self.h, int(years), abi.fptr(co2), C.c_void_p(monthly_dev_ptr), abi.fptr(yearly),
                                      abi.RUN_DEVICE_OUT), self.h)
         return None, yearly
+
+    def run_diag(self, years: int, co2_ppm, plan, what: int | None = None):
+        """The scenario run of run() that hands back only the reduced products of `plan` (diag.Plan): regional means,
+        zonal means and annual-mean maps made on the device year by year (greb_engine_run_diag).  what: abi.D_* bits,
+        default all three.  Returns a diag.Result (regions, zonal, annual, yearly, region names; a product that was
+        not selected is None).  State, clock and yearly are those of run() over the same years."""
+        from . import diag
+        what = diag.ALL if what is None else int(what)
+        co2 = np.ascontiguousarray(np.broadcast_to(np.asarray(co2_ppm, np.float32), (self.nm, years)))
+        yearly = np.zeros((self.nm, years, 2), np.float32)
+        regions = np.empty((self.nm, years, 12, 5, plan.nr), np.float32) if what & abi.D_REGIONS else None
+        zonal = np.empty((self.nm, years, 12, 5, self.ny), np.float32) if what & abi.D_ZONAL else None
+        annual = np.empty((self.nm, years, 5, self.ny, self.nx), np.float32) if what & abi.D_ANNUAL else None
+        ptr = [None if a is None else abi.fptr(a) for a in (regions, zonal, annual)]
+        _check(lib().greb_engine_run_diag(self.h, int(years), abi.fptr(co2), plan.h, C.c_uint(what), *ptr, abi.fptr(yearly)),
+               self.h)
+        return diag.Result(regions, zonal, annual, yearly, plan.names)
 
     def state(self, member: int = 0) -> np.ndarray:
         s = np.empty((5, self.ny, self.nx), np.float32)

@@ -65,6 +65,34 @@ module greb_c_api
        real(c_float), intent(in) :: co2_ppm(*)
        real(c_float), intent(out) :: monthly(*), yearly(*)
      end function
+     ! reduced output (greb_diag.hip): a plan = grid + region weights [n_regions][ny][nx] in [0,1] (c_null_ptr with 0 regions)
+     integer(c_int) function greb_diag_create(nx, ny, region_w, n_regions, plan) bind(C, name="greb_diag_create")
+       import :: c_int, c_ptr
+       integer(c_int), value :: nx, ny, n_regions
+       type(c_ptr), value :: region_w
+       type(c_ptr), intent(out) :: plan
+     end function
+     integer(c_int) function greb_diag_destroy(plan) bind(C, name="greb_diag_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan
+     end function
+     ! device pointers (c_ptr); a product whose pointer is c_null_ptr is skipped; launches on `stream`, no synchronisation
+     integer(c_int) function greb_diag_reduce_dev(plan, device, monthly_year_dev, n_members, regions_dev, zonal_dev, &
+          annual_dev, stream) bind(C, name="greb_diag_reduce_dev")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan, monthly_year_dev, regions_dev, zonal_dev, annual_dev, stream
+       integer(c_int), value :: device, n_members
+     end function
+     ! greb_engine_run that delivers only the products selected by `what` (1 regions, 2 zonal, 4 annual):
+     ! regions(1+n_regions,5,12,years,n_members), zonal(ny,5,12,years,n_members), annual(nx,ny,5,years,n_members)
+     integer(c_int) function greb_engine_run_diag(eng, years, co2_ppm, plan, what, regions, zonal, annual, yearly) &
+          bind(C, name="greb_engine_run_diag")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, plan
+       integer(c_int), value :: years, what
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: regions(*), zonal(*), annual(*), yearly(*)
+     end function
      integer(c_int) function greb_engine_get_corrections(eng, member, corr, state5) &
           bind(C, name="greb_engine_get_corrections")
        import :: c_int, c_ptr, c_float

@@ -155,6 +155,46 @@ const char* greb_engine_describe(greb_engine* e);
 int greb_engine_run(greb_engine* e, int years, const float* co2_ppm, float* monthly, float* yearly,
                     unsigned run_flags);
 
+/* ---- reduced output: regional, zonal and annual diagnostics made on the device ------------------
+ * The reference leaves every diagnostic to R scripts over the output file (R/analyse_output_fields.R).  A big ensemble
+ * cannot hand back [n_members][years][12][5][ny][nx]; what its analysis wants per member is small, and comes from ONE pass
+ * over a model year of monthly records while they are still in HBM (greb_diag.hip).  Three products, chosen by flags:
+ *   GREB_D_REGIONS  [..][12][5][1 + n_regions]  weighted means  sum w_r(j,i) c_j x / sum w_r(j,i) c_j;  region 0 is the
+ *                   globe (w = 1), regions 1 ... n_regions are the caller's;  c_j = cos(lat_j), lat_j = (j + 0.5) 180 / ny
+ *                   - 90 degrees (row 0 = south), evaluated in double with the true pi, not greb_params.pi
+ *   GREB_D_ZONAL    [..][12][5][ny]             the plain mean over longitude
+ *   GREB_D_ANNUAL   [..][5][ny][nx]             the day-weighted mean of the twelve records, sum jday_mon[m] X_m / 365
+ *                   (src/greb.f90:42): in exact arithmetic the mean over the year's 730 steps
+ * Every sum is accumulated in fp64 in an order the grid alone fixes (no atomics) and rounded to fp32 once: results are
+ * deterministic, and a member's numbers do not depend on how many members are reduced with it or where it sits. */
+#define GREB_D_REGIONS 1u
+#define GREB_D_ZONAL   2u
+#define GREB_D_ANNUAL  4u
+typedef struct greb_diag greb_diag;
+/* A plan: the grid and the regions.  region_w: [n_regions][ny][nx] weights in [0, 1] shared by all members (NULL with
+ * n_regions = 0: the globe alone), n_regions <= 15.  Host work only -- the combined weights w_r c_j and the reciprocals of
+ * their sums are made here in double -- and validated without touching a device: a grid the engine does not take,
+ * n_regions > 15, a weight outside [0, 1] or not finite, a region whose weights are all zero are GREB_E_INVALID with a
+ * message that names the offender (greb_engine_last_error(NULL)).  A plan serves any number of engines and calls, one at
+ * a time. */
+int greb_diag_create(int nx, int ny, const float* region_w, int n_regions, greb_diag** out);
+int greb_diag_destroy(greb_diag* d);
+/* One model year [n_members][12][5][ny][nx] on HIP device `device` -> the products whose pointer is not NULL (device
+ * pointers, laid out [n_members] + the shapes above; monthly_year_dev and annual_dev 16-byte aligned).  Launches on
+ * `stream` (a hipStream_t, may be NULL) and does not synchronise: e.g. ahead of an RCCL all-reduce of the small products. */
+int greb_diag_reduce_dev(greb_diag* d, int device, const float* monthly_year_dev, int n_members, float* regions_dev,
+                         float* zonal_dev, float* annual_dev, void* stream);
+/* greb_engine_run that delivers ONLY the products selected by `what` (GREB_D_*), to host memory:
+ *   regions [n_members][years][12][5][1 + n_regions]   zonal [n_members][years][12][5][ny]   annual [n_members][years][5][ny][nx]
+ * (a pointer whose product is not selected is ignored and may be NULL; a selected product with a NULL pointer is
+ * GREB_E_INVALID, as is a plan made for another grid).  co2_ppm, yearly, the model clock and the state the engine is left
+ * in are those of greb_engine_run over the same years, bit for bit.  Each year is integrated into one of the engine's two
+ * one-year staging slots and reduced there; zonal means and annual maps leave per year on the copy stream.  Device memory
+ * does not grow with `years` except for the yearly scalars and the region series: a 100-year run of 512 members needs
+ * what a 1-year run needs. */
+int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_diag* d, unsigned what, float* regions,
+                         float* zonal, float* annual, float* yearly);
+
 /* ---- sensitivity-experiment switches -----------------------------------------
  * Runtime switches on the same kernels that reproduce the `log_exp` experiments of the upstream model
  * variant (src/greb.original.model.f90:60,162-166,394,423-430,452-453,492-495,513-515,553-571; doc in its
