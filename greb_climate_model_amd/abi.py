@@ -16,6 +16,12 @@ F_PERSISTENT = 16
 RUN_DEVICE_OUT = 1
 D_REGIONS, D_ZONAL, D_ANNUAL = 1, 2, 4  # reduced-output products, GREB_D_* of include/greb_engine.h
 D_MAX_REGIONS = 15
+# budget output, GREB_NBUDGET / GREB_B_* of include/greb_engine.h: the flux terms of the update in its order, sign and unit
+BUDGET_NAMES = ("sw", "LW_surf", "LWair_down", "LW_abs", "Q_sens", "Q_lat", "Q_lat_air", "dq_eva", "dq_rain", "dT_ocean",
+                "dTo", "dTa_crcl", "dq_crcl")
+NBUDGET = len(BUDGET_NAMES)
+(B_SW, B_LW_SURF, B_LWAIR_DOWN, B_LW_ABS, B_Q_SENS, B_Q_LAT, B_Q_LAT_AIR, B_DQ_EVA, B_DQ_RAIN, B_DT_OCEAN, B_DTO,
+ B_DTA_CRCL, B_DQ_CRCL) = range(NBUDGET)
 JDAY_MON = (31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31)  # src/greb.f90:42
 # sensitivity-experiment switches, GREB_X_* of include/greb_engine.h
 X_NO_ICE, X_NO_HYDRO, X_NO_DEEP_OCEAN, X_LW_LINEAR_VAPOR = 1, 2, 4, 8

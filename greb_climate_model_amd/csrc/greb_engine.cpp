@@ -145,6 +145,9 @@ struct greb_engine {
   Phys* phys = nullptr;
   float* co2_dev = nullptr; size_t co2_cap = 0;
   float* monthly_dev = nullptr; size_t monthly_cap = 0;
+  float* bsum = nullptr;                               // run_budget: [nm][GREB_NBUDGET][np] running sums, made on the first budget run
+  float* budget_dev = nullptr; size_t budget_cap = 0;  // run_budget: two one-year staging slots of budget records
+  long long budget_runs = 0;                           // run_budget calls so far (describe)
   float* yearly_dev = nullptr; size_t yearly_cap = 0;
   float* diag_out = nullptr; size_t diag_out_cap = 0; // run_diag: zonal means and annual maps of two years (one per staging slot)
   float* diag_reg = nullptr; size_t diag_reg_cap = 0; // run_diag: the region series of the whole call
@@ -604,6 +607,96 @@ int create_engine(const char* who, const greb_params* p, int nx, int ny, const g
   }
   return 0;
 }
+
+// greb_engine_run (budget == nullptr) and greb_engine_run_budget (budget != nullptr, monthly may be nullptr): `years`
+// scenario years, each year's records delivered to the caller.  With a budget the launches take the BUDGET instantiations
+// (MemberArgs::bsum set); what they leave in state, clock, monthly and yearly is what the default ones leave.
+int run_scenario(greb_engine* e, int years, const float* co2_ppm, float* monthly, float* budget, float* yearly,
+                 unsigned run_flags) {
+  HIP_TRY(e, hipSetDevice(e->device));
+  const size_t np = (size_t)e->np, nm = (size_t)e->nm;
+  const size_t rec_year = 12 * 5 * np, bud_year = (size_t)12 * GREB_NBUDGET * np; // floats per member-year
+  const bool dev_out = (run_flags & GREB_RUN_DEVICE_OUT) != 0;
+  if (int rc = ensure(e, &e->co2_dev, &e->co2_cap, nm * years)) return rc;
+  HIP_TRY(e, hipMemcpyAsync(e->co2_dev, co2_ppm, nm * years * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  if (int rc = ensure(e, &e->yearly_dev, &e->yearly_cap, nm * years * 2)) return rc;
+  HIP_TRY(e, hipMemsetAsync(e->yearly_dev, 0, nm * years * 2 * sizeof(float), e->stream));
+  const size_t slot = nm * rec_year, bslot = nm * bud_year;
+  // scenario year y of this call: its records go to year mon_y of mon_years in `mon`, and bud_y of bud_years in `bud`
+  auto year_args = [&](int y, float* mon, int mon_years, int mon_y, float* bud, int bud_years, int bud_y) {
+    MemberArgs a = base_args(e);
+    a.flux_phase = 0;
+    a.it0 = e->it_scnr + 1 + (long long)y * kNT; a.nsteps = kNT;
+    a.co2 = e->co2_dev; a.co2_stride = years; a.co2_year0 = y;
+    a.monthly = mon; a.monthly_years = mon_years; a.year_out0 = mon_y;
+    a.yearly = e->yearly_dev; a.yearly_years = years; a.yearly_year0 = y;
+    if (budget) { a.bsum = e->bsum; a.brec = bud; a.brec_years = bud_years; a.brec_year0 = bud_y; }
+    return a;
+  };
+  if (dev_out) {
+    // (a budget-only run: the kernels write their five records regardless -- into one staging slot nobody reads)
+    if (!monthly) if (int rc = ensure(e, &e->monthly_dev, &e->monthly_cap, slot)) return rc;
+    for (int y = 0; y < years; ++y) {
+      const MemberArgs a = monthly ? year_args(y, monthly, years, y, budget, years, y)
+                                   : year_args(y, e->monthly_dev, 1, 0, budget, years, y);
+      if (int rc = run_year(e, a, e->nm)) return rc;
+    }
+  } else {
+    // Host delivery: year y's records leave over PCIe on the copy stream while year y+1 integrates on the compute
+    // stream (two staging slots of one model year each, [member][12][5][np], and the same of budget records); the host
+    // side is strided by the caller's [member][years] layout.  A pinned destination makes the copies true DMA; a
+    // pageable one is staged by the runtime and still overlaps the kernels.
+    if (int rc = ensure(e, &e->monthly_dev, &e->monthly_cap, 2 * slot)) return rc;
+    if (budget) if (int rc = ensure(e, &e->budget_dev, &e->budget_cap, 2 * bslot)) return rc;
+    if (!e->copy_stream) HIP_TRY(e, hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
+    for (int i = 0; i < 2; ++i) {
+      if (!e->ev_done[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_done[i], hipEventDisableTiming));
+      if (!e->ev_free[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_free[i], hipEventDisableTiming));
+    }
+    // copy of year y: issued AFTER year y+1's kernels are enqueued, so that even a copy the runtime performs
+    // synchronously (pageable destination) runs beside a kernel
+    auto deliver = [&](int y) -> int {
+      const int sl = y & 1;
+      HIP_TRY(e, hipStreamWaitEvent(e->copy_stream, e->ev_done[sl], 0));
+      if (monthly)
+        HIP_TRY(e, hipMemcpy2DAsync(monthly + (size_t)y * rec_year, (size_t)years * rec_year * sizeof(float),
+                                    e->monthly_dev + (size_t)sl * slot, rec_year * sizeof(float), rec_year * sizeof(float),
+                                    nm, hipMemcpyDeviceToHost, e->copy_stream));
+      if (budget)
+        HIP_TRY(e, hipMemcpy2DAsync(budget + (size_t)y * bud_year, (size_t)years * bud_year * sizeof(float),
+                                    e->budget_dev + (size_t)sl * bslot, bud_year * sizeof(float), bud_year * sizeof(float),
+                                    nm, hipMemcpyDeviceToHost, e->copy_stream));
+      HIP_TRY(e, hipEventRecord(e->ev_free[sl], e->copy_stream));
+      return 0;
+    };
+    // an error anywhere below must not return while copies into the CALLER's buffer are still in flight (the caller
+    // may free it as soon as it sees the error): the body runs in a lambda and both streams are drained on failure
+    const int rc_years = [&]() -> int {
+    for (int y = 0; y < years; ++y) {
+      const int sl = y & 1;
+      if (y >= 2) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_free[sl], 0)); // slot's previous year has left
+      const MemberArgs a = year_args(y, e->monthly_dev + (size_t)sl * slot, 1, 0,
+                                     budget ? e->budget_dev + (size_t)sl * bslot : nullptr, 1, 0);
+      if (int rc = run_year(e, a, e->nm)) return rc;
+      HIP_TRY(e, hipEventRecord(e->ev_done[sl], e->stream));
+      if (y > 0) if (int rc = deliver(y - 1)) return rc;
+    }
+    if (int rc = deliver(years - 1)) return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->copy_stream));
+    return 0;
+    }();
+    if (rc_years) {
+      (void)hipStreamSynchronize(e->copy_stream);
+      (void)hipStreamSynchronize(e->stream);
+      return rc_years;
+    }
+  }
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  if (int rc = check_circulation(e)) return rc;
+  e->it_scnr += (long long)years * kNT;
+  if (yearly) HIP_TRY(e, hipMemcpy(yearly, e->yearly_dev, nm * years * 2 * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
 } // namespace
 
 extern "C" {
@@ -637,7 +730,7 @@ int greb_engine_destroy(greb_engine* e) {
   void* ptrs[] = {e->z_topo, e->glacier, e->sw_solar, e->tclim, e->qclim, e->uclim, e->vclim, e->mldclim,
                   e->cldclim, e->swetclim, e->toclim, e->z_ocean, e->wz_air, e->wz_vapor, e->state, e->acc,
                   e->corr, e->corr_index, e->tab_index, e->tabs, e->phys, e->co2_dev, e->monthly_dev, e->yearly_dev,
-                  e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev, e->diag_out, e->diag_reg};
+                  e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev, e->diag_out, e->diag_reg, e->bsum, e->budget_dev};
   for (void* q : ptrs) if (q) (void)hipFree(q);
   for (auto& kv : e->plans) free_plan(kv.second);
   if (e->call != greb_engine::kCallNever) ledger_release(e);
@@ -686,78 +779,27 @@ int greb_engine_flux_correction(greb_engine* e, int years, float* yearly) {
 int greb_engine_run(greb_engine* e, int years, const float* co2_ppm, float* monthly, float* yearly,
                     unsigned run_flags) {
   if (!e || years < 1 || !co2_ppm || !monthly) return fail(e, GREB_E_INVALID, "run: bad argument");
+  return run_scenario(e, years, co2_ppm, monthly, nullptr, yearly, run_flags);
+}
+
+int greb_engine_run_budget(greb_engine* e, int years, const float* co2_ppm, float* monthly, float* budget, float* yearly,
+                           unsigned run_flags) {
+  if (!e || years < 1 || !co2_ppm) return fail(e, GREB_E_INVALID, "run_budget: bad argument (engine, years or co2_ppm)");
+  if (!budget) return fail(e, GREB_E_INVALID, "run_budget: `budget` is NULL (greb_engine_run is the run without budget output)");
   HIP_TRY(e, hipSetDevice(e->device));
-  const size_t np = (size_t)e->np, nm = (size_t)e->nm;
-  const size_t rec_year = 12 * 5 * np; // floats per member-year
-  const bool dev_out = (run_flags & GREB_RUN_DEVICE_OUT) != 0;
-  if (int rc = ensure(e, &e->co2_dev, &e->co2_cap, nm * years)) return rc;
-  HIP_TRY(e, hipMemcpyAsync(e->co2_dev, co2_ppm, nm * years * sizeof(float), hipMemcpyHostToDevice, e->stream));
-  if (int rc = ensure(e, &e->yearly_dev, &e->yearly_cap, nm * years * 2)) return rc;
-  HIP_TRY(e, hipMemsetAsync(e->yearly_dev, 0, nm * years * 2 * sizeof(float), e->stream));
-  if (dev_out) {
-    for (int y = 0; y < years; ++y) {
-      MemberArgs a = base_args(e);
-      a.flux_phase = 0;
-      a.it0 = e->it_scnr + 1 + (long long)y * kNT; a.nsteps = kNT;
-      a.co2 = e->co2_dev; a.co2_stride = years; a.co2_year0 = y;
-      a.monthly = monthly; a.monthly_years = years; a.year_out0 = y;
-      a.yearly = e->yearly_dev; a.yearly_years = years; a.yearly_year0 = y;
-      if (int rc = run_year(e, a, e->nm)) return rc;
-    }
-  } else {
-    // Host delivery: year y's records leave over PCIe on the copy stream while year y+1 integrates on the compute
-    // stream (two staging slots of one model year each, [member][12][5][np]); the host side is strided by the
-    // caller's [member][years] layout.  A pinned `monthly` makes the copies true DMA; a pageable one is staged by
-    // the runtime and still overlaps the kernels.
-    const size_t slot = nm * rec_year;
-    if (int rc = ensure(e, &e->monthly_dev, &e->monthly_cap, 2 * slot)) return rc;
-    if (!e->copy_stream) HIP_TRY(e, hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-      if (!e->ev_done[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_done[i], hipEventDisableTiming));
-      if (!e->ev_free[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_free[i], hipEventDisableTiming));
-    }
-    // copy of year y: issued AFTER year y+1's kernels are enqueued, so that even a copy the runtime performs
-    // synchronously (pageable destination) runs beside a kernel
-    auto deliver = [&](int y) -> int {
-      const int sl = y & 1;
-      HIP_TRY(e, hipStreamWaitEvent(e->copy_stream, e->ev_done[sl], 0));
-      HIP_TRY(e, hipMemcpy2DAsync(monthly + (size_t)y * rec_year, (size_t)years * rec_year * sizeof(float),
-                                  e->monthly_dev + (size_t)sl * slot, rec_year * sizeof(float), rec_year * sizeof(float),
-                                  nm, hipMemcpyDeviceToHost, e->copy_stream));
-      HIP_TRY(e, hipEventRecord(e->ev_free[sl], e->copy_stream));
-      return 0;
-    };
-    // an error anywhere below must not return while copies into the CALLER's buffer are still in flight (the caller
-    // may free it as soon as it sees the error): the body runs in a lambda and both streams are drained on failure
-    const int rc_years = [&]() -> int {
-    for (int y = 0; y < years; ++y) {
-      const int sl = y & 1;
-      if (y >= 2) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_free[sl], 0)); // slot's previous year has left
-      MemberArgs a = base_args(e);
-      a.flux_phase = 0;
-      a.it0 = e->it_scnr + 1 + (long long)y * kNT; a.nsteps = kNT;
-      a.co2 = e->co2_dev; a.co2_stride = years; a.co2_year0 = y;
-      a.monthly = e->monthly_dev + (size_t)sl * slot; a.monthly_years = 1; a.year_out0 = 0;
-      a.yearly = e->yearly_dev; a.yearly_years = years; a.yearly_year0 = y;
-      if (int rc = run_year(e, a, e->nm)) return rc;
-      HIP_TRY(e, hipEventRecord(e->ev_done[sl], e->stream));
-      if (y > 0) if (int rc = deliver(y - 1)) return rc;
-    }
-    if (int rc = deliver(years - 1)) return rc;
-    HIP_TRY(e, hipStreamSynchronize(e->copy_stream));
-    return 0;
-    }();
-    if (rc_years) {
-      (void)hipStreamSynchronize(e->copy_stream);
-      (void)hipStreamSynchronize(e->stream);
-      return rc_years;
-    }
+  if (!e->bsum) { // zero from here on: every December ends with the sums cleared
+    const size_t n = (size_t)e->nm * GREB_NBUDGET * e->np;
+    HIP_TRY(e, dev_alloc(&e->bsum, n));
+    HIP_TRY(e, hipMemsetAsync(e->bsum, 0, n * sizeof(float), e->stream));
   }
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  if (int rc = check_circulation(e)) return rc;
-  e->it_scnr += (long long)years * kNT;
-  if (yearly) HIP_TRY(e, hipMemcpy(yearly, e->yearly_dev, nm * years * 2 * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
+  ++e->budget_runs;
+  return run_scenario(e, years, co2_ppm, monthly, budget, yearly, run_flags);
+}
+
+const char* greb_budget_name(int i) {
+  static const char* const names[GREB_NBUDGET] = {"sw", "LW_surf", "LWair_down", "LW_abs", "Q_sens", "Q_lat", "Q_lat_air",
+                                                  "dq_eva", "dq_rain", "dT_ocean", "dTo", "dTa_crcl", "dq_crcl"};
+  return i >= 0 && i < GREB_NBUDGET ? names[i] : nullptr;
 }
 
 } // extern "C"
@@ -1000,6 +1042,8 @@ const char* greb_engine_describe(greb_engine* e) {
   s = buf;
   std::snprintf(buf, sizeof(buf), ", \"member_switches\": \"%s\", \"correction_sets\": %d, \"physics_sets\": %d",
                 e->xsw_uniform ? "uniform" : "per member", e->shared_corr ? 1 : e->nm, e->n_phys_sets);
+  s += buf;
+  std::snprintf(buf, sizeof(buf), ", \"budget_runs\": %lld", e->budget_runs);
   s += buf;
   if (e->call != greb_engine::kCallNever) {
     std::snprintf(buf, sizeof(buf), ", \"wavefront_slots_granted\": %d, \"circulation\": [", e->slots_granted);

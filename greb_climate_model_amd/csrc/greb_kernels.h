@@ -69,7 +69,15 @@ struct MemberArgs {
   // per-member experiment control (read by the switch-aware instantiations only; greb_physics_step.h: member_switches)
   const unsigned* xsw_m;   // [nm] experiment switches of each member; null: xsw applies to all
   const float* co2_flux_m; // [nm] flux-phase CO2 of each member; null: co2_flux applies to all
+  // budget output (read by the BUDGET instantiations only; null otherwise: greb_physics_step.h, budget_sink)
+  float* bsum;             // [nm][kNBudget][np] running sums of the month's flux terms
+  float* brec;             // [nm][brec_years][12][kNBudget][np] monthly means of the terms
+  int brec_years;          // years per member in `brec`
+  int brec_year0;          // index there of the year containing it0
 };
+
+// GREB_NBUDGET, GREB_B_*: the flux terms of one step in the order of include/greb_engine.h
+enum { kBsw, kBLWsurf, kBLWdown, kBLWabs, kBQsens, kBQlat, kBQlatAir, kBdqEva, kBdqRain, kBdTocean, kBdTo, kBdTaCrcl, kBdqCrcl, kNBudget };
 
 
 // fused engine (greb_member.hip): 96x48 with the default sub-cycling layout -- rows 0-9 and 38-47

@@ -636,9 +636,13 @@ __device__ __forceinline__ void quad_chain_substep(lfloat* lds, int cur, QuadCha
 // stage this step's winds (src/greb.f90:203-216, 732): raw for STRICT and for the polar rows,
 // otherwise scaled by the row's advection constants so the sign split is one max/min per use:
 //   x = c*u, c = ccx/3 (full rows) or ccx2/20 (sub-cycled rows);  y = ccy/3 * v
-template <bool STRICT>
+// REMAT (the switch-aware FAST kernels, whose sub-step loop exists twice): the thread's addresses are derived anew every
+// model step -- a few instructions -- instead of living in registers across the sub-steps, where that kernel has none left.
+template <bool STRICT, bool REMAT = false>
 __device__ __forceinline__ void stage_winds(lfloat* lds, const float* __restrict__ u, const float* __restrict__ v,
                                             const RowTables* __restrict__ tab) {
+  int tid0 = threadIdx.x;
+  if (REMAT) asm volatile("" : "+v"(tid0));
   // All of a thread's wind quads are requested before the first is waited for (unconditional loads at clamped
   // indices, predicated stores): as a plain load-scale-store loop the three iterations were three dependent round
   // trips, 2 700 cycles per model step.  The row's constants come from the LDS copy staged at init.
@@ -646,12 +650,12 @@ __device__ __forceinline__ void stage_winds(lfloat* lds, const float* __restrict
   f4 uq[kIt], vq[kIt];
 #pragma unroll
   for (int j = 0; j < kIt; ++j) {
-    const int i = min((int)threadIdx.x + j * kThreads, NP / 4 - 1);
+    const int i = min(tid0 + j * kThreads, NP / 4 - 1);
     uq[j] = ld4(u + 4 * i); vq[j] = ld4(v + 4 * i);
   }
 #pragma unroll
   for (int j = 0; j < kIt; ++j) {
-    const int i = threadIdx.x + j * kThreads;
+    const int i = tid0 + j * kThreads;
     if (i < NP / 4) {
       const int k = i / NQ;
       if (!(STRICT || k == 0 || k == NY - 1)) {
@@ -685,12 +689,15 @@ struct Circ {
   // One wave's share of `nsub` sub-steps, one s_barrier after each (every wave of the workgroup executes the same
   // number of barriers, each in its own loop).  WAVE is compile-time: the loop body is the wave's own straight-line
   // task sequence.  dbg: timing experiments only (tools/microbench_circ.py): bit0/1/2 skip sub / full / chain work.
-  template <int WAVE>
-  __device__ __forceinline__ void role_loop(lfloat* lds, int cur, int nsub, int lane, int dbg, bool calm_q
+  // NOT_CALM: the caller knows calm_q to be false (see substeps): the loop is then compiled as the default instantiation
+  // compiles it.
+  template <int WAVE, bool NOT_CALM>
+  __device__ __forceinline__ void role_loop(lfloat* lds, int cur, int nsub, int lane, int dbg, bool calm_runtime
 #ifdef GREB_TUNING
                                             , bool stamp, unsigned long long& busy
 #endif
   ) {
+    const bool calm_q = NOT_CALM ? false : calm_runtime;
     // the lane's task addresses: derived once per circulation call (not per launch -- values that live across the
     // point-physics phase, where the register pressure peaks, come back as scratch reloads inside this loop)
     constexpr bool kPolar = is_polar_wave<STRICT>(WAVE);
@@ -721,11 +728,18 @@ struct Circ {
   ) {
     int lane = threadIdx.x & 63;
     asm volatile("" : "+v"(lane)); // opaque: nothing derived from it is hoisted out of the model-step loop
+    // FAST: a launch whose member does not have the vapour-diffusion-only switch takes a copy of the loop in which calm_q
+    // is the constant false.  With the switch as a run-time select inside the update (greb_pair.h: da.y = 0) the compiler
+    // fuses the multiply-adds around it differently, and a member WITHOUT switches in a switch-aware launch then differs
+    // in the last bits from the same member in the default instantiation; so, the two are the same code.  (STRICT has no
+    // contraction: one loop.)
 #ifdef GREB_TUNING
     unsigned long long b = 0;
-#define GREB_ROLE(W) case W: role_loop<W>(lds, cur, nsub, lane, dbg, calm_q, stamp, b); break;
+#define GREB_ROLE(W) case W: if (!STRICT && !calm_q) role_loop<W, true>(lds, cur, nsub, lane, dbg, false, stamp, b); \
+                             else role_loop<W, false>(lds, cur, nsub, lane, dbg, calm_q, stamp, b); break;
 #else
-#define GREB_ROLE(W) case W: role_loop<W>(lds, cur, nsub, lane, dbg, calm_q); break;
+#define GREB_ROLE(W) case W: if (!STRICT && !calm_q) role_loop<W, true>(lds, cur, nsub, lane, dbg, false); \
+                             else role_loop<W, false>(lds, cur, nsub, lane, dbg, calm_q); break;
 #endif
     switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) { // a scalar branch per circulation call
       GREB_ROLE(0) GREB_ROLE(1) GREB_ROLE(2) GREB_ROLE(3) GREB_ROLE(4) GREB_ROLE(5) GREB_ROLE(6) GREB_ROLE(7)
@@ -788,7 +802,9 @@ hipError_t launch_circulation_g96(const float* X, const float* wz, const float* 
 // the point physics, the vapour-diffusion-only form of the sub-steps and the member's OWN sub-step count -- a member
 // without circulation does none while its neighbours do 24 (every wave of a workgroup runs the same count, so the
 // barriers inside Circ::substeps stay matched).
-template <bool STRICT, bool FLUX, bool EXP>
+// BUDGET (scenario phase, opt-in: greb_engine_run_budget): the monthly means of the step's thirteen flux terms go out
+// beside the five standard records.  The default instantiations contain none of it.
+template <bool STRICT, bool FLUX, bool EXP, bool BUDGET = false>
 __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
   extern __shared__ __align__(16) float lds_raw[];
   lfloat* lds = (lfloat*)lds_raw;
@@ -833,7 +849,7 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
     const size_t off = ck.off;
 
     GREB_STAMP(t_a);
-    stage_winds<STRICT>(lds, a.uclim + off, a.vclim + off, tab);
+    stage_winds<STRICT, EXP && !STRICT>(lds, a.uclim + off, a.vclim + off, tab);
     __syncthreads();
     GREB_STAMP(t_b);
 
@@ -866,6 +882,21 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
     // Also measured: the next quad's operands requested BETWEEN the arithmetic of the current quad and its stores
     // (physics_load / physics_compute / physics_store, the inputs dead by then): 116 + 56 live VGPRs of operands and
     // results still spill 68 registers at the 256 cap, and the phase takes 41 600 cycles instead of 24 900.
+    // BUDGET: a pass of its own over the step's quads BEFORE the update pass, while the old state and the transported
+    // tracers are still in place: it evaluates the physics functions once more and only accumulates (the state outputs,
+    // the corrections and the monthly sums of physics_load / physics_compute are dead here and compiled out).  Adding the
+    // thirteen terms inside the update pass -- each by its own load, add and store, as the any-grid kernel does -- spills
+    // 19 (EXP: 37) VGPRs of the FAST kernel to scratch at the 256 cap; in this form it has none.  A thread takes the
+    // same quads in both passes, so the two need no barrier between them.
+    if constexpr (BUDGET) {
+      const BudgetSink bs = budget_sink<true>(a, m, ck);
+#pragma unroll 1
+      for (int qd = tid; qd < NP / 4; qd += kThreads) {
+        const q8 xpair = ld8(Xf + (qd / NQ) * RS, qd % NQ);
+        const PhysIn in = physics_load<FLUX, EXP>(a, qd, ck, state, acc, corr, xsw);
+        (void)physics_compute<STRICT, FLUX, EXP, true>(a, P, in, co2, comp(xpair, 0), comp(xpair, 1), xsw, bs, 4 * qd);
+      }
+    }
 #pragma unroll 1
     for (int qd = tid; qd < NP / 4; qd += kThreads) {
 #ifdef GREB_TUNING
@@ -889,8 +920,10 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
           y[1] = red[(a.ipy - 1) * NX + (a.ipx - 1)] - 273.15f;
         }
       } else if (a.yearly) { // FAST: per-lane partial sums, wavefront shuffle reduction, 8 wave totals through LDS
+        int t0 = tid;
+        if (EXP) asm volatile("" : "+v"(t0)); // (as in stage_winds: the address is not kept across the year's sub-steps)
         float part = 0.f;
-        for (int i = tid; i < NP; i += kThreads) part += red[i];
+        for (int i = t0; i < NP; i += kThreads) part += red[i];
         part = wave_sum(part);
         const float point = red[(a.ipy - 1) * NX + (a.ipx - 1)];
         __syncthreads(); // everyone has read red[]; its first words now carry the wave totals
@@ -926,7 +959,11 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 hipError_t launch_member_kernel(const MemberArgs& a, int n_members, bool strict, hipStream_t s) {
   if (a.nx != NX || a.ny != NY) return hipErrorInvalidValue;
   void (*kern)(MemberArgs);
-  if (a.xsw || a.xsw_m) { // sensitivity experiment (of every member or of some): the switch-aware instantiation
+  if (a.bsum) { // budget output (scenario phase only): the opt-in instantiations
+    if (a.flux_phase || !a.brec) return hipErrorInvalidValue;
+    if (a.xsw || a.xsw_m) kern = strict ? member_kernel<true, false, true, true> : member_kernel<false, false, true, true>;
+    else kern = strict ? member_kernel<true, false, false, true> : member_kernel<false, false, false, true>;
+  } else if (a.xsw || a.xsw_m) { // sensitivity experiment (of every member or of some): the switch-aware instantiation
     if (a.flux_phase) kern = strict ? member_kernel<true, true, true> : member_kernel<false, true, true>;
     else kern = strict ? member_kernel<true, false, true> : member_kernel<false, false, true>;
   } else if (a.flux_phase) kern = strict ? member_kernel<true, true, false> : member_kernel<false, true, false>;

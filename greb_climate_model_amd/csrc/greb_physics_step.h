@@ -87,12 +87,52 @@ __device__ __forceinline__ PhysIn physics_load(const MemberArgs& a, int qd, cons
   return i;
 }
 
+// Budget output (BUDGET instantiations, scenario phase only): where the thirteen flux terms of a step go.  Block-uniform:
+// the member's running sums [kNBudget][np], and -- on the last step of a month -- the month's record and its step count
+// (:974-984; step_clock is the one source of month ends for both record kinds).
+struct BudgetSink {
+  float* sum;
+  float* rec; // null unless a month ends with this step
+  float ndm;
+};
+template <bool BUDGET>
+__device__ __forceinline__ BudgetSink budget_sink(const MemberArgs& a, int m, const StepClock& ck) {
+  BudgetSink b{nullptr, nullptr, 1.f};
+  if (BUDGET) {
+    b.sum = a.bsum + (size_t)m * kNBudget * a.np;
+    if (ck.mon >= 0) {
+      b.ndm = (float)(kMonthDays[ck.mon] * 2);
+      b.rec = a.brec + (((size_t)m * a.brec_years + (a.brec_year0 + ck.yr_rel)) * 12 + ck.mon) * kNBudget * a.np;
+    }
+  }
+  return b;
+}
+// One term of one point into its sum, by its own load, add and store as soon as the term exists: nothing of the budget
+// lives across the physics of a quad (the FAST member kernel has no register to spare there).  At a month's end the mean
+// leaves non-temporally, as the five standard records do, and the sum restarts from zero.
+template <bool BUDGET>
+__device__ __forceinline__ void budget_add(const BudgetSink& b, int np, int term, int p, float x) {
+  if (BUDGET) {
+#pragma clang fp contract(off)
+    float* s = b.sum + (size_t)term * np + p;
+    float v = *s + x;
+    if (b.rec) {
+      __builtin_nontemporal_store(v / b.ndm, b.rec + (size_t)term * np + p);
+      v = 0.f;
+    }
+    *s = v;
+  }
+}
+
 // the point physics and the Euler update of the quad (src/greb.f90:254-268 scenario, :328-361 flux correction);
-// xTa, xq: the tracers after the 24 circulation sub-steps
-template <bool STRICT, bool FLUX, bool EXP>
+// xTa, xq: the tracers after the 24 circulation sub-steps.  BUDGET: the terms of the update are also added to the member's
+// budget sums (bs; p0: the quad's first point) -- under a member's switches they are what the update really used.
+template <bool STRICT, bool FLUX, bool EXP, bool BUDGET = false>
 __device__ __forceinline__ PhysOut physics_compute(const MemberArgs& a, const Phys& P, const PhysIn& in, float co2, const f4& xTa,
-                                                   const f4& xq, unsigned xsw_member) {
+                                                   const f4& xq, unsigned xsw_member, const BudgetSink& bs = BudgetSink{}, int p0 = 0) {
+  static_assert(!(BUDGET && FLUX), "the flux-correction phase delivers no budget");
   const unsigned xsw = EXP ? xsw_member : 0u;
+  const int np = a.np;
   PhysOut o;
   o.TF = o.qF = o.ToF = zero4();
 #pragma unroll
@@ -108,12 +148,21 @@ __device__ __forceinline__ PhysOut physics_compute(const MemberArgs& a, const Ph
     const bool calm = EXP && (xsw & kXNoCirc);
     const float dTa_crcl = calm ? 0.f : xTa.v[e] - Ta1; // :551
     const float dq_crcl = (calm || (EXP && (xsw & kXNoQTransport))) ? 0.f : xq.v[e] - q1; // greb.original.model.f90:554-555
+    budget_add<BUDGET>(bs, np, kBdTaCrcl, p0 + e, dTa_crcl); budget_add<BUDGET>(bs, np, kBdqCrcl, p0 + e, dq_crcl);
     float albedo, sw, LWsurf, LWdown, em, Qlat, Qlat_air, dq_eva, dq_rain, dT_ocean, dTo;
     sw_radiation<STRICT>(P, Ts1, zt, gl, cld, in.solar, albedo, sw, xsw);
+    budget_add<BUDGET>(bs, np, kBsw, p0 + e, sw);
     lw_radiation<STRICT>(P, Ts1, Ta1, q1, co2, ez, cld, tcl, LWsurf, LWdown, em, xsw, in.qcl.v[e]);
+    budget_add<BUDGET>(bs, np, kBLWsurf, p0 + e, LWsurf); budget_add<BUDGET>(bs, np, kBLWdown, p0 + e, LWdown);
+    const float LWabs = em * LWsurf; // the product of :260
+    budget_add<BUDGET>(bs, np, kBLWabs, p0 + e, LWabs);
     const float Qsens = P.ct_sens * (Ta1 - Ts1); // :295
+    budget_add<BUDGET>(bs, np, kBQsens, p0 + e, Qsens);
     hydro<STRICT>(P, Ts1, q1, in.u.v[e], in.v.v[e], zt, ez, in.swet.v[e], Qlat, Qlat_air, dq_eva, dq_rain, xsw);
+    budget_add<BUDGET>(bs, np, kBQlat, p0 + e, Qlat); budget_add<BUDGET>(bs, np, kBQlatAir, p0 + e, Qlat_air);
+    budget_add<BUDGET>(bs, np, kBdqEva, p0 + e, dq_eva); budget_add<BUDGET>(bs, np, kBdqRain, p0 + e, dq_rain);
     deep_ocean<STRICT>(P, Ts1, To1, zt, mld, in.mldm.v[e], in.zo.v[e], dT_ocean, dTo, xsw);
+    budget_add<BUDGET>(bs, np, kBdTocean, p0 + e, dT_ocean); budget_add<BUDGET>(bs, np, kBdTo, p0 + e, dTo);
     const float LWup = LWdown; // :432
     float Ts0, Ta0, To0, q0;
     if (FLUX) {
@@ -198,13 +247,13 @@ __device__ __forceinline__ void physics_store(const MemberArgs& a, int m, int qd
 }
 
 // the three pieces in a row (one quad per thread: the any-grid engine)
-template <bool STRICT, bool FLUX, bool EXP = false>
+template <bool STRICT, bool FLUX, bool EXP = false, bool BUDGET = false>
 __device__ __forceinline__ void physics_quad(const MemberArgs& a, const Phys& P, int m, int qd, const StepClock& ck,
                                              float co2, float* __restrict__ state, float* __restrict__ acc,
                                              float* __restrict__ corr, const f4& xTa, const f4& xq, f4& oTa_out,
                                              f4& oq_out, f4& tsmn_mean, unsigned xsw = 0u) {
   const PhysIn in = physics_load<FLUX, EXP>(a, qd, ck, state, acc, corr, xsw);
-  const PhysOut o = physics_compute<STRICT, FLUX, EXP>(a, P, in, co2, xTa, xq, xsw);
+  const PhysOut o = physics_compute<STRICT, FLUX, EXP, BUDGET>(a, P, in, co2, xTa, xq, xsw, budget_sink<BUDGET>(a, m, ck), 4 * qd);
   physics_store<FLUX>(a, m, qd, ck, o, state, acc, corr, tsmn_mean);
   oTa_out = o.Ta; oq_out = o.q;
 }

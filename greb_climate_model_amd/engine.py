@@ -57,7 +57,7 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_ensemble_moments_dev", "greb_ensemble_quantiles_dev", "greb_engine_set_state", "greb_release_caches", "greb_diffusion_launch_order",
            "greb_substep_launch_order", "greb_circulation_launch_plan", "greb_engine_describe",
            "greb_engine_create_members", "greb_engine_set_member_experiments", "greb_diag_create", "greb_diag_destroy",
-           "greb_diag_reduce_dev", "greb_engine_run_diag"]
+           "greb_diag_reduce_dev", "greb_engine_run_diag", "greb_engine_run_budget", "greb_budget_name"]
 
 
 def _check(rc: int, h=None):
@@ -68,6 +68,14 @@ def _check(rc: int, h=None):
 
 def device_info(device: int = 0) -> dict:
     return json.loads(lib().greb_device_info(device).decode())
+
+
+def budget_name(i: int) -> str | None:
+    """greb_budget_name: the library's name of budget term i (abi.BUDGET_NAMES mirrors them), None outside 0 ... 12."""
+    f = lib().greb_budget_name
+    f.restype = C.c_char_p
+    s = f(int(i))
+    return None if s is None else s.decode()
 
 
 def log_exp_switches(log_exp: int) -> int:
@@ -195,6 +203,28 @@ class Engine:
         _check(lib().greb_engine_run(self.h, int(years), abi.fptr(co2), C.c_void_p(monthly_dev_ptr), abi.fptr(yearly),
                                      abi.RUN_DEVICE_OUT), self.h)
         return None, yearly
+
+    def run_budget(self, years: int, co2_ppm, want_monthly: bool = True, monthly_dev_ptr: int | None = None,
+                   budget_dev_ptr: int | None = None):
+        """The scenario run of run() that also hands back the monthly means of the thirteen flux terms of the update
+        (abi.BUDGET_NAMES; greb_engine_run_budget).  Returns (monthly, budget, yearly) with budget
+        [n_members][years][12][13][ny][nx]; monthly is None with want_monthly=False (a budget-only run).  State, clock,
+        monthly and yearly are those of run() over the same years.  With budget_dev_ptr (a device address) the records
+        stay on the GPU (GREB_RUN_DEVICE_OUT: monthly then goes to monthly_dev_ptr, or nowhere) and both are None."""
+        co2 = np.ascontiguousarray(np.broadcast_to(np.asarray(co2_ppm, np.float32), (self.nm, years)))
+        yearly = np.zeros((self.nm, years, 2), np.float32)
+        f = lib().greb_engine_run_budget
+        if budget_dev_ptr is not None:
+            _check(f(self.h, int(years), abi.fptr(co2), None if monthly_dev_ptr is None else C.c_void_p(monthly_dev_ptr),
+                     C.c_void_p(budget_dev_ptr), abi.fptr(yearly), abi.RUN_DEVICE_OUT), self.h)
+            return None, None, yearly
+        if monthly_dev_ptr is not None:
+            raise GrebError(-1, "run_budget: monthly_dev_ptr needs budget_dev_ptr (one run delivers to one side)")
+        monthly = np.empty((self.nm, years, 12, 5, self.ny, self.nx), np.float32) if want_monthly else None
+        budget = np.empty((self.nm, years, 12, abi.NBUDGET, self.ny, self.nx), np.float32)
+        _check(f(self.h, int(years), abi.fptr(co2), None if monthly is None else abi.fptr(monthly), abi.fptr(budget),
+                 abi.fptr(yearly), 0), self.h)
+        return monthly, budget, yearly
 
     def run_diag(self, years: int, co2_ppm, plan, what: int | None = None):
         """The scenario run of run() that hands back only the reduced products of `plan` (diag.Plan): regional means,

@@ -93,6 +93,16 @@ module greb_c_api
        real(c_float), intent(in) :: co2_ppm(*)
        real(c_float), intent(out) :: regions(*), zonal(*), annual(*), yearly(*)
      end function
+     ! greb_engine_run that also delivers the monthly means of the 13 flux terms of the update (GREB_B_* of greb_engine.h):
+     ! budget(nx,ny,13,12,years,n_members); monthly as in greb_engine_run, or c_null_ptr for a budget-only run
+     integer(c_int) function greb_engine_run_budget(eng, years, co2_ppm, monthly, budget, yearly, run_flags) &
+          bind(C, name="greb_engine_run_budget")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, monthly
+       integer(c_int), value :: years, run_flags
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: budget(*), yearly(*)
+     end function
      integer(c_int) function greb_engine_get_corrections(eng, member, corr, state5) &
           bind(C, name="greb_engine_get_corrections")
        import :: c_int, c_ptr, c_float

@@ -155,6 +155,41 @@ const char* greb_engine_describe(greb_engine* e);
 int greb_engine_run(greb_engine* e, int years, const float* co2_ppm, float* monthly, float* yearly,
                     unsigned run_flags);
 
+/* ---- budget output: monthly means of the energy and water flux terms ------------------------------
+ * Every step the point physics evaluates the terms of the reference's update (src/greb.f90:254-268, 277-308) and folds
+ * them into the new state.  They are non-linear in the state, so the monthly mean of a flux is not the flux of the
+ * monthly-mean state: only the step loop can deliver them.  GREB_NBUDGET fields per month, in the order, with the sign and
+ * in the unit in which the update uses them; a monthly mean is the fp32 sum of the step values over the month divided by
+ * 2 * days (the rule and the month boundaries of :974-984).  Under a member's GREB_X_* switches the terms are what the
+ * update really used: 0 where a process is switched off.  The flux corrections TF, qF, ToF are not terms
+ * (greb_engine_get_corrections has them per step). */
+#define GREB_NBUDGET 13
+#define GREB_B_SW          0  /* absorbed solar, :258                                   W/m2 */
+#define GREB_B_LW_SURF     1  /* surface long-wave (negative), :258                     W/m2 */
+#define GREB_B_LWAIR_DOWN  2  /* :258, :260 (LWair_up equals it, :432)                  W/m2 */
+#define GREB_B_LW_ABS      3  /* em * LW_surf as formed in :260                         W/m2 */
+#define GREB_B_Q_SENS      4  /* :295                                                   W/m2 */
+#define GREB_B_Q_LAT       5  /*                                                        W/m2 */
+#define GREB_B_Q_LAT_AIR   6  /*                                                        W/m2 */
+#define GREB_B_DQ_EVA      7  /*                                                        1/s  */
+#define GREB_B_DQ_RAIN     8  /*                                                        1/s  */
+#define GREB_B_DT_OCEAN    9  /*                                                        K per step */
+#define GREB_B_DTO         10 /*                                                        K per step */
+#define GREB_B_DTA_CRCL    11 /* the Tair increment of the circulation sub-steps, :551  K per step */
+#define GREB_B_DQ_CRCL     12 /* the same for q, after the switch handling              per step */
+/* "sw", "LW_surf", ... for i = 0 ... GREB_NBUDGET - 1, NULL otherwise. */
+const char* greb_budget_name(int i);
+/* greb_engine_run that also delivers
+ *   budget : [n_members][years][12][GREB_NBUDGET][ny][nx]   host memory, or device memory under GREB_RUN_DEVICE_OUT,
+ *            exactly as `monthly`
+ * monthly, yearly, the model clock and the state the engine is left in are those of greb_engine_run over the same years,
+ * bit for bit.  monthly may be NULL (a budget-only run); a NULL budget is GREB_E_INVALID.  Scenario phase only: the
+ * flux-correction phase delivers nothing, as in the reference.  Host delivery follows greb_engine_run's scheme (two
+ * staging slots, year y leaves while year y + 1 integrates); device memory does not grow with `years`.  The budget sums
+ * are zero at every year boundary, so run and run_budget calls may alternate freely. */
+int greb_engine_run_budget(greb_engine* e, int years, const float* co2_ppm, float* monthly, float* budget, float* yearly,
+                           unsigned run_flags);
+
 /* ---- reduced output: regional, zonal and annual diagnostics made on the device ------------------
  * The reference leaves every diagnostic to R scripts over the output file (R/analyse_output_fields.R).  A big ensemble
  * cannot hand back [n_members][years][12][5][ny][nx]; what its analysis wants per member is small, and comes from ONE pass

@@ -5,7 +5,9 @@ stamp code).  Prints, as medians over the members (= workgroups = CUs):
   * cycles per model step spent in wind staging / the 24 circulation sub-steps / point physics + accumulation
   * per wave: busy cycles per sub-step (barrier release -> arrival at the next barrier) and the share of the
     sub-step it waits at the barrier -- which wave is the critical path
-  python tools/stamp_member.py [members=512] [years=2]"""
+  python tools/stamp_member.py [members=512] [years=2] [budget]
+`budget`: the stamped years run through Engine.run_budget (the budget instantiation: its physics phase includes the
+accumulation pre-pass)."""
 import ctypes as C
 import os
 import sys
@@ -21,6 +23,7 @@ if os.environ.get("GREB_LIB"):  # a variant build of the tuning library (deal ex
     engine._lib_path = os.path.abspath(os.environ["GREB_LIB"])
 M = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 years = int(sys.argv[2]) if len(sys.argv) > 2 else 2
+budget = len(sys.argv) > 3 and sys.argv[3] == "budget"
 inp = workload.make_inputs()
 p = engine.params_default(); p.ipx, p.ipy = 95, 38
 e = engine.Engine(inp, p, n_members=M)
@@ -34,8 +37,12 @@ f = engine.lib().greb_tuning_set_stamps
 f.argtypes = [C.c_void_p, C.c_void_p]
 assert f(e.h, st.data_ptr()) == 0
 tot = np.zeros((M, 8, 8), np.float64)
+bud = torch.empty((M, 1, 12, 13, e.np), dtype=torch.float32, device="cuda") if budget else None
 for _ in range(years):
-    e.run(1, levels[:, None], monthly_dev_ptr=mon.data_ptr())
+    if budget:
+        e.run_budget(1, levels[:, None], monthly_dev_ptr=mon.data_ptr(), budget_dev_ptr=bud.data_ptr())
+    else:
+        e.run(1, levels[:, None], monthly_dev_ptr=mon.data_ptr())
     torch.cuda.synchronize()
     tot += st.cpu().numpy().astype(np.float64)
 f(e.h, None)
@@ -44,7 +51,7 @@ tot /= years
 cyc, rt, wind, circ, busy, phys, nsteps, nsub = [tot[:, :, i] for i in range(8)]
 clk = np.median(cyc[:, 0] / rt[:, 0]) * 100.0  # MHz
 ns, nsb = nsteps[0, 0], nsub[0, 0]
-print(f"members {M}: launch = {np.median(cyc[:, 0]) / 1e6:.1f} Mcycles = {np.median(rt[:, 0]) / 1e5:.2f} ms; "
+print(f"{'run_budget' if budget else 'run'}: members {M}: launch = {np.median(cyc[:, 0]) / 1e6:.1f} Mcycles = {np.median(rt[:, 0]) / 1e5:.2f} ms; "
       f"in-kernel clock {clk:.0f} MHz (median over workgroups; min {np.min(cyc[:, 0] / rt[:, 0]) * 100:.0f}, max {np.max(cyc[:, 0] / rt[:, 0]) * 100:.0f})")
 w0 = lambda x: np.median(x[:, 0]) / ns
 print(f"per model step (wave 0): wind staging {w0(wind):.0f} cyc, circulation {w0(circ):.0f} cyc ({w0(circ) / nsb:.0f} per sub-step), "
