@@ -7,7 +7,7 @@ import pytest
 from greb_climate_model_amd import abi, engine
 
 
-@pytest.mark.parametrize("batch", [1, 2, 7, 8, 9, 37, 1024])
+@pytest.mark.parametrize("batch", [1, 2, 7, 8, 9, 37, 161, 168, 179, 1024])
 @pytest.mark.parametrize("kappa", [None, 7.2e5])
 def test_every_row_of_every_field_exactly_once(batch, kappa):
     p = abi.default_params()
