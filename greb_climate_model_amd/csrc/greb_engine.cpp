@@ -1289,6 +1289,12 @@ int greb_diffusion_launch_order(const greb_params* p, int nx, int ny, int batch,
   return (int)tasks.size();
 }
 
+int greb_member_deal_cover(int strict, int* counts) {
+  if (!counts) return fail(nullptr, GREB_E_INVALID, "member_deal_cover: bad argument");
+  member_deal_cover(strict != 0, counts);
+  return 0;
+}
+
 int greb_substep_launch_order(const greb_params* p, int nx, int ny, int n_members, const float* kappa, int* field, int* k0,
                               int* k1, int capacity) {
   if (!p || nx < 12 || (nx & 3) || ny < 5 || ny > kMaxNy || n_members < 1 || capacity < 0 || (capacity > 0 && (!field || !k0 || !k1)))

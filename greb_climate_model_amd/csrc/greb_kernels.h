@@ -83,6 +83,8 @@ enum { kBsw, kBLWsurf, kBLWdown, kBLWabs, kBQsens, kBQlat, kBQlatAir, kBdqEva, k
 // fused engine (greb_member.hip): 96x48 with the default sub-cycling layout -- rows 0-9 and 38-47
 // sub-cycled, only the two polar rows iterating; whole member resident in one CU
 bool member_layout_supported(const RowTables& tab, int nx, int ny);
+// how often the member kernel's static deal computes each row-quad of the 96x48 grid: counts[48 * 24]
+void member_deal_cover(bool strict, int* counts);
 hipError_t launch_member_kernel(const MemberArgs& a, int n_members, bool strict, hipStream_t s);
 hipError_t launch_circulation_g96(const float* X, const float* wz, const float* u, const float* v, float* dX,
                                   const RowTables* tab_dev, int batch, int nsub, bool strict, hipStream_t s);

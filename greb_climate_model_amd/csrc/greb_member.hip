@@ -23,9 +23,9 @@
 //   a TASK works on pair-quads: 4 longitudes x (Tair,q) of one row, or of two vertically stacked rows that share
 //   the six rows of their column (44 instead of 62 ds_read_b128).  The 46 non-polar rows are the "sub" family
 //   (rows 1-9, 38-46: sub-cycled formulas, one sweep) and the "full" family (rows 10-37).  A PASS is 64 tasks of
-//   one kind, one per lane; FAST: 3 passes of sub row-pairs, 3 of full row-pairs, 1 + 4.5 of single rows,
-//   in both arithmetic modes; dealt statically to the seven (STRICT: six) bulk waves (see "The schedule") with
-//   each lane's task addresses computed once per launch.
+//   one kind, one per lane; 3 passes of sub row-pairs, 3 of full row-pairs, 1 + 4.5 of single rows, in both arithmetic
+//   modes; dealt statically to the seven (STRICT: six) bulk waves (see "The schedule") with each lane's task addresses
+//   computed once per circulation call.
 //   polar rows 0 / 47 (8 dependent Jacobi sweeps per diffusion call, src/greb.f90:656-717): FAST -- ONE wave, each
 //   DPP row of 16 lanes x 6 longitudes one (pole, tracer) chain, neighbours by row rotates (quad_chain_substep);
 //   STRICT -- one wave per pole, 48 lanes x 2 longitudes x (Tair,q), neighbours by ds_bpermute (chain_substep).
@@ -59,6 +59,7 @@ constexpr int kOffW = 2 * XB + RS;  // row 0 of W  [NY][NX][{wz_air,wz_vapor}]
 constexpr int kOffWX = 3 * XB;      // [NP]  cu*u   (raw u in rows 0, 47 and in STRICT)
 constexpr int kOffWY = kOffWX + NP; // [NP]  ccy/3*v (raw v ...)
 constexpr int kOffRowK = kOffWY + NP; // [NY][kRowKWords]
+constexpr int kRowKCsDif = 7;        // FAST: dif_cc/20 in the spare word of a row's constants (Circ::init)
 constexpr int kLdsFloats = kOffRowK + NY * kRowKWords;
 constexpr size_t kLdsBytes = (size_t)kLdsFloats * sizeof(float);
 
@@ -111,27 +112,23 @@ __device__ __forceinline__ q8 ld8p(const lfloat* p) {
 template <bool SUB>
 __device__ __forceinline__ q8 fast_row(const q8& LT, const q8& CT, const q8& RT, const q8& Tm2, const q8& Tm1, const q8& Tp1,
                                        const q8& Tp2, const q8& LW, const q8& CW, const q8& RW, const q8& Wm2, const q8& Wm1,
-                                       const q8& Wp1, const q8& Wp2, const f4& xq, const f4& yq, int k, bool last_quad,
-                                       float dif_cc, float dif_ccy, bool calm_q) {
+                                       const q8& Wp1, const q8& Wp2, const f4& xq, const f4& yq, bool last_quad,
+                                       float cs_dif, float dif_ccy, bool calm_q) {
   v2 T[12], w[12];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     T[j] = LT.v[j]; T[4 + j] = CT.v[j]; T[8 + j] = RT.v[j];
     w[j] = LW.v[j]; w[4 + j] = CW.v[j]; w[8 + j] = RW.v[j];
   }
-  // the latitudinal advection term is not divided by 3 at k = 1 (v>=0 part) and k = ny-2 (v<0 part)
-  // (only rows 1 and NY-2, which are in the sub-cycled family: the full family skips the two multiplications)
-  const float fm = SUB && k == 1 ? 3.f : 1.f, fp = SUB && k == NY - 2 ? 3.f : 1.f; // :766-769, :784-787
+  // (the latitudinal advection term is not divided by 3 at k = 1 (v>=0 part) and k = ny-2 (v<0 part), :766-769, :784-787:
+  // stage_winds folds that factor into the staged v of rows 1 and NY-2, once per model step)
   float um[4], up[4], vm[4], vp[4]; // the sign split is shared by the two tracers
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     split_sign(xq.v[i], um[i], up[i]);
-    float a, b;
-    split_sign(yq.v[i], a, b);
-    vm[i] = SUB ? fm * a : a; vp[i] = SUB ? fp * b : b;
+    split_sign(yq.v[i], vm[i], vp[i]);
   }
-  return substep_pair<SUB>(T, w, Tm2, Tm1, Tp1, Tp2, Wm2, Wm1, Wp1, Wp2, um, up, vm, vp, dif_cc * 0.05f, dif_ccy, last_quad,
-                           calm_q);
+  return substep_pair<SUB>(T, w, Tm2, Tm1, Tp1, Tp2, Wm2, Wm1, Wp1, Wp2, um, up, vm, vp, cs_dif, dif_ccy, last_quad, calm_q);
 }
 
 __device__ __forceinline__ void st8p(lfloat* o, const q8& xn) {
@@ -197,18 +194,20 @@ __device__ __forceinline__ q8 one_row(const q8& LT, const q8& CT, const q8& RT, 
                                       const q8& Wp1, const q8& Wp2, const f4& xq, const f4& yq, int k, int q, const RowK& rk,
                                       bool calm_q) {
   if (STRICT) return strict_row(LT, CT, RT, Tm2, Tm1, Tp1, Tp2, LW, CW, RW, Wm2, Wm1, Wp1, Wp2, xq, yq, k, q, rk, calm_q);
-  return fast_row<SUB>(LT, CT, RT, Tm2, Tm1, Tp1, Tp2, LW, CW, RW, Wm2, Wm1, Wp1, Wp2, xq, yq, k, q == NQ - 1, rk.dif_cc, rk.dif_ccy,
+  // FAST: rk.dif_cc holds the row's dif_cc/20 as Circ::init staged it (task_consts)
+  return fast_row<SUB>(LT, CT, RT, Tm2, Tm1, Tp1, Tp2, LW, CW, RW, Wm2, Wm1, Wp1, Wp2, xq, yq, q == NQ - 1, rk.dif_cc, rk.dif_ccy,
                        calm_q);
 }
 
-// the row constants a task needs: everything in STRICT, two words in FAST (the advection constants are folded into
-// the staged winds) -- the full 32-byte read costs the FAST loop 3 %
+// the row constants a task needs: everything in STRICT; in FAST ONE word, the row's dif_cc/20 as Circ::init staged it
+// (the advection constants are folded into the staged winds, and dif_ccy is the same in every row: the caller read it
+// once per circulation call, role_loop) -- the full 32-byte read costs the FAST loop 3 %
 template <bool STRICT>
-__device__ __forceinline__ RowK task_consts(const lfloat* lds, int k) {
+__device__ __forceinline__ RowK task_consts(const lfloat* lds, int k, float ccy_dif) {
   if (STRICT) return row_consts((const lfloat*)(lds + kOffRowK), k);
   RowK rk{};
-  rk.dif_cc = lds[kOffRowK + k * kRowKWords];
-  rk.dif_ccy = lds[kOffRowK + k * kRowKWords + 2];
+  rk.dif_cc = lds[kOffRowK + k * kRowKWords + kRowKCsDif];
+  rk.dif_ccy = ccy_dif;
   return rk;
 }
 
@@ -216,11 +215,11 @@ __device__ __forceinline__ RowK task_consts(const lfloat* lds, int k) {
 // rows make k-2 = -1 and k+2 = NY valid reads: zero weights in FAST, not referenced by the reference's boundary
 // formulas in STRICT), the row's left and right quads from the two precomputed offsets.
 template <bool STRICT, bool SUB>
-__device__ __forceinline__ void row_task(lfloat* lds, int cur, const TaskAddr& ta, bool calm_q = false) {
+__device__ __forceinline__ void row_task(lfloat* lds, int cur, const TaskAddr& ta, float ccy_dif, bool calm_q = false) {
   const int k = ta.kq & 255, q = ta.kq >> 8;
   const lfloat* Xc = lds + kOffX + cur * XB;
   const lfloat* Wc = lds + kOffW;
-  const RowK rk = row_consts((const lfloat*)(lds + kOffRowK), k); // (the two-word form of task_consts measured 3 % slower HERE)
+  const RowK rk = task_consts<STRICT>(lds, k, ccy_dif);
   const f4 xq = ld4(lds + kOffWX + k * NX + 4 * q), yq = ld4(lds + kOffWY + k * NX + 4 * q);
   const lfloat* xb = Xc + ta.c - 2 * RS;
   const lfloat* wb = Wc + ta.c - 2 * RS;
@@ -235,7 +234,7 @@ __device__ __forceinline__ void row_task(lfloat* lds, int cur, const TaskAddr& t
 // column are loaded once and shared -- 44 instead of 62 ds_read_b128 for the two rows.  The sub-step loop is
 // co-limited by LDS bandwidth: dropping 39 % of the bulk reads (timing experiment) made it 12 % faster.
 template <bool STRICT, bool SUB>
-__device__ __forceinline__ void row_task2(lfloat* lds, int cur, const TaskAddr& ta, bool calm_q = false) {
+__device__ __forceinline__ void row_task2(lfloat* lds, int cur, const TaskAddr& ta, float ccy_dif, bool calm_q = false) {
   const int k = ta.kq & 255, q = ta.kq >> 8;
   const lfloat* Xc = lds + kOffX + cur * XB;
   const lfloat* Wc = lds + kOffW;
@@ -247,7 +246,7 @@ __device__ __forceinline__ void row_task2(lfloat* lds, int cur, const TaskAddr& 
   {
     const q8 LT = ld8p(Xc + ta.l), RT = ld8p(Xc + ta.r), LW = ld8p(Wc + ta.l), RW = ld8p(Wc + ta.r);
     const f4 xq = ld4(lds + kOffWX + k * NX + 4 * q), yq = ld4(lds + kOffWY + k * NX + 4 * q);
-    const RowK rk = task_consts<STRICT>(lds, k);
+    const RowK rk = task_consts<STRICT>(lds, k, ccy_dif);
     st8p(out, one_row<STRICT, SUB>(LT, T2, RT, T0, T1, T3, T4, LW, W2, RW, W0, W1, W3, W4, xq, yq, k, q, rk, calm_q));
   }
   __builtin_amdgcn_sched_barrier(0); // row k+1 after row k: keeps the two rows' temporaries from piling up
@@ -255,7 +254,7 @@ __device__ __forceinline__ void row_task2(lfloat* lds, int cur, const TaskAddr& 
     const q8 T5 = ld8p(xb + 5 * RS), W5 = ld8p(wb + 5 * RS); // row k+3: only the second row needs it
     const q8 LT = ld8p(Xc + ta.l + RS), RT = ld8p(Xc + ta.r + RS), LW = ld8p(Wc + ta.l + RS), RW = ld8p(Wc + ta.r + RS);
     const f4 xq = ld4(lds + kOffWX + (k + 1) * NX + 4 * q), yq = ld4(lds + kOffWY + (k + 1) * NX + 4 * q);
-    const RowK rk = task_consts<STRICT>(lds, k + 1);
+    const RowK rk = task_consts<STRICT>(lds, k + 1, ccy_dif);
     st8p(out + RS, one_row<STRICT, SUB>(LT, T3, RT, T1, T2, T4, T5, LW, W3, RW, W1, W2, W4, W5, xq, yq, k + 1, q, rk, calm_q));
   }
 }
@@ -263,10 +262,13 @@ __device__ __forceinline__ void row_task2(lfloat* lds, int cur, const TaskAddr& 
 struct BulkTasks { TaskAddr t[3]; };
 
 // The schedule (both arithmetic modes).  Task kinds: one row (S1 sub-cycled family, F1 full family) or two stacked rows (ST, FT).
-//   ST  rows (1,2) (3,4) (5,6) (7,8) (39,40) .. (45,46) : 8 pairs x 24 quads = 3 full passes   (426 VALU instructions)
-//   FT  rows (10,11) .. (24,25)                          : 8 pairs x 24 quads = 3 full passes   (306)
-//   S1  rows 9, 38                                       : 48 tasks, one pass                   (223)
-//   F1  rows 26 .. 37                                    : 288 tasks, 4.5 passes                (156)
+//   ST  rows (1,2) (3,4) (5,6) (7,8) (39,40) .. (45,46) : 8 pairs x 24 quads = 3 full passes
+//   FT  rows (10,11) .. (24,25)                          : 8 pairs x 24 quads = 3 full passes
+//   S1  rows 9, 38                                       : 48 tasks, one pass
+//   F1  rows 26 .. 37                                    : 288 tasks, 4.5 passes
+// VALU instructions per pass in FAST before the factor 3 of rows 1 / 46 moved to stage_winds and dif_cc/20 to Circ::init:
+// ST 426, FT 306, S1 223, F1 156.  After it the sub-step loop bodies of the bulk waves hold 288 / 346 / 435 / 493 / 493
+// vector instructions where they held 290 / 364 / 438 / 512 / 512 (read off the release library's ISA).
 // Waves w and w+4 share a SIMD; the polar rows (a dependent chain of 8 + 1 Jacobi sweeps per sub-step) have their own
 // wave(s): wave 6 in FAST, waves 2 and 3 in STRICT.  The SIMD's issue arbiter favours the OLDER wave; the younger one runs in the
 // slots that leaves, and once the older wave is done the younger runs alone at a single wave's issue rate (one
@@ -297,7 +299,12 @@ struct Pass { int kind, index; };
 //     S0+F0 S2+T0 C     H+F1+F2 | S1    T2    T1    F3+F4   5 094
 //     S0    S2+F0 C     H+F1+F2 | S1    T0    T1+T2 F3+F4   5 988   (two FT passes behind the chain wave)
 //   chains on wave 7 (younger wave of SIMD 3): 5 432
-// With the table below the busiest wave of each SIMD is busy 4 325 / 4 348 / 4 379 / 4 368 cycles: balanced to 1 %.
+// With the table below the busiest wave of each SIMD is busy 4 318 / 4 296 / 4 225 / 4 393 cycles.
+// Also measured (same tooling, one call, chains on wave 6, this table 4 684): the full family's 672 row-quads dealt as
+// X = 4 passes of (row pair, quad) tasks + 2.5 passes of single rows instead of 3 + 4.5 -- a lane's pair task need not
+// belong to a whole row pair -- took 4 654 at best (S0+F0 S2+F1 T1+F2 T2+H | S1 T0 C T3), 4 658 and 4 850 in two other
+// deals; X = 5 (+ half a single pass) 5 060 .. 5 641 in four deals: a fifth pair pass finds no SIMD it balances on.  30
+// cycles did not pay for a second task enumeration; the split stays 3 + 4.5.
 __host__ __device__ constexpr Pass deal_fast(int wave, int i) {
   constexpr Pass none{kNone, 0};
 #if defined(GREB_TUNING) && defined(GREB_DEAL_FAST) // tools/deal_search.py: a deal given on the compiler command line
@@ -341,31 +348,67 @@ constexpr int kPolarWaveFast = 6;
 template <bool STRICT>
 __host__ __device__ constexpr bool is_polar_wave(int wave) { return STRICT ? (wave == 2 || wave == 3) : wave == kPolarWaveFast; }
 
-// every pass of every kind is dealt to exactly one wave slot (a deal that drops or doubles a pass would still "run")
-template <bool STRICT>
-__host__ __device__ constexpr int times_dealt(int kind, int index) {
-  int n = 0;
-  for (int w = 0; w < 8; ++w)
-    for (int i = 0; i < 3; ++i) n += (deal<STRICT>(w, i).kind == kind && deal<STRICT>(w, i).index == index) ? 1 : 0;
-  return n;
+// the first row and the quad of task t (= 64 * pass index + lane) of a kind; valid = 0: no such task
+struct RowQuad { int k, q, valid; };
+__host__ __device__ constexpr int task_rows(int kind) { return kind == kST || kind == kFT ? 2 : (kind == kS1 || kind == kF1 ? 1 : 0); }
+__host__ __device__ constexpr RowQuad task_rowquad(int kind, int t) {
+  int k = 1, q = 0, valid = 0;
+  const int r = t / NQ;
+  q = t % NQ;
+  // row order: consecutive r of a pass sit two rows (= 8 slot classes) apart wherever the rows allow it
+  if (kind == kST) { valid = r < 8; k = r < 4 ? 1 + 2 * r : (r == 4 ? 41 : (r == 5 ? 39 : (r == 6 ? 45 : 43))); }
+  else if (kind == kFT) { valid = r < 8; k = 10 + 2 * r; }
+  else if (kind == kS1) { valid = r < 2; k = r == 0 ? 9 : 38; if (r == 1) q = (q + 4) % NQ; }
+  else if (kind == kF1) { valid = r < 12; k = r < 6 ? 26 + 2 * r : 27 + 2 * (r - 6); }
+  if (!valid) { k = 1; q = 0; }
+  return RowQuad{k, q, valid};
 }
-template <bool STRICT>
-__host__ __device__ constexpr bool deal_is_complete() {
-  for (int p = 0; p < 3; ++p) if (times_dealt<STRICT>(kST, p) != 1 || times_dealt<STRICT>(kFT, p) != 1) return false;
-  for (int p = 0; p < 5; ++p) if (times_dealt<STRICT>(kF1, p) != 1) return false;
-  if (times_dealt<STRICT>(kS1, 0) != 1) return false;
-  for (int w = 0; w < 8; ++w)
-    for (int i = 0; i < 3; ++i) if (is_polar_wave<STRICT>(w) && deal<STRICT>(w, i).kind != kNone) return false;
-  return true;
-}
-static_assert(deal_is_complete<true>() && deal_is_complete<false>(),
-              "a deal must cover 3 ST, 3 FT, 1 S1 and 5 F1 passes exactly once");
 
-// number of tasks of a pass: 64 = every lane has one
+// number of passes of a kind, and of tasks of one of its passes: 64 = every lane has one
+__host__ __device__ constexpr int kind_passes(int kind) { return kind == kST || kind == kFT ? 3 : (kind == kS1 ? 1 : (kind == kF1 ? 5 : 0)); }
 __host__ __device__ constexpr int pass_tasks(int kind, int index) {
   const int total = kind == kST || kind == kFT ? 8 * NQ : (kind == kS1 ? 2 * NQ : (kind == kF1 ? 12 * NQ : 0));
   const int left = total - 64 * index;
   return left >= 64 ? 64 : (left > 0 ? left : 0);
+}
+
+// How often the deal computes each row-quad: every lane's task of every dealt pass, counted by the rows it writes.
+// (A deal that drops or doubles a pass, or a task enumeration that misses a quad, would still "run".)
+struct DealCover { int n[NY * NQ]; };
+template <bool STRICT>
+__host__ __device__ constexpr DealCover deal_cover() {
+  DealCover c{};
+  for (int w = 0; w < 8; ++w)
+    for (int i = 0; i < 3; ++i) {
+      const Pass p = deal<STRICT>(w, i);
+      if (p.kind == kNone) continue;
+      for (int lane = 0; lane < 64; ++lane) {
+        const RowQuad rq = task_rowquad(p.kind, 64 * p.index + lane);
+        for (int j = 0; j < (rq.valid ? task_rows(p.kind) : 0); ++j) ++c.n[(rq.k + j) * NQ + rq.q];
+      }
+    }
+  return c;
+}
+template <bool STRICT>
+__host__ __device__ constexpr bool deal_is_complete() {
+  for (int w = 0; w < 8; ++w)
+    for (int i = 0; i < 3; ++i) {
+      const Pass p = deal<STRICT>(w, i);
+      if (is_polar_wave<STRICT>(w) && p.kind != kNone) return false;
+      if (p.kind != kNone && (p.index < 0 || p.index >= kind_passes(p.kind))) return false; // a pass without tasks
+    }
+  const DealCover c = deal_cover<STRICT>();
+  for (int k = 0; k < NY; ++k)
+    for (int q = 0; q < NQ; ++q) if (c.n[k * NQ + q] != (k >= 1 && k <= NY - 2 ? 1 : 0)) return false;
+  return true;
+}
+static_assert(deal_is_complete<true>() && deal_is_complete<false>(),
+              "a deal must compute every row-quad of rows 1 .. 46 exactly once and give the polar waves no bulk pass");
+
+// host-visible form of the above (greb_member_deal_cover): counts[k * NQ + q], rows 0 .. NY-1
+void member_deal_cover(bool strict, int* counts) {
+  constexpr DealCover cs = deal_cover<true>(), cf = deal_cover<false>();
+  for (int i = 0; i < NY * NQ; ++i) counts[i] = strict ? cs.n[i] : cf.n[i];
 }
 
 // once per launch; the asm makes the values opaque, so the compiler keeps them instead of re-deriving them from
@@ -375,18 +418,8 @@ __device__ __forceinline__ BulkTasks make_tasks(int wave, int lane) {
   BulkTasks b;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    int k = 1, q = 0, valid = 0;
-    {
-      const int kind = deal<STRICT>(wave, i).kind, t = deal<STRICT>(wave, i).index * 64 + lane;
-      const int r = t / NQ;
-      q = t % NQ;
-      // row order: consecutive r of a pass sit two rows (= 8 slot classes) apart wherever the rows allow it
-      if (kind == kST) { valid = r < 8; k = r < 4 ? 1 + 2 * r : (r == 4 ? 41 : (r == 5 ? 39 : (r == 6 ? 45 : 43))); }
-      else if (kind == kFT) { valid = r < 8; k = 10 + 2 * r; }
-      else if (kind == kS1) { valid = r < 2; k = r == 0 ? 9 : 38; if (r == 1) q = (q + 4) % NQ; }
-      else if (kind == kF1) { valid = r < 12; k = r < 6 ? 26 + 2 * r : 27 + 2 * (r - 6); }
-      if (!valid) { k = 1; q = 0; }
-    }
+    const RowQuad rq = task_rowquad(deal<STRICT>(wave, i).kind, deal<STRICT>(wave, i).index * 64 + lane);
+    const int k = rq.k, q = rq.q, valid = rq.valid;
     TaskAddr a;
     a.c = k * RS + 4 * q;
     a.l = k * RS + 4 * (q == 0 ? NQ - 1 : q - 1);
@@ -402,21 +435,22 @@ __device__ __forceinline__ BulkTasks make_tasks(int wave, int lane) {
 // per-sub-step dispatch on the wave number (that dispatch, a switch on a VGPR lowered to exec-mask bookkeeping, cost
 // every bulk wave ~100 issue slots per sub-step)
 template <bool STRICT, int SLOT, int I>
-__device__ __forceinline__ void bulk_task(lfloat* lds, int cur, const BulkTasks& tasks, int dbg, bool calm_q) {
+__device__ __forceinline__ void bulk_task(lfloat* lds, int cur, const BulkTasks& tasks, float ccy_dif, int dbg, bool calm_q) {
   constexpr int kind = deal<STRICT>(SLOT, I).kind, ntask = pass_tasks(kind, deal<STRICT>(SLOT, I).index);
   if constexpr (kind != kNone && ntask > 0) {
     if (ntask < 64 && tasks.t[I].kq < 0) return; // partial pass: lanes without a task
-    if constexpr (kind == kS1) { if (!(dbg & 1)) row_task<STRICT, true>(lds, cur, tasks.t[I], calm_q); }
-    else if constexpr (kind == kF1) { if (!(dbg & 2)) row_task<STRICT, false>(lds, cur, tasks.t[I], calm_q); }
-    else if constexpr (kind == kST) { if (!(dbg & 1)) row_task2<STRICT, true>(lds, cur, tasks.t[I], calm_q); }
-    else { if (!(dbg & 2)) row_task2<STRICT, false>(lds, cur, tasks.t[I], calm_q); }
+    if constexpr (kind == kS1) { if (!(dbg & 1)) row_task<STRICT, true>(lds, cur, tasks.t[I], ccy_dif, calm_q); }
+    else if constexpr (kind == kF1) { if (!(dbg & 2)) row_task<STRICT, false>(lds, cur, tasks.t[I], ccy_dif, calm_q); }
+    else if constexpr (kind == kST) { if (!(dbg & 1)) row_task2<STRICT, true>(lds, cur, tasks.t[I], ccy_dif, calm_q); }
+    else { if (!(dbg & 2)) row_task2<STRICT, false>(lds, cur, tasks.t[I], ccy_dif, calm_q); }
   }
 }
 template <bool STRICT, int SLOT>
-__device__ __forceinline__ void bulk_substep(lfloat* lds, int cur, const BulkTasks& tasks, int dbg, bool calm_q = false) {
-  bulk_task<STRICT, SLOT, 0>(lds, cur, tasks, dbg, calm_q);
-  bulk_task<STRICT, SLOT, 1>(lds, cur, tasks, dbg, calm_q);
-  bulk_task<STRICT, SLOT, 2>(lds, cur, tasks, dbg, calm_q);
+__device__ __forceinline__ void bulk_substep(lfloat* lds, int cur, const BulkTasks& tasks, float ccy_dif, int dbg,
+                                             bool calm_q = false) {
+  bulk_task<STRICT, SLOT, 0>(lds, cur, tasks, ccy_dif, dbg, calm_q);
+  bulk_task<STRICT, SLOT, 1>(lds, cur, tasks, ccy_dif, dbg, calm_q);
+  bulk_task<STRICT, SLOT, 2>(lds, cur, tasks, ccy_dif, dbg, calm_q);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -635,7 +669,7 @@ __device__ __forceinline__ void quad_chain_substep(lfloat* lds, int cur, QuadCha
 
 // stage this step's winds (src/greb.f90:203-216, 732): raw for STRICT and for the polar rows,
 // otherwise scaled by the row's advection constants so the sign split is one max/min per use:
-//   x = c*u, c = ccx/3 (full rows) or ccx2/20 (sub-cycled rows);  y = ccy/3 * v
+//   x = c*u, c = ccx/3 (full rows) or ccx2/20 (sub-cycled rows);  y = ccy/3 * v (rows 1 and NY-2: see below)
 // REMAT (the switch-aware FAST kernels, whose sub-step loop exists twice): the thread's addresses are derived anew every
 // model step -- a few instructions -- instead of living in registers across the sub-steps, where that kernel has none left.
 template <bool STRICT, bool REMAT = false>
@@ -664,6 +698,18 @@ __device__ __forceinline__ void stage_winds(lfloat* lds, const float* __restrict
         const float cv = rk.adv_ccy * (1.f / 3.f);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { uq[j].v[e] *= cu; vq[j].v[e] *= cv; }
+        // The latitudinal advection term is not divided by 3 for the v>=0 part of row 1 and the v<0 part of row NY-2
+        // (:766-769, :784-787).  The factor 3 goes onto that part of the staged wind here, once per model step, instead
+        // of onto the split halves in every sub-cycled row task: with y' = 3y where y has the part's sign and y' = y
+        // elsewhere, max(y',0) and y' - max(y',0) are the bits of 3 max(y,0) and y - max(y,0) (row 1), or of max(y,0)
+        // and 3 (y - max(y,0)) (row NY-2); the product still feeds a multiply, so no contraction changes either.
+        if (k == 1 || k == NY - 2) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float y = vq[j].v[e];
+            vq[j].v[e] = (k == 1 ? y > 0.f : y < 0.f) ? 3.f * y : y;
+          }
+        }
       }
       st4(lds + kOffWX + 4 * i, uq[j]); st4(lds + kOffWY + 4 * i, vq[j]);
     }
@@ -682,6 +728,11 @@ struct Circ {
       lds[(g >> 1) * XB + (g & 1) * (NY + 1) * RS + o] = 0.f;
     }
     stage_row_consts(lds + kOffRowK, *tab, 0, NY);
+    // FAST: the diffusion constant as the bulk tasks use it, dif_cc/20, in the row's spare word -- the same single fp32
+    // multiply the tasks did (each thread rescales the rows it has just staged: LDS operations of a thread stay in order)
+    if (!STRICT)
+      for (int k = threadIdx.x; k < NY; k += blockDim.x)
+        lds[kOffRowK + k * kRowKWords + kRowKCsDif] = lds[kOffRowK + k * kRowKWords] * 0.05f;
     for (int i = threadIdx.x; i < NP / 4; i += kThreads)
       st8(lds + kOffW + (i / NQ) * RS, i % NQ, zip(ld4(wz_air + 4 * i), ld4(wz_vapor + 4 * i)));
   }
@@ -705,6 +756,9 @@ struct Circ {
     QuadChain quad;
     if constexpr (!kPolar) tasks = make_tasks<STRICT>(WAVE, lane);
     else if constexpr (!STRICT) quad_chain_setup(lds, cur, lane, calm_q, quad);
+    // FAST bulk waves: dif_ccy, the one row constant that is the same in every row, as a scalar for the whole call
+    float ccy_dif = 0.f;
+    if constexpr (!kPolar && !STRICT) ccy_dif = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(lds[kOffRowK + 2])));
 #pragma unroll 1
     for (int tt = 0; tt < nsub; ++tt) {
 #ifdef GREB_TUNING
@@ -712,7 +766,7 @@ struct Circ {
 #endif
       if constexpr (kPolar && STRICT) { if (!(dbg & 4)) chain_substep_strict(lds, cur, WAVE - 2, lane, calm_q); }
       else if constexpr (kPolar) { if (!(dbg & 4)) quad_chain_substep(lds, cur, quad); }
-      else bulk_substep<STRICT, WAVE>(lds, cur, tasks, dbg, calm_q);
+      else bulk_substep<STRICT, WAVE>(lds, cur, tasks, ccy_dif, dbg, calm_q);
 #ifdef GREB_TUNING
       if (stamp) busy += __builtin_amdgcn_s_memtime() - t0;
 #endif

@@ -57,7 +57,8 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_ensemble_moments_dev", "greb_ensemble_quantiles_dev", "greb_engine_set_state", "greb_release_caches", "greb_diffusion_launch_order",
            "greb_substep_launch_order", "greb_circulation_launch_plan", "greb_engine_describe",
            "greb_engine_create_members", "greb_engine_set_member_experiments", "greb_diag_create", "greb_diag_destroy",
-           "greb_diag_reduce_dev", "greb_engine_run_diag", "greb_engine_run_budget", "greb_budget_name"]
+           "greb_diag_reduce_dev", "greb_engine_run_diag", "greb_engine_run_budget", "greb_budget_name",
+           "greb_member_deal_cover"]
 
 
 def _check(rc: int, h=None):
@@ -341,6 +342,14 @@ def substep_launch_order(params, nx, ny, n_members, kappa=None):
     if n:
         ptr = [a.ctypes.data_as(C.POINTER(C.c_int)) for a in out]
         assert f(C.byref(params), nx, ny, n_members, kp, *ptr, n) == n
+    return out
+
+
+def member_deal_cover(strict=False):
+    """Host-only diagnostic: how often a sub-step of the fused 96x48 member kernel computes each row-quad, int array
+    (48, 24) (include/greb_engine.h: greb_member_deal_cover)."""
+    out = np.zeros((48, 24), np.int32)
+    _check(lib().greb_member_deal_cover(int(bool(strict)), out.ctypes.data_as(C.POINTER(C.c_int))))
     return out
 
 

@@ -323,6 +323,13 @@ int greb_substep_launch_order(const greb_params* p, int nx, int ny, int n_member
 int greb_circulation_launch_plan(const greb_params* p, int nx, int ny, int n_members, const float* kappa, int slots,
                                  int* field, int* k0, int* k1, int* chain, int* dep4, int capacity);
 
+/* Diagnostic, host only (no GPU call): how often one circulation sub-step of the fused 96x48 member kernel computes each
+ * 4-longitude quad of each row under the kernel's static work deal (greb_member.hip), FAST (strict = 0) or STRICT:
+ * counts[48 * 24], counts[k * 24 + q].  A complete deal has 1 for rows 1 .. 46 and 0 for the polar rows 0 and 47,
+ * which have their own wave(s); the library asserts this when it is compiled, this is the same table for tests.
+ * Returns 0, < 0 on a bad argument. */
+int greb_member_deal_cover(int strict, int* counts);
+
 /* Point physics of one step for a batch of columns sets (tests): SWradiation :367-403,
  * LWradiation :407-434, hydro :438-469, deep_ocean :495-525, seaice :472-492 evaluated by the
  * same device functions the engine uses.  in  : Ts,Ta,To,q,cap_surf [5][ny][nx]

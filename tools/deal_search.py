@@ -15,6 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 VARDIR = os.path.join(ROOT, "greb_climate_model_amd", "variants")
+CANDIDATE_TIMEOUT_S = 150
 
 DEALS = {  # a leading "P<w>:" puts the polar chains on wave w (default 6); the slot list omits that wave
     "p6g":   "P6:S0+F0 S2+F1 T1+F3 T2+H+F2 S1 T0 F4",
@@ -65,20 +66,32 @@ def table(deal: str) -> str:
 
 
 def build_one(name: str) -> str:
+    """greb_member.hip alone is compiled per candidate; the other objects are the tuning library's (build.build_lib)."""
     from greb_climate_model_amd import build
     out = os.path.join(VARDIR, f"libgreb_hip_deal_{name}.so")
-    cmd = [build.hipcc(), *build.HIPCC_FLAGS, "-DGREB_TUNING", "-DGREB_DEAL_FAST=" + table(DEALS[name]),
-           f"-DGREB_POLAR_WAVE_FAST={polar_wave(DEALS[name])}", "-o", out,
-           *[os.path.join(build.CSRC, s) for s in build.SOURCES]]
-    subprocess.run(cmd, check=True, cwd=build.CSRC, stdout=subprocess.DEVNULL)
+    obj = os.path.join(VARDIR, f"greb_member_deal_{name}.o")
+    flags = [f for f in build.HIPCC_FLAGS if f != "-shared"]
+    subprocess.run([build.hipcc(), *flags, "-DGREB_TUNING", "-DGREB_DEAL_FAST=" + table(DEALS[name]),
+                    f"-DGREB_POLAR_WAVE_FAST={polar_wave(DEALS[name])}",
+                    "-c", os.path.join(build.CSRC, "greb_member.hip"), "-o", obj], check=True, cwd=build.CSRC, stdout=subprocess.DEVNULL)
+    objs = [obj if s == "greb_member.hip" else os.path.join(build.OBJ_DIR, os.path.splitext(s)[0] + "_tuning.o") for s in build.SOURCES]
+    subprocess.run([build.hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, *objs], check=True, cwd=build.CSRC)
     return out
 
 
 def main() -> None:
     mode = sys.argv[1] if len(sys.argv) > 1 else "build"
-    names = [n for n in (sys.argv[3:] if mode == "run" else sys.argv[2:]) if n in DEALS] or list(DEALS)
+    if mode not in ("build", "run"):
+        sys.exit(__doc__)
+    names = sys.argv[3:] if mode == "run" else sys.argv[2:]
+    unknown = [n for n in names if n not in DEALS]
+    if unknown:
+        sys.exit(f"unknown deal(s) {' '.join(unknown)}; known: {' '.join(DEALS)}")
+    names = names or list(DEALS)
     if mode == "build":
         os.makedirs(VARDIR, exist_ok=True)
+        from greb_climate_model_amd import build
+        build.build_lib(tuning=True)
         with ThreadPoolExecutor(4) as ex:
             for out in ex.map(build_one, names):
                 print("built", os.path.relpath(out, ROOT))
@@ -88,8 +101,13 @@ def main() -> None:
         lib = os.path.join(VARDIR, f"libgreb_hip_deal_{n}.so")
         if not os.path.exists(lib):
             continue
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "stamp_member.py"), members, "2"],
-                           env=dict(os.environ, GREB_LIB=lib), capture_output=True, text=True)
+        try:  # every candidate under its own time limit; nothing more is started on the GPU after one that failed
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "stamp_member.py"), members, "2"],
+                               env=dict(os.environ, GREB_LIB=lib), capture_output=True, text=True, timeout=CANDIDATE_TIMEOUT_S)
+        except subprocess.TimeoutExpired:
+            sys.exit(f"{n}: no result after {CANDIDATE_TIMEOUT_S} s; stopping")
+        if r.returncode != 0:
+            sys.exit(f"{n}: exit status {r.returncode}; stopping\n{r.stderr[-400:]}")
         sub = [l for l in r.stdout.splitlines() if l.startswith("sub-step")]
         busy = [l.split("busy")[1].split("cyc")[0].strip() for l in r.stdout.splitlines() if "busy" in l and "wave" in l]
         print(f"{n:6s} {DEALS[n]:48s} {sub[0] if sub else r.stderr[-200:]}  busy {' '.join(busy)}", flush=True)
