@@ -15,7 +15,7 @@
 //   Registers hold nothing across sub-steps.
 //
 // The tracer interleave makes every FAST arithmetic instruction a packed v_pk_*_f32 on an aligned
-// (Tair,q) register pair (greb_pair.h): both tracers share the winds, the sign split, the address
+// (Tair,q) register pair (greb_pair.h): both tracers share the winds, their signs, the address
 // arithmetic and the row constants.
 //
 // Work distribution per sub-step (measured on MI355X: the bulk is the critical path, bound by VALU issue on the
@@ -109,11 +109,12 @@ __device__ __forceinline__ q8 ld8p(const lfloat* p) {
 }
 
 // FAST arithmetic of one bulk row task from its loaded neighbourhood (shared by the one-row and the two-row task)
+// ws: the signs of the eight winds, lane masks kept since the start of the circulation call (make_signs)
 template <bool SUB>
 __device__ __forceinline__ q8 fast_row(const q8& LT, const q8& CT, const q8& RT, const q8& Tm2, const q8& Tm1, const q8& Tp1,
                                        const q8& Tp2, const q8& LW, const q8& CW, const q8& RW, const q8& Wm2, const q8& Wm1,
-                                       const q8& Wp1, const q8& Wp2, const f4& xq, const f4& yq, bool last_quad,
-                                       float cs_dif, float dif_ccy, bool calm_q) {
+                                       const q8& Wp1, const q8& Wp2, const f4& xq, const f4& yq, const WindSigns& ws,
+                                       bool last_quad, float cs_dif, float dif_ccy, bool calm_q) {
   v2 T[12], w[12];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -122,13 +123,8 @@ __device__ __forceinline__ q8 fast_row(const q8& LT, const q8& CT, const q8& RT,
   }
   // (the latitudinal advection term is not divided by 3 at k = 1 (v>=0 part) and k = ny-2 (v<0 part), :766-769, :784-787:
   // stage_winds folds that factor into the staged v of rows 1 and NY-2, once per model step)
-  float um[4], up[4], vm[4], vp[4]; // the sign split is shared by the two tracers
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    split_sign(xq.v[i], um[i], up[i]);
-    split_sign(yq.v[i], vm[i], vp[i]);
-  }
-  return substep_pair<SUB>(T, w, Tm2, Tm1, Tp1, Tp2, Wm2, Wm1, Wp1, Wp2, um, up, vm, vp, cs_dif, dif_ccy, last_quad, calm_q);
+  // (the signs are shared by the two tracers)
+  return substep_pair<SUB>(T, w, Tm2, Tm1, Tp1, Tp2, Wm2, Wm1, Wp1, Wp2, xq.v, ws.x, yq.v, ws.y, cs_dif, dif_ccy, last_quad, calm_q);
 }
 
 __device__ __forceinline__ void st8p(lfloat* o, const q8& xn) {
@@ -191,12 +187,12 @@ __device__ __forceinline__ q8 strict_row(const q8& LT, const q8& CT, const q8& R
 template <bool STRICT, bool SUB>
 __device__ __forceinline__ q8 one_row(const q8& LT, const q8& CT, const q8& RT, const q8& Tm2, const q8& Tm1, const q8& Tp1,
                                       const q8& Tp2, const q8& LW, const q8& CW, const q8& RW, const q8& Wm2, const q8& Wm1,
-                                      const q8& Wp1, const q8& Wp2, const f4& xq, const f4& yq, int k, int q, const RowK& rk,
-                                      bool calm_q) {
+                                      const q8& Wp1, const q8& Wp2, const f4& xq, const f4& yq, const WindSigns& ws, int k, int q,
+                                      const RowK& rk, bool calm_q) {
   if (STRICT) return strict_row(LT, CT, RT, Tm2, Tm1, Tp1, Tp2, LW, CW, RW, Wm2, Wm1, Wp1, Wp2, xq, yq, k, q, rk, calm_q);
   // FAST: rk.dif_cc holds the row's dif_cc/20 as Circ::init staged it (task_consts)
-  return fast_row<SUB>(LT, CT, RT, Tm2, Tm1, Tp1, Tp2, LW, CW, RW, Wm2, Wm1, Wp1, Wp2, xq, yq, q == NQ - 1, rk.dif_cc, rk.dif_ccy,
-                       calm_q);
+  return fast_row<SUB>(LT, CT, RT, Tm2, Tm1, Tp1, Tp2, LW, CW, RW, Wm2, Wm1, Wp1, Wp2, xq, yq, ws, q == NQ - 1, rk.dif_cc,
+                       rk.dif_ccy, calm_q);
 }
 
 // the row constants a task needs: everything in STRICT; in FAST ONE word, the row's dif_cc/20 as Circ::init staged it
@@ -215,7 +211,8 @@ __device__ __forceinline__ RowK task_consts(const lfloat* lds, int k, float ccy_
 // rows make k-2 = -1 and k+2 = NY valid reads: zero weights in FAST, not referenced by the reference's boundary
 // formulas in STRICT), the row's left and right quads from the two precomputed offsets.
 template <bool STRICT, bool SUB>
-__device__ __forceinline__ void row_task(lfloat* lds, int cur, const TaskAddr& ta, float ccy_dif, bool calm_q = false) {
+__device__ __forceinline__ void row_task(lfloat* lds, int cur, const TaskAddr& ta, const WindSigns* ws, float ccy_dif,
+                                         bool calm_q = false) {
   const int k = ta.kq & 255, q = ta.kq >> 8;
   const lfloat* Xc = lds + kOffX + cur * XB;
   const lfloat* Wc = lds + kOffW;
@@ -226,7 +223,8 @@ __device__ __forceinline__ void row_task(lfloat* lds, int cur, const TaskAddr& t
   const q8 Tm2 = ld8p(xb), Tm1 = ld8p(xb + RS), CT = ld8p(xb + 2 * RS), Tp1 = ld8p(xb + 3 * RS), Tp2 = ld8p(xb + 4 * RS);
   const q8 Wm2 = ld8p(wb), Wm1 = ld8p(wb + RS), CW = ld8p(wb + 2 * RS), Wp1 = ld8p(wb + 3 * RS), Wp2 = ld8p(wb + 4 * RS);
   const q8 LT = ld8p(Xc + ta.l), RT = ld8p(Xc + ta.r), LW = ld8p(Wc + ta.l), RW = ld8p(Wc + ta.r);
-  const q8 xn = one_row<STRICT, SUB>(LT, CT, RT, Tm2, Tm1, Tp1, Tp2, LW, CW, RW, Wm2, Wm1, Wp1, Wp2, xq, yq, k, q, rk, calm_q);
+  const q8 xn = one_row<STRICT, SUB>(LT, CT, RT, Tm2, Tm1, Tp1, Tp2, LW, CW, RW, Wm2, Wm1, Wp1, Wp2, xq, yq, ws[0], k, q, rk,
+                                     calm_q);
   st8p(lds + kOffX + (cur ^ 1) * XB + ta.c, xn); // own quad of the other buffer: same offset
 }
 
@@ -234,7 +232,8 @@ __device__ __forceinline__ void row_task(lfloat* lds, int cur, const TaskAddr& t
 // column are loaded once and shared -- 44 instead of 62 ds_read_b128 for the two rows.  The sub-step loop is
 // co-limited by LDS bandwidth: dropping 39 % of the bulk reads (timing experiment) made it 12 % faster.
 template <bool STRICT, bool SUB>
-__device__ __forceinline__ void row_task2(lfloat* lds, int cur, const TaskAddr& ta, float ccy_dif, bool calm_q = false) {
+__device__ __forceinline__ void row_task2(lfloat* lds, int cur, const TaskAddr& ta, const WindSigns* ws, float ccy_dif,
+                                          bool calm_q = false) {
   const int k = ta.kq & 255, q = ta.kq >> 8;
   const lfloat* Xc = lds + kOffX + cur * XB;
   const lfloat* Wc = lds + kOffW;
@@ -247,7 +246,7 @@ __device__ __forceinline__ void row_task2(lfloat* lds, int cur, const TaskAddr& 
     const q8 LT = ld8p(Xc + ta.l), RT = ld8p(Xc + ta.r), LW = ld8p(Wc + ta.l), RW = ld8p(Wc + ta.r);
     const f4 xq = ld4(lds + kOffWX + k * NX + 4 * q), yq = ld4(lds + kOffWY + k * NX + 4 * q);
     const RowK rk = task_consts<STRICT>(lds, k, ccy_dif);
-    st8p(out, one_row<STRICT, SUB>(LT, T2, RT, T0, T1, T3, T4, LW, W2, RW, W0, W1, W3, W4, xq, yq, k, q, rk, calm_q));
+    st8p(out, one_row<STRICT, SUB>(LT, T2, RT, T0, T1, T3, T4, LW, W2, RW, W0, W1, W3, W4, xq, yq, ws[0], k, q, rk, calm_q));
   }
   __builtin_amdgcn_sched_barrier(0); // row k+1 after row k: keeps the two rows' temporaries from piling up
   {
@@ -255,11 +254,14 @@ __device__ __forceinline__ void row_task2(lfloat* lds, int cur, const TaskAddr& 
     const q8 LT = ld8p(Xc + ta.l + RS), RT = ld8p(Xc + ta.r + RS), LW = ld8p(Wc + ta.l + RS), RW = ld8p(Wc + ta.r + RS);
     const f4 xq = ld4(lds + kOffWX + (k + 1) * NX + 4 * q), yq = ld4(lds + kOffWY + (k + 1) * NX + 4 * q);
     const RowK rk = task_consts<STRICT>(lds, k + 1, ccy_dif);
-    st8p(out + RS, one_row<STRICT, SUB>(LT, T3, RT, T1, T2, T4, T5, LW, W3, RW, W1, W2, W4, W5, xq, yq, k + 1, q, rk, calm_q));
+    st8p(out + RS,
+         one_row<STRICT, SUB>(LT, T3, RT, T1, T2, T4, T5, LW, W3, RW, W1, W2, W4, W5, xq, yq, ws[1], k + 1, q, rk, calm_q));
   }
 }
 
 struct BulkTasks { TaskAddr t[3]; };
+// FAST: the wind signs of a lane's tasks, [pass][row of the task], as lane masks in scalar registers (greb_pair.h: wind_term)
+struct BulkSigns { WindSigns s[3][2]; };
 
 // The schedule (both arithmetic modes).  Task kinds: one row (S1 sub-cycled family, F1 full family) or two stacked rows (ST, FT).
 //   ST  rows (1,2) (3,4) (5,6) (7,8) (39,40) .. (45,46) : 8 pairs x 24 quads = 3 full passes
@@ -285,7 +287,7 @@ struct Pass { int kind, index; };
 // both finish together.  Measured sub-step times (tools/deal_search.py: in-kernel stamps, 512 members, one gpurun call
 // per group; slots w0 w1 w2 w3 | w4 w5 w6 w7, C = the chains, S = ST, T = FT, H = S1, F = F1):
 //   chains on wave 6 (younger wave of SIMD 2)
-//     S0+F0 S2+F1 T1+F3 T2+H+F2 | S1    T0    C     F4      4 773   <- the table below
+//     S0+F0 S2+F1 T1+F3 T2+H+F2 | S1    T0    C     F4      4 773   <- the table until the wind signs became masks
 //     S0+F0 S1+H  T1+F3 T2+F1+F2| S2    T0    C     F4      4 814
 //     S0+F0 S2+H  T1+F3 T2+F1+F2| S1    T0    C     F4      4 817
 //     S0+F0 S2+H  T1+F3 T2+F1   | S1    T0    C     F2+F4   4 886
@@ -305,6 +307,14 @@ struct Pass { int kind, index; };
 // belong to a whole row pair -- took 4 654 at best (S0+F0 S2+F1 T1+F2 T2+H | S1 T0 C T3), 4 658 and 4 850 in two other
 // deals; X = 5 (+ half a single pass) 5 060 .. 5 641 in four deals: a fifth pair pass finds no SIMD it balances on.  30
 // cycles did not pay for a second task enumeration; the split stays 3 + 4.5.
+// With the wind signs kept as lane masks (greb_pair.h: wind_term; profiles/r06_member_wind_masks_stamps.txt) every bulk wave
+// but wave 3 got shorter under the table above -- its T2+H+F2 stayed at 4 387 busy cycles, sub-step 4 664 where the split
+// form took 4 685 -- and the F1 pass F2 moved from wave 3 to wave 7:
+//     S0+F0 S2+F1 T1+F3 T2+H    | S1    T0    C     F2+F4   4 579   <- the table below (busy 3 535 3 641 3 127 3 364 | 4 243 4 184 4 154 4 057)
+//     S0+F0 S2+F1 T1+F3 T2+F2   | S1    T0    C     H+F4    4 582
+//     S0+F0 S2+F1 T1+F3 T2+H+F2 | S1    T0    C     F4      4 664
+//     S0    S2+F1 T1+F3 T2+H+F2 | S1    T0    C     F0+F4   4 889
+//     S0+F0 S2+F1 T1+F3+F2 T2+H | S1    T0    C     F4      5 089
 __host__ __device__ constexpr Pass deal_fast(int wave, int i) {
   constexpr Pass none{kNone, 0};
 #if defined(GREB_TUNING) && defined(GREB_DEAL_FAST) // tools/deal_search.py: a deal given on the compiler command line
@@ -312,9 +322,9 @@ __host__ __device__ constexpr Pass deal_fast(int wave, int i) {
 #else
   constexpr Pass t[8][3] = {
       /* w0 */ {{kST, 0}, {kF1, 0}, none},     /* w1 */ {{kST, 2}, {kF1, 1}, none},
-      /* w2 */ {{kFT, 1}, {kF1, 3}, none},     /* w3 */ {{kFT, 2}, {kS1, 0}, {kF1, 2}},
+      /* w2 */ {{kFT, 1}, {kF1, 3}, none},     /* w3 */ {{kFT, 2}, {kS1, 0}, none},
       /* w4 */ {{kST, 1}, none, none},         /* w5 */ {{kFT, 0}, none, none},
-      /* w6 */ {none, none, none},             /* w7 */ {{kF1, 4}, none, none}};
+      /* w6 */ {none, none, none},             /* w7 */ {{kF1, 2}, {kF1, 4}, none}};
 #endif
   return t[wave][i];
 }
@@ -431,26 +441,52 @@ __device__ __forceinline__ BulkTasks make_tasks(int wave, int lane) {
   return b;
 }
 
+// Once per circulation call -- that is once per model step in every kernel, beside make_tasks at the top of role_loop, after
+// stage_winds and the barrier behind it; nothing of this lives across a step: every lane of the wave compares the staged winds of its
+// task rows with zero and the wave keeps the outcome as 64-bit lane masks, 16 scalar registers per task row.  The winds do
+// not change until the next stage_winds, and a lane's tasks are fixed.  Lanes without a task in a partial pass read row 1,
+// quad 0.
+template <int WAVE>
+__device__ __forceinline__ void make_signs(const lfloat* lds, const BulkTasks& tasks, BulkSigns& b) {
+  static_for<3>([&](auto I) {
+    constexpr int i = I, rows = task_rows(deal_fast(WAVE, i).kind);
+    if constexpr (rows > 0) {
+      const int kq = tasks.t[i].kq < 0 ? 1 : tasks.t[i].kq, k = kq & 255, q = kq >> 8;
+#pragma unroll
+      for (int j = 0; j < rows; ++j) {
+        const f4 xq = ld4(lds + kOffWX + (k + j) * NX + 4 * q), yq = ld4(lds + kOffWY + (k + j) * NX + 4 * q);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          unsigned long long mx = __builtin_amdgcn_ballot_w64(xq.v[e] > 0.f), my = __builtin_amdgcn_ballot_w64(yq.v[e] > 0.f);
+          asm volatile("" : "+s"(mx), "+s"(my)); // opaque: kept, not re-derived from the winds inside the sub-step loop
+          b.s[i][j].x[e] = mx; b.s[i][j].y[e] = my;
+        }
+      }
+    }
+  });
+}
+
 // task i of bulk wave SLOT: kind and pass are compile-time, so a wave's sub-step is straight-line code -- no
 // per-sub-step dispatch on the wave number (that dispatch, a switch on a VGPR lowered to exec-mask bookkeeping, cost
 // every bulk wave ~100 issue slots per sub-step)
 template <bool STRICT, int SLOT, int I>
-__device__ __forceinline__ void bulk_task(lfloat* lds, int cur, const BulkTasks& tasks, float ccy_dif, int dbg, bool calm_q) {
+__device__ __forceinline__ void bulk_task(lfloat* lds, int cur, const BulkTasks& tasks, const BulkSigns& signs, float ccy_dif,
+                                          int dbg, bool calm_q) {
   constexpr int kind = deal<STRICT>(SLOT, I).kind, ntask = pass_tasks(kind, deal<STRICT>(SLOT, I).index);
   if constexpr (kind != kNone && ntask > 0) {
     if (ntask < 64 && tasks.t[I].kq < 0) return; // partial pass: lanes without a task
-    if constexpr (kind == kS1) { if (!(dbg & 1)) row_task<STRICT, true>(lds, cur, tasks.t[I], ccy_dif, calm_q); }
-    else if constexpr (kind == kF1) { if (!(dbg & 2)) row_task<STRICT, false>(lds, cur, tasks.t[I], ccy_dif, calm_q); }
-    else if constexpr (kind == kST) { if (!(dbg & 1)) row_task2<STRICT, true>(lds, cur, tasks.t[I], ccy_dif, calm_q); }
-    else { if (!(dbg & 2)) row_task2<STRICT, false>(lds, cur, tasks.t[I], ccy_dif, calm_q); }
+    if constexpr (kind == kS1) { if (!(dbg & 1)) row_task<STRICT, true>(lds, cur, tasks.t[I], signs.s[I], ccy_dif, calm_q); }
+    else if constexpr (kind == kF1) { if (!(dbg & 2)) row_task<STRICT, false>(lds, cur, tasks.t[I], signs.s[I], ccy_dif, calm_q); }
+    else if constexpr (kind == kST) { if (!(dbg & 1)) row_task2<STRICT, true>(lds, cur, tasks.t[I], signs.s[I], ccy_dif, calm_q); }
+    else { if (!(dbg & 2)) row_task2<STRICT, false>(lds, cur, tasks.t[I], signs.s[I], ccy_dif, calm_q); }
   }
 }
 template <bool STRICT, int SLOT>
-__device__ __forceinline__ void bulk_substep(lfloat* lds, int cur, const BulkTasks& tasks, float ccy_dif, int dbg,
-                                             bool calm_q = false) {
-  bulk_task<STRICT, SLOT, 0>(lds, cur, tasks, ccy_dif, dbg, calm_q);
-  bulk_task<STRICT, SLOT, 1>(lds, cur, tasks, ccy_dif, dbg, calm_q);
-  bulk_task<STRICT, SLOT, 2>(lds, cur, tasks, ccy_dif, dbg, calm_q);
+__device__ __forceinline__ void bulk_substep(lfloat* lds, int cur, const BulkTasks& tasks, const BulkSigns& signs, float ccy_dif,
+                                             int dbg, bool calm_q = false) {
+  bulk_task<STRICT, SLOT, 0>(lds, cur, tasks, signs, ccy_dif, dbg, calm_q);
+  bulk_task<STRICT, SLOT, 1>(lds, cur, tasks, signs, ccy_dif, dbg, calm_q);
+  bulk_task<STRICT, SLOT, 2>(lds, cur, tasks, signs, ccy_dif, dbg, calm_q);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -668,7 +704,7 @@ __device__ __forceinline__ void quad_chain_substep(lfloat* lds, int cur, QuadCha
 }
 
 // stage this step's winds (src/greb.f90:203-216, 732): raw for STRICT and for the polar rows,
-// otherwise scaled by the row's advection constants so the sign split is one max/min per use:
+// otherwise scaled by the row's advection constants, so that a row task multiplies by the staged wind alone:
 //   x = c*u, c = ccx/3 (full rows) or ccx2/20 (sub-cycled rows);  y = ccy/3 * v (rows 1 and NY-2: see below)
 // REMAT (the switch-aware FAST kernels, whose sub-step loop exists twice): the thread's addresses are derived anew every
 // model step -- a few instructions -- instead of living in registers across the sub-steps, where that kernel has none left.
@@ -702,7 +738,8 @@ __device__ __forceinline__ void stage_winds(lfloat* lds, const float* __restrict
         // (:766-769, :784-787).  The factor 3 goes onto that part of the staged wind here, once per model step, instead
         // of onto the split halves in every sub-cycled row task: with y' = 3y where y has the part's sign and y' = y
         // elsewhere, max(y',0) and y' - max(y',0) are the bits of 3 max(y,0) and y - max(y,0) (row 1), or of max(y,0)
-        // and 3 (y - max(y,0)) (row NY-2); the product still feeds a multiply, so no contraction changes either.
+        // and 3 (y - max(y,0)) (row NY-2); the product still feeds a multiply, so no contraction changes either.  (The
+        // row tasks no longer form the two parts: wind_term selects by the sign of y', which is the sign of y.)
         if (k == 1 || k == NY - 2) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -753,9 +790,11 @@ struct Circ {
     // point-physics phase, where the register pressure peaks, come back as scratch reloads inside this loop)
     constexpr bool kPolar = is_polar_wave<STRICT>(WAVE);
     BulkTasks tasks;
+    BulkSigns signs;
     QuadChain quad;
     if constexpr (!kPolar) tasks = make_tasks<STRICT>(WAVE, lane);
     else if constexpr (!STRICT) quad_chain_setup(lds, cur, lane, calm_q, quad);
+    if constexpr (!kPolar && !STRICT) make_signs<WAVE>(lds, tasks, signs);
     // FAST bulk waves: dif_ccy, the one row constant that is the same in every row, as a scalar for the whole call
     float ccy_dif = 0.f;
     if constexpr (!kPolar && !STRICT) ccy_dif = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(lds[kOffRowK + 2])));
@@ -766,7 +805,7 @@ struct Circ {
 #endif
       if constexpr (kPolar && STRICT) { if (!(dbg & 4)) chain_substep_strict(lds, cur, WAVE - 2, lane, calm_q); }
       else if constexpr (kPolar) { if (!(dbg & 4)) quad_chain_substep(lds, cur, quad); }
-      else bulk_substep<STRICT, WAVE>(lds, cur, tasks, ccy_dif, dbg, calm_q);
+      else bulk_substep<STRICT, WAVE>(lds, cur, tasks, signs, ccy_dif, dbg, calm_q);
 #ifdef GREB_TUNING
       if (stamp) busy += __builtin_amdgcn_s_memtime() - t0;
 #endif

@@ -5,7 +5,7 @@
 // delivers two longitudes of both tracers and every arithmetic operation is a packed
 // v_pk_{add,mul,fma}_f32 on an even-aligned register pair: no shuffles to form the packed operands
 // (the scalar formulation spent ~22 % of its VALU issue slots on v_mov / v_pk_mov), and the wind
-// sign split, the address arithmetic and the row constants are shared by the two tracers.
+// signs, the address arithmetic and the row constants are shared by the two tracers.
 // Same formulas as greb_device.h's FAST pieces (edge-flux form, pre-scaled winds).
 #pragma once
 #include "greb_device.h"
@@ -50,12 +50,32 @@ __device__ __forceinline__ v2 pk_sub(v2 a, v2 b) {
   asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
-// max(u,0) / min(u,0) of a finite wind: v_med3_f32 needs no canonicalising v_max(x,x) in front (fmaxf does),
-// and min(u,0) = u - max(u,0) exactly
-__device__ __forceinline__ void split_sign(float u, float& pos, float& neg) {
-  pos = __builtin_amdgcn_fmed3f(u, 0.f, 3.0e38f); // (an infinite bound is folded back into v_max)
-  neg = u - pos;
+// The sign split of a staged wind, without the split.  The reference multiplies max(u,0) by one stencil sum and
+// min(u,0) by another (src/greb.f90:203-208); of the two products one is an exact zero, so `min(u,0)*A - max(u,0)*B`
+// has the bits of the ROUNDED product u*A (u <= 0) or -(u*B) (u > 0) -- up to the sign of a zero result, which every
+// use below adds to the (non-zero) tracer or to a sum that is.  So: select the operand by the wind's sign, one packed
+// multiply.  `pos` is the wave's lane mask of u > 0 in a scalar register pair: either kept from the circulation call's
+// start (WindSigns: the winds do not change between two stage_winds) or one v_cmp in the task.  The select is written
+// as the instruction: the negation is its source modifier (left to the compiler, -B is a packed instruction of its own).
+// Contraction is off: the product is rounded before the sums it goes into, as the split form's was.
+template <bool NEG_A>
+__device__ __forceinline__ float wind_operand(float a, float b, unsigned long long pos) { // pos ? -b : (NEG_A ? -a : a)
+  float r;
+  if (NEG_A) asm("v_cndmask_b32_e64 %0, -%1, -%2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(pos));
+  else asm("v_cndmask_b32_e64 %0, %1, -%2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(pos));
+  return r;
 }
+// min(u,0)*A - max(u,0)*B, or with NEG_A -min(u,0)*A - max(u,0)*B
+template <bool NEG_A = false>
+__device__ __forceinline__ v2 wind_term(float u, unsigned long long pos, v2 A, v2 B) {
+#pragma clang fp contract(off)
+  const v2 op{wind_operand<NEG_A>(A.x, B.x, pos), wind_operand<NEG_A>(A.y, B.y, pos)};
+  return u * op;
+}
+// bit l of x[i] / y[i]: lane l's i-th zonal / meridional staged wind of a task row is > 0
+struct WindSigns {
+  unsigned long long x[4], y[4];
+};
 
 struct Flux2 {
   v2 Pp[10]; // Pp[m] = w[m+1]*(T[m+1]-T[m]), m = 4..9
@@ -81,20 +101,20 @@ __device__ __forceinline__ void dif_lon2(const Flux2& f, float cs, v2 d[4]) {
   }
 }
 
-// um = (ccx/3)*max(u,0), up = (ccx/3)*min(u,0)  (src/greb.f90:802-806)
-__device__ __forceinline__ void adv_lon_full2(const Flux2& f, const v2 T[12], const v2 w[12], const float um[4],
-                                              const float up[4], v2 d[4]) {
+// u = (ccx/3)*u_wind, pos = lanes of u > 0: up*(...) - um*(...) of um = max(u,0), up = min(u,0)  (src/greb.f90:802-806)
+__device__ __forceinline__ void adv_lon_full2(const Flux2& f, const v2 T[12], const v2 w[12], const float u[4],
+                                              const unsigned long long pos[4], v2 d[4]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int c = 4 + i;
     const v2 em2 = w[c - 2] * (T[c] - T[c - 2]), ep2 = w[c + 2] * (T[c] - T[c + 2]);
-    d[i] = up[i] * (ep2 - f.Pp[c]) - um[i] * (f.Pm[c - 1] + em2);
+    d[i] = wind_term(u[i], pos[i], ep2 - f.Pp[c], f.Pm[c - 1] + em2);
   }
 }
 
-// um = (ccx2/20)*max(u,0), ...  (src/greb.f90:845-851, index bug :881 for the last quad's 2nd point)
-__device__ __forceinline__ void adv_lon_sub2(const Flux2& f, const v2 T[12], const v2 w[12], const float um[4],
-                                             const float up[4], bool last_quad, v2 d[4]) {
+// u = (ccx2/20)*u_wind: -up*ap - um*am  (src/greb.f90:845-851, index bug :881 for the last quad's 2nd point)
+__device__ __forceinline__ void adv_lon_sub2(const Flux2& f, const v2 T[12], const v2 w[12], const float u[4],
+                                             const unsigned long long pos[4], bool last_quad, v2 d[4]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int c = 4 + i;
@@ -104,7 +124,7 @@ __device__ __forceinline__ void adv_lon_sub2(const Flux2& f, const v2 T[12], con
       const v2 bug = 10.f * f.Pp[c] - w[c + 3] * (T[c + 1] - T[c + 3]);
       ap = last_quad ? bug : ap;
     }
-    d[i] = -up[i] * ap - um[i] * am;
+    d[i] = wind_term<true>(u[i], pos[i], ap, am);
   }
 }
 
@@ -120,17 +140,17 @@ __device__ __forceinline__ void clamp_add2(v2 T1h[4], v2 d[4]) {
   }
 }
 
-// latitudinal diffusion + advection; vm = am*max(v,0), vp = ap*min(v,0); missing rows have w = 0
+// latitudinal diffusion + advection; v = the staged wind (vp*(...) - vm*(...) of its split), pos = lanes of v > 0; missing rows have w = 0
 __device__ __forceinline__ void lat2(const v2 T0[4], const v2 Tm2[4], const v2 Tm1[4], const v2 Tp1[4],
                                      const v2 Tp2[4], const v2 wm2[4], const v2 wm1[4], const v2 wp1[4],
-                                     const v2 wp2[4], const float vm[4], const float vp[4], float ccy_dif,
+                                     const v2 wp2[4], const float v[4], const unsigned long long pos[4], float ccy_dif,
                                      v2 ddif[4], v2 dadv[4]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const v2 gm1 = wm1[i] * pk_sub(Tm1[i], T0[i]), gp1 = wp1[i] * pk_sub(Tp1[i], T0[i]);
     const v2 dm2 = wm2[i] * pk_sub(T0[i], Tm2[i]), dp2 = wp2[i] * pk_sub(T0[i], Tp2[i]);
     ddif[i] = ccy_dif * (gm1 + gp1);
-    dadv[i] = vp[i] * (dp2 - gp1) - vm[i] * (dm2 - gm1);
+    dadv[i] = wind_term(v[i], pos[i], dp2 - gp1, dm2 - gm1);
   }
 }
 
@@ -139,15 +159,15 @@ __device__ __forceinline__ void lat2(const v2 T0[4], const v2 Tm2[4], const v2 T
 template <bool SUB>
 __device__ __forceinline__ q8 substep_pair(const v2 T[12], const v2 w[12], const q8& Tm2, const q8& Tm1,
                                            const q8& Tp1, const q8& Tp2, const q8& wm2, const q8& wm1,
-                                           const q8& wp1, const q8& wp2, const float um[4], const float up[4],
-                                           const float vm[4], const float vp[4], float cs_dif, float ccy_dif,
+                                           const q8& wp1, const q8& wp2, const float u[4], const unsigned long long upos[4],
+                                           const float v[4], const unsigned long long vpos[4], float cs_dif, float ccy_dif,
                                            bool last_quad, bool calm_q = false) {
   Flux2 f;
   make_flux2(T, w, f);
   v2 ddx[4], dax[4], ddy[4], day[4];
   dif_lon2(f, cs_dif, ddx);
   if (SUB) {
-    adv_lon_sub2(f, T, w, um, up, last_quad, dax);
+    adv_lon_sub2(f, T, w, u, upos, last_quad, dax);
     // The sub-cycle clamp `where(dTxh <= -T1h) dTxh = -0.9*T1h` (:715, :907) fires only where an increment would take
     // the tracer to zero or below.  d <= -T implies fl(T + d) <= 0 (rounding is monotonic), so one min over the 16
     // updated values (v_min3 chain) decides conservatively whether any lane component needs the reference's
@@ -168,9 +188,9 @@ __device__ __forceinline__ q8 substep_pair(const v2 T[12], const v2 w[12], const
 #pragma unroll
     for (int i = 0; i < 4; ++i) { ddx[i] = T1h[i] - T[4 + i]; dax[i] = T2h[i] - T[4 + i]; } // :718, :910
   } else {
-    adv_lon_full2(f, T, w, um, up, dax);
+    adv_lon_full2(f, T, w, u, upos, dax);
   }
-  lat2(&T[4], Tm2.v, Tm1.v, Tp1.v, Tp2.v, wm2.v, wm1.v, wp1.v, wp2.v, vm, vp, ccy_dif, ddy, day);
+  lat2(&T[4], Tm2.v, Tm1.v, Tp1.v, Tp2.v, wm2.v, wm1.v, wp1.v, wp2.v, v, vpos, ccy_dif, ddy, day);
   q8 r;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
