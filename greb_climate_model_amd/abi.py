@@ -58,6 +58,14 @@ class GrebMemberConfig(C.Structure):
     _fields_ = [("p", GrebParams), ("switches", C.c_uint32)]
 
 
+MAX_FORCING_TABLES = 16  # GREB_MAX_FORCING_TABLES: CO2 patterns, and insolation tables, of one engine
+
+
+class GrebMemberForcing(C.Structure):
+    """struct greb_member_forcing: a member's CO2 pattern (-1: none) and reference, insolation table (-1: the engine's) and scale."""
+    _fields_ = [("co2_pattern", C.c_int32), ("co2_ref", C.c_float), ("solar_table", C.c_int32), ("solar_scale", C.c_float)]
+
+
 # what a member may NOT change (it feeds data every member shares): greb_engine_create_members rejects a difference
 MEMBER_SHARED = ("pi", "z_air", "z_vapor", "dt", "dt_crcl", "ipx", "ipy", "year0")
 

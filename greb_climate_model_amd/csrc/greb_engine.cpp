@@ -148,6 +148,12 @@ struct greb_engine {
   float* bsum = nullptr;                               // run_budget: [nm][GREB_NBUDGET][np] running sums, made on the first budget run
   float* budget_dev = nullptr; size_t budget_cap = 0;  // run_budget: two one-year staging slots of budget records
   long long budget_runs = 0;                           // run_budget calls so far (describe)
+  // per-member forcing (set_forcing_tables, set_member_forcing): scenario phase only
+  int n_patterns = 0, n_solar = 0;
+  float *f_space = nullptr, *f_season = nullptr, *f_solar = nullptr; // [n_patterns][np], [n_patterns][730], [n_solar][730][ny]
+  std::vector<greb_member_forcing> h_force;            // [nm], or empty: no member forcing set
+  MemberForcing* force_dev = nullptr;                  // [nm], current whenever forced_members > 0
+  int forced_members = 0;                              // members that name a pattern or a table or scale the insolation
   float* yearly_dev = nullptr; size_t yearly_cap = 0;
   float* diag_out = nullptr; size_t diag_out_cap = 0; // run_diag: zonal means and annual maps of two years (one per staging slot)
   float* diag_reg = nullptr; size_t diag_reg_cap = 0; // run_diag: the region series of the whole call
@@ -206,6 +212,15 @@ MemberArgs base_args(greb_engine* e) {
   if (all) a.nsub = 0;
   return a;
 }
+
+// scenario launches only: with a forced member the launch carries the forcing and takes the forcing-aware kernels
+void apply_forcing(const greb_engine* e, MemberArgs& a) {
+  if (e->forced_members <= 0) return;
+  a.force_m = e->force_dev;
+  a.f_space = e->f_space; a.f_season = e->f_season; a.f_solar = e->f_solar;
+}
+
+bool is_forced(const greb_member_forcing& f) { return f.co2_pattern >= 0 || f.solar_table >= 0 || !(f.solar_scale == 1.f); }
 
 // vapour diffused but not advected (GREB_X_VAPOR_DIFFUSION_ONLY): on the any-grid engine a property of the launch, so
 // every member has it or none (checked where switches are set)
@@ -631,6 +646,7 @@ int run_scenario(greb_engine* e, int years, const float* co2_ppm, float* monthly
     a.monthly = mon; a.monthly_years = mon_years; a.year_out0 = mon_y;
     a.yearly = e->yearly_dev; a.yearly_years = years; a.yearly_year0 = y;
     if (budget) { a.bsum = e->bsum; a.brec = bud; a.brec_years = bud_years; a.brec_year0 = bud_y; }
+    apply_forcing(e, a);
     return a;
   };
   if (dev_out) {
@@ -730,7 +746,8 @@ int greb_engine_destroy(greb_engine* e) {
   void* ptrs[] = {e->z_topo, e->glacier, e->sw_solar, e->tclim, e->qclim, e->uclim, e->vclim, e->mldclim,
                   e->cldclim, e->swetclim, e->toclim, e->z_ocean, e->wz_air, e->wz_vapor, e->state, e->acc,
                   e->corr, e->corr_index, e->tab_index, e->tabs, e->phys, e->co2_dev, e->monthly_dev, e->yearly_dev,
-                  e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev, e->diag_out, e->diag_reg, e->bsum, e->budget_dev};
+                  e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev, e->diag_out, e->diag_reg, e->bsum, e->budget_dev,
+                  e->f_space, e->f_season, e->f_solar, e->force_dev};
   for (void* q : ptrs) if (q) (void)hipFree(q);
   for (auto& kv : e->plans) free_plan(kv.second);
   if (e->call != greb_engine::kCallNever) ledger_release(e);
@@ -1007,6 +1024,7 @@ int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_d
       a.co2 = e->co2_dev; a.co2_stride = years; a.co2_year0 = y;
       a.monthly = e->monthly_dev + (size_t)sl * slot; a.monthly_years = 1; a.year_out0 = 0;
       a.yearly = e->yearly_dev; a.yearly_years = years; a.yearly_year0 = y;
+      apply_forcing(e, a);
       if (int rc = run_year(e, a, e->nm)) return rc;
       if (y >= 2) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_free[sl], 0)); // the slot's products of year y - 2 have left
       float* out = out_slot ? e->diag_out + (size_t)sl * out_slot : nullptr;
@@ -1044,6 +1062,9 @@ const char* greb_engine_describe(greb_engine* e) {
                 e->xsw_uniform ? "uniform" : "per member", e->shared_corr ? 1 : e->nm, e->n_phys_sets);
   s += buf;
   std::snprintf(buf, sizeof(buf), ", \"budget_runs\": %lld", e->budget_runs);
+  s += buf;
+  std::snprintf(buf, sizeof(buf), ", \"forcing\": {\"patterns\": %d, \"solar_tables\": %d, \"forced_members\": %d}", e->n_patterns,
+                e->n_solar, e->forced_members);
   s += buf;
   if (e->call != greb_engine::kCallNever) {
     std::snprintf(buf, sizeof(buf), ", \"wavefront_slots_granted\": %d, \"circulation\": [", e->slots_granted);
@@ -1153,6 +1174,132 @@ int greb_engine_set_member_experiments(greb_engine* e, const uint32_t* switches)
   e->h_xsw = sw;
   e->xsw_uniform = uniform;
   e->xsw = uniform ? sw[0] : 0u;
+  return 0;
+}
+
+static_assert(sizeof(greb_member_forcing) == sizeof(MemberForcing) && sizeof(MemberForcing) == 16,
+              "the kernels read greb_member_forcing as it is");
+
+int greb_engine_set_forcing_tables(greb_engine* e, int n_patterns, const float* co2_space, const float* co2_season, int n_solar,
+                                   const float* sw_solar) {
+  const char* who = "set_forcing_tables: ";
+  if (!e) return fail(nullptr, GREB_E_INVALID, std::string(who) + "no engine (greb_engine is NULL)");
+  if (n_patterns < 0 || n_patterns > GREB_MAX_FORCING_TABLES)
+    return fail(e, GREB_E_INVALID, who + ("n_patterns = " + std::to_string(n_patterns)) + " (0 ... " + std::to_string(GREB_MAX_FORCING_TABLES) + ")");
+  if (n_solar < 0 || n_solar > GREB_MAX_FORCING_TABLES)
+    return fail(e, GREB_E_INVALID, who + ("n_solar = " + std::to_string(n_solar)) + " (0 ... " + std::to_string(GREB_MAX_FORCING_TABLES) + ")");
+  if (n_patterns > 0 && !co2_space) return fail(e, GREB_E_INVALID, std::string(who) + "co2_space is NULL with n_patterns > 0");
+  if (n_solar > 0 && !sw_solar) return fail(e, GREB_E_INVALID, std::string(who) + "sw_solar is NULL with n_solar > 0");
+  const size_t np = (size_t)e->np, nx = (size_t)e->nx, ny = (size_t)e->ny;
+  char buf[200];
+  for (int k = 0; k < n_patterns; ++k) {
+    for (size_t i = 0; i < np; ++i) {
+      const float v = co2_space[(size_t)k * np + i];
+      if (!(v >= 0.f && v <= 1.f)) { // (a NaN fails both comparisons)
+        std::snprintf(buf, sizeof(buf), "%sco2_space: pattern %d: weight %g at row %zu, column %zu is not in [0, 1]", who, k, (double)v,
+                      i / nx, i % nx);
+        return fail(e, GREB_E_INVALID, buf);
+      }
+    }
+    for (int t = 0; co2_season && t < kNT; ++t) {
+      const float v = co2_season[(size_t)k * kNT + t];
+      if (!(v >= 0.f && v <= 1.f)) {
+        std::snprintf(buf, sizeof(buf), "%sco2_season: pattern %d: weight %g at step %d is not in [0, 1]", who, k, (double)v, t + 1);
+        return fail(e, GREB_E_INVALID, buf);
+      }
+    }
+  }
+  for (int t = 0; t < n_solar; ++t)
+    for (size_t i = 0; i < (size_t)kNT * ny; ++i) {
+      const float v = sw_solar[(size_t)t * kNT * ny + i];
+      if (!(v >= 0.f && std::isfinite(v))) {
+        std::snprintf(buf, sizeof(buf), "%ssw_solar: table %d: value %g at step %zu, row %zu is negative or not finite", who, t, (double)v,
+                      i / ny + 1, i % ny);
+        return fail(e, GREB_E_INVALID, buf);
+      }
+    }
+  for (size_t m = 0; m < e->h_force.size(); ++m) { // the members' current indices must stay inside the new tables
+    const greb_member_forcing& f = e->h_force[m];
+    if (f.co2_pattern >= n_patterns || f.solar_table >= n_solar) {
+      std::snprintf(buf, sizeof(buf), "%smember %zu is forced with co2_pattern %d, solar_table %d: outside the new %d patterns, %d tables "
+                    "(change or clear the member forcing first)", who, m, f.co2_pattern, f.solar_table, n_patterns, n_solar);
+      return fail(e, GREB_E_INVALID, buf);
+    }
+  }
+  HIP_TRY(e, hipSetDevice(e->device));
+  // new buffers first; the engine changes only once they are complete
+  float *space = nullptr, *season = nullptr, *solar = nullptr;
+  auto step = [&](hipError_t err, const char* what) -> int {
+    if (err == hipSuccess) return 0;
+    if (space) (void)hipFree(space);
+    if (season) (void)hipFree(season);
+    if (solar) (void)hipFree(solar);
+    return fail(e, (int)err, std::string(who) + what + ": " + hipGetErrorString(err));
+  };
+  if (n_patterns > 0) {
+    std::vector<float> ones;
+    if (!co2_season) ones.assign((size_t)n_patterns * kNT, 1.f);
+    if (int rc = step(dev_alloc(&space, (size_t)n_patterns * np), "hipMalloc")) return rc;
+    if (int rc = step(dev_alloc(&season, (size_t)n_patterns * kNT), "hipMalloc")) return rc;
+    if (int rc = step(hipMemcpy(space, co2_space, (size_t)n_patterns * np * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy")) return rc;
+    if (int rc = step(hipMemcpy(season, co2_season ? co2_season : ones.data(), (size_t)n_patterns * kNT * sizeof(float),
+                                hipMemcpyHostToDevice), "hipMemcpy")) return rc;
+  }
+  if (n_solar > 0) {
+    if (int rc = step(dev_alloc(&solar, (size_t)n_solar * kNT * ny), "hipMalloc")) return rc;
+    if (int rc = step(hipMemcpy(solar, sw_solar, (size_t)n_solar * kNT * ny * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy")) return rc;
+  }
+  if (int rc = step(hipStreamSynchronize(e->stream), "hipStreamSynchronize")) return rc; // nothing in flight reads the old ones
+  if (e->f_space) (void)hipFree(e->f_space);
+  if (e->f_season) (void)hipFree(e->f_season);
+  if (e->f_solar) (void)hipFree(e->f_solar);
+  e->f_space = space; e->f_season = season; e->f_solar = solar;
+  e->n_patterns = n_patterns; e->n_solar = n_solar;
+  return 0;
+}
+
+int greb_engine_set_member_forcing(greb_engine* e, const greb_member_forcing* f) {
+  const char* who = "set_member_forcing: ";
+  if (!e) return fail(nullptr, GREB_E_INVALID, std::string(who) + "no engine (greb_engine is NULL)");
+  if (!f) { // every member {-1, ., -1, 1}: the default kernels again
+    e->h_force.clear();
+    e->forced_members = 0;
+    return 0;
+  }
+  const size_t nm = (size_t)e->nm;
+  char buf[200];
+  int forced = 0;
+  for (size_t m = 0; m < nm; ++m) {
+    const greb_member_forcing& x = f[m];
+    buf[0] = 0;
+    if (x.co2_pattern < -1 || x.co2_pattern >= e->n_patterns)
+      std::snprintf(buf, sizeof(buf), "%smember %zu: co2_pattern %d is outside -1 ... %d (set_forcing_tables gave %d patterns)", who, m,
+                    x.co2_pattern, e->n_patterns - 1, e->n_patterns);
+    else if (x.solar_table < -1 || x.solar_table >= e->n_solar)
+      std::snprintf(buf, sizeof(buf), "%smember %zu: solar_table %d is outside -1 ... %d (set_forcing_tables gave %d tables)", who, m,
+                    x.solar_table, e->n_solar - 1, e->n_solar);
+    else if (x.co2_pattern >= 0 && !(std::isfinite(x.co2_ref) && x.co2_ref > 0.f))
+      std::snprintf(buf, sizeof(buf), "%smember %zu: co2_ref %g is not finite or not positive", who, m, (double)x.co2_ref);
+    else if (!(std::isfinite(x.solar_scale) && x.solar_scale >= 0.f))
+      std::snprintf(buf, sizeof(buf), "%smember %zu: solar_scale %g is not finite or negative", who, m, (double)x.solar_scale);
+    if (buf[0]) return fail(e, GREB_E_INVALID, buf);
+    forced += is_forced(x);
+  }
+  std::vector<MemberForcing> w(nm);
+  for (size_t m = 0; m < nm; ++m) // (co2_ref of a member without a pattern is never read: any bits may stand there)
+    w[m] = MemberForcing{f[m].co2_pattern, f[m].co2_pattern >= 0 ? f[m].co2_ref : 1.f, f[m].solar_table, f[m].solar_scale};
+  if (forced > 0) {
+    HIP_TRY(e, hipSetDevice(e->device));
+    MemberForcing* dev = nullptr;
+    HIP_TRY(e, dev_alloc(&dev, nm));
+    hipError_t err = hipMemcpy(dev, w.data(), nm * sizeof(MemberForcing), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    if (err != hipSuccess) { (void)hipFree(dev); HIP_TRY(e, err); }
+    if (e->force_dev) (void)hipFree(e->force_dev);
+    e->force_dev = dev;
+  }
+  e->h_force.assign(f, f + nm);
+  e->forced_members = forced;
   return 0;
 }
 

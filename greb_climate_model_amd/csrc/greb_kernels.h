@@ -30,6 +30,14 @@ constexpr int tuning_int(const char*, int dflt) { return dflt; }
 // passes, not this ceiling.
 constexpr int kMaxDynamicLds = 160 * 1024;
 
+// greb_member_forcing of include/greb_engine.h as the kernels read it: four words per member
+struct MemberForcing {
+  int co2_pattern;   // -1: CO2 is the member's scalar; else the pattern whose weights blend it with co2_ref
+  float co2_ref;     // CO2 where the weight is 0
+  int solar_table;   // -1: MemberArgs::sw_solar; else a table of MemberArgs::f_solar
+  float solar_scale; // multiplies the table
+};
+
 // Everything the fused member kernel needs (passed by value as a kernel argument).
 struct MemberArgs {
   int nx, ny, np;
@@ -74,6 +82,12 @@ struct MemberArgs {
   float* brec;             // [nm][brec_years][12][kNBudget][np] monthly means of the terms
   int brec_years;          // years per member in `brec`
   int brec_year0;          // index there of the year containing it0
+  // per-member forcing (read by the FORCE instantiations only, which a launch takes when force_m is set; scenario phase
+  // only: greb_physics_step.h, member_force).  Appended: the offsets of everything above are those of a build without it.
+  const MemberForcing* force_m; // [nm] each member's four words; null: no member of the launch is forced
+  const float* f_space;         // [n_patterns][np]  CO2 weights in [0, 1]
+  const float* f_season;        // [n_patterns][730] their seasonal factor (all ones where the caller gave none)
+  const float* f_solar;         // [n_solar][730][ny] insolation tables
 };
 
 // GREB_NBUDGET, GREB_B_*: the flux terms of one step in the order of include/greb_engine.h

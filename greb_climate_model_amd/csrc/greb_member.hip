@@ -897,7 +897,10 @@ hipError_t launch_circulation_g96(const float* X, const float* wz, const float* 
 // barriers inside Circ::substeps stay matched).
 // BUDGET (scenario phase, opt-in: greb_engine_run_budget): the monthly means of the step's thirteen flux terms go out
 // beside the five standard records.  The default instantiations contain none of it.
-template <bool STRICT, bool FLUX, bool EXP, bool BUDGET = false>
+// FORCE (scenario phase, with EXP: a launch with any forced member, greb_engine_set_member_forcing): the member's CO2 pattern,
+// insolation table and scale act in the point physics (greb_physics_step.h: member_force).  Its words are read anew every
+// model step, into scalar registers, so that nothing of it lives across the sub-steps.  No other instantiation contains it.
+template <bool STRICT, bool FLUX, bool EXP, bool BUDGET = false, bool FORCE = false>
 __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
   extern __shared__ __align__(16) float lds_raw[];
   lfloat* lds = (lfloat*)lds_raw;
@@ -958,6 +961,7 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
     // ---- point physics on the OLD state + Euler update (:254-268 / :328-361)
     const Phys P = a.phys[m];
     const float co2 = FLUX ? co2_flux : a.co2[(size_t)m * a.co2_stride + a.co2_year0 + yr_rel]; // :924
+    const MemberForce mf = member_force<FORCE>(a, m, ck);
     lfloat* Xf = lds + kOffX + cur * XB;       // the tracers after the 24 sub-steps
     lfloat* red = lds + kOffX + (cur ^ 1) * XB; // idle buffer: annual-mean reduction scratch
     // Each thread takes whole quads (4 consecutive longitudes): every load/store of the ~26
@@ -986,8 +990,8 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 #pragma unroll 1
       for (int qd = tid; qd < NP / 4; qd += kThreads) {
         const q8 xpair = ld8(Xf + (qd / NQ) * RS, qd % NQ);
-        const PhysIn in = physics_load<FLUX, EXP>(a, qd, ck, state, acc, corr, xsw);
-        (void)physics_compute<STRICT, FLUX, EXP, true>(a, P, in, co2, comp(xpair, 0), comp(xpair, 1), xsw, bs, 4 * qd);
+        const PhysIn in = physics_load<FLUX, EXP, FORCE>(a, qd, ck, state, acc, corr, xsw, mf);
+        (void)physics_compute<STRICT, FLUX, EXP, true, FORCE>(a, P, in, co2, comp(xpair, 0), comp(xpair, 1), xsw, bs, 4 * qd, mf);
       }
     }
 #pragma unroll 1
@@ -997,7 +1001,7 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 #endif
       const q8 xpair = ld8(Xf + (qd / NQ) * RS, qd % NQ);
       f4 oTa, oq, tsm;
-      physics_quad<STRICT, FLUX, EXP>(a, P, m, qd, ck, co2, state, acc, corr, comp(xpair, 0), comp(xpair, 1), oTa, oq, tsm, xsw);
+      physics_quad<STRICT, FLUX, EXP, false, FORCE>(a, P, m, qd, ck, co2, state, acc, corr, comp(xpair, 0), comp(xpair, 1), oTa, oq, tsm, xsw, mf);
       st8(Xf + (qd / NQ) * RS, qd % NQ, zip(oTa, oq));
       if (ityr == kNT) st4(red + 4 * qd, tsm);
     }
@@ -1052,7 +1056,11 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 hipError_t launch_member_kernel(const MemberArgs& a, int n_members, bool strict, hipStream_t s) {
   if (a.nx != NX || a.ny != NY) return hipErrorInvalidValue;
   void (*kern)(MemberArgs);
-  if (a.bsum) { // budget output (scenario phase only): the opt-in instantiations
+  if (a.force_m) { // a forced member (scenario phase only): every member of the launch takes the forcing-aware instantiation
+    if (a.flux_phase || (a.bsum && !a.brec)) return hipErrorInvalidValue;
+    if (a.bsum) kern = strict ? member_kernel<true, false, true, true, true> : member_kernel<false, false, true, true, true>;
+    else kern = strict ? member_kernel<true, false, true, false, true> : member_kernel<false, false, true, false, true>;
+  } else if (a.bsum) { // budget output (scenario phase only): the opt-in instantiations
     if (a.flux_phase || !a.brec) return hipErrorInvalidValue;
     if (a.xsw || a.xsw_m) kern = strict ? member_kernel<true, false, true, true> : member_kernel<false, false, true, true>;
     else kern = strict ? member_kernel<true, false, false, true> : member_kernel<false, false, false, true>;

@@ -35,6 +35,41 @@ __device__ __forceinline__ unsigned member_switches(const MemberArgs& a, int m) 
   return (unsigned)__builtin_amdgcn_readfirstlane((int)(a.xsw_m ? a.xsw_m[m] : a.xsw));
 }
 
+// Per-member forcing (FORCE instantiations, scenario phase only; greb_engine_set_member_forcing): the member's four words
+// and what they select from the engine's shared tables, for one model step.  Everything here is block-uniform and read
+// once per step into scalar registers -- nothing of it lives across the circulation sub-steps; what is per point is the
+// pattern's weight quad (PhysIn::fw) and the three operations of forced_co2.
+struct MemberForce {
+  const float* space; // the member's CO2 pattern [np]; null: none, CO2 is the member's scalar
+  const float* solar; // the member's insolation table [730][ny] (the engine's own where the member names none)
+  float season;       // the pattern's seasonal factor of this step
+  float ref, scale;   // CO2 where the weight is 0; factor on the insolation
+};
+__device__ __forceinline__ float uniform_f(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+template <bool FORCE>
+__device__ __forceinline__ MemberForce member_force(const MemberArgs& a, int m, const StepClock& ck) {
+  MemberForce f{nullptr, a.sw_solar, 1.f, 0.f, 1.f};
+  if (FORCE) {
+    const MemberForcing w = a.force_m[m];
+    const int k = __builtin_amdgcn_readfirstlane(w.co2_pattern), t = __builtin_amdgcn_readfirstlane(w.solar_table);
+    f.ref = uniform_f(w.co2_ref); f.scale = uniform_f(w.solar_scale);
+    if (k >= 0) {
+      f.space = a.f_space + (size_t)k * a.np;
+      f.season = uniform_f(a.f_season[(size_t)k * kNT + (ck.ityr - 1)]);
+    }
+    if (t >= 0) f.solar = a.f_solar + (size_t)t * kNT * a.ny;
+  }
+  return f;
+}
+// CO2 of one point under a pattern: the lerp whose ends are exact -- weight 1 gives co2 bit for bit, weight 0 gives ref
+__device__ __forceinline__ float forced_co2(const MemberForce& f, float w_space, float co2) {
+#pragma clang fp contract(off)
+  const float w = w_space * f.season;
+  const float part = w * co2;
+  const float rest = (1.f - w) * f.ref;
+  return part + rest;
+}
+
 // One quad in three pieces -- load, compute, store -- so that a caller with several quads per thread can request the
 // next quad's operands BETWEEN the arithmetic of the current one and its stores (vector-memory operations retire in
 // order: loads issued behind a quad's stores wait for those stores as well).
@@ -47,6 +82,7 @@ struct PhysIn {
   f4 c0, c1, c2;                              // flux: Toclim, qclim, -- ; scenario: TF, qF, ToF
   f4 acc0, acc1, acc2, acc3, acc4, acc5;      // monthly sums, annual Tsurf sum
   f4 qcl, tclp;                               // experiments only
+  f4 fw;                                      // FORCE only: the CO2 pattern's weights
   float solar;
 };
 struct PhysOut { // everything the stores need: the inputs are dead once this exists
@@ -54,9 +90,11 @@ struct PhysOut { // everything the stores need: the inputs are dead once this ex
   f4 s0, s1, s2, s3, s4; // the monthly sums including this step (:974)
 };
 
-template <bool FLUX, bool EXP>
+template <bool FLUX, bool EXP, bool FORCE = false>
 __device__ __forceinline__ PhysIn physics_load(const MemberArgs& a, int qd, const StepClock& ck, const float* __restrict__ state,
-                                               const float* __restrict__ acc, const float* __restrict__ corr, unsigned xsw_member) {
+                                               const float* __restrict__ acc, const float* __restrict__ corr, unsigned xsw_member,
+                                               const MemberForce& F = MemberForce{}) {
+  static_assert(!FORCE || (EXP && !FLUX), "forcing: scenario phase, switch-aware instantiations only");
   const int nx = a.nx, ny = a.ny, np = a.np, p0 = 4 * qd;
   const size_t off = ck.off, offm = ck.offm;
   const unsigned xsw = EXP ? xsw_member : 0u;
@@ -67,7 +105,10 @@ __device__ __forceinline__ PhysIn physics_load(const MemberArgs& a, int qd, cons
   i.tcl = ld4(a.tclim + off + p0); i.cld = ld4(a.cldclim + off + p0); i.mld = ld4(a.mldclim + off + p0);
   i.mldm = ld4(a.mldclim + offm + p0); i.swet = ld4(a.swetclim + off + p0); i.u = ld4(a.uclim + off + p0);
   i.v = ld4(a.vclim + off + p0);
-  i.solar = a.sw_solar[(size_t)(ck.ityr - 1) * ny + p0 / nx]; // a quad never straddles rows
+  if (FORCE) {
+#pragma clang fp contract(off)
+    i.solar = F.solar[(size_t)(ck.ityr - 1) * ny + p0 / nx] * F.scale; // one rounding, then sw = solar * (1 - albedo)
+  } else i.solar = a.sw_solar[(size_t)(ck.ityr - 1) * ny + p0 / nx]; // a quad never straddles rows
   if (FLUX) { i.c0 = ld4(a.toclim + p0); i.c1 = ld4(a.qclim + off + p0); i.c2 = zero4(); }
   else { i.c0 = ld4(corr + off + p0); i.c1 = ld4(corr + (size_t)kNT * np + off + p0); i.c2 = ld4(corr + (size_t)2 * kNT * np + off + p0); }
   i.acc0 = i.acc1 = i.acc2 = i.acc3 = i.acc4 = zero4();
@@ -84,6 +125,8 @@ __device__ __forceinline__ PhysIn physics_load(const MemberArgs& a, int qd, cons
   i.qcl = zero4(); i.tclp = zero4(); // experiments only: qclim(ityr) for the linear emissivity, Tclim of the previous step
   if (EXP && (xsw & kXLwLinear)) i.qcl = FLUX ? i.c1 : ld4(a.qclim + off + p0);
   if (EXP && !FLUX && (xsw & kXSstPlus1)) i.tclp = ld4(a.tclim + offm + p0);
+  i.fw = zero4();
+  if (FORCE && F.space) i.fw = ld4(F.space + p0);
   return i;
 }
 
@@ -127,9 +170,12 @@ __device__ __forceinline__ void budget_add(const BudgetSink& b, int np, int term
 // the point physics and the Euler update of the quad (src/greb.f90:254-268 scenario, :328-361 flux correction);
 // xTa, xq: the tracers after the 24 circulation sub-steps.  BUDGET: the terms of the update are also added to the member's
 // budget sums (bs; p0: the quad's first point) -- under a member's switches they are what the update really used.
-template <bool STRICT, bool FLUX, bool EXP, bool BUDGET = false>
+// FORCE: CO2 is the member's scalar blended per point with its reference by the pattern's weight (forced_co2); the insolation
+// came forced from physics_load.
+template <bool STRICT, bool FLUX, bool EXP, bool BUDGET = false, bool FORCE = false>
 __device__ __forceinline__ PhysOut physics_compute(const MemberArgs& a, const Phys& P, const PhysIn& in, float co2, const f4& xTa,
-                                                   const f4& xq, unsigned xsw_member, const BudgetSink& bs = BudgetSink{}, int p0 = 0) {
+                                                   const f4& xq, unsigned xsw_member, const BudgetSink& bs = BudgetSink{}, int p0 = 0,
+                                                   const MemberForce& F = MemberForce{}) {
   static_assert(!(BUDGET && FLUX), "the flux-correction phase delivers no budget");
   const unsigned xsw = EXP ? xsw_member : 0u;
   const int np = a.np;
@@ -152,7 +198,8 @@ __device__ __forceinline__ PhysOut physics_compute(const MemberArgs& a, const Ph
     float albedo, sw, LWsurf, LWdown, em, Qlat, Qlat_air, dq_eva, dq_rain, dT_ocean, dTo;
     sw_radiation<STRICT>(P, Ts1, zt, gl, cld, in.solar, albedo, sw, xsw);
     budget_add<BUDGET>(bs, np, kBsw, p0 + e, sw);
-    lw_radiation<STRICT>(P, Ts1, Ta1, q1, co2, ez, cld, tcl, LWsurf, LWdown, em, xsw, in.qcl.v[e]);
+    const float co2_e = (FORCE && F.space) ? forced_co2(F, in.fw.v[e], co2) : co2;
+    lw_radiation<STRICT>(P, Ts1, Ta1, q1, co2_e, ez, cld, tcl, LWsurf, LWdown, em, xsw, in.qcl.v[e]);
     budget_add<BUDGET>(bs, np, kBLWsurf, p0 + e, LWsurf); budget_add<BUDGET>(bs, np, kBLWdown, p0 + e, LWdown);
     const float LWabs = em * LWsurf; // the product of :260
     budget_add<BUDGET>(bs, np, kBLWabs, p0 + e, LWabs);
@@ -247,13 +294,13 @@ __device__ __forceinline__ void physics_store(const MemberArgs& a, int m, int qd
 }
 
 // the three pieces in a row (one quad per thread: the any-grid engine)
-template <bool STRICT, bool FLUX, bool EXP = false, bool BUDGET = false>
+template <bool STRICT, bool FLUX, bool EXP = false, bool BUDGET = false, bool FORCE = false>
 __device__ __forceinline__ void physics_quad(const MemberArgs& a, const Phys& P, int m, int qd, const StepClock& ck,
                                              float co2, float* __restrict__ state, float* __restrict__ acc,
                                              float* __restrict__ corr, const f4& xTa, const f4& xq, f4& oTa_out,
-                                             f4& oq_out, f4& tsmn_mean, unsigned xsw = 0u) {
-  const PhysIn in = physics_load<FLUX, EXP>(a, qd, ck, state, acc, corr, xsw);
-  const PhysOut o = physics_compute<STRICT, FLUX, EXP, BUDGET>(a, P, in, co2, xTa, xq, xsw, budget_sink<BUDGET>(a, m, ck), 4 * qd);
+                                             f4& oq_out, f4& tsmn_mean, unsigned xsw = 0u, const MemberForce& F = MemberForce{}) {
+  const PhysIn in = physics_load<FLUX, EXP, FORCE>(a, qd, ck, state, acc, corr, xsw, F);
+  const PhysOut o = physics_compute<STRICT, FLUX, EXP, BUDGET, FORCE>(a, P, in, co2, xTa, xq, xsw, budget_sink<BUDGET>(a, m, ck), 4 * qd, F);
   physics_store<FLUX>(a, m, qd, ck, o, state, acc, corr, tsmn_mean);
   oTa_out = o.Ta; oq_out = o.q;
 }

@@ -58,7 +58,7 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_substep_launch_order", "greb_circulation_launch_plan", "greb_engine_describe",
            "greb_engine_create_members", "greb_engine_set_member_experiments", "greb_diag_create", "greb_diag_destroy",
            "greb_diag_reduce_dev", "greb_engine_run_diag", "greb_engine_run_budget", "greb_budget_name",
-           "greb_member_deal_cover"]
+           "greb_member_deal_cover", "greb_engine_set_forcing_tables", "greb_engine_set_member_forcing"]
 
 
 def _check(rc: int, h=None):
@@ -273,6 +273,47 @@ class Engine:
         if sw.shape != (self.nm,):
             raise GrebError(-1, f"set_member_experiments: {self.nm} switch words expected")
         _check(lib().greb_engine_set_member_experiments(self.h, sw.ctypes.data_as(C.POINTER(C.c_uint32))), self.h)
+
+    def set_forcing_tables(self, space, season=None, solar=None):
+        """The forcing tables every member shares (greb_engine_set_forcing_tables; replaces the ones set before):
+        space [n_patterns][ny][nx] CO2 weights in [0, 1] (or None: no patterns), season [n_patterns][730] their seasonal
+        factor in [0, 1] (None: 1 everywhere), solar [n_solar][730][ny] insolation tables in W/m2 (None: none)."""
+        def arr(x, tail, what):
+            if x is None:
+                return None
+            x = np.ascontiguousarray(x, np.float32)
+            if x.ndim == len(tail):
+                x = x[None]
+            if x.shape[1:] != tail:
+                raise GrebError(-1, f"set_forcing_tables: {what} has shape {x.shape}, expected [n]{list(tail)}")
+            return x
+        space = arr(space, (self.ny, self.nx), "space")
+        season = arr(season, (abi.NSTEP_YR,), "season")
+        solar = arr(solar, (abi.NSTEP_YR, self.ny), "solar")
+        if season is not None and (space is None or len(season) != len(space)):
+            raise GrebError(-1, "set_forcing_tables: season needs one row of 730 per pattern of space")
+        ptr = lambda x: None if x is None else abi.fptr(x)
+        _check(lib().greb_engine_set_forcing_tables(self.h, 0 if space is None else len(space), ptr(space), ptr(season),
+                                                    0 if solar is None else len(solar), ptr(solar)), self.h)
+
+    def set_member_forcing(self, forcing):
+        """One dict per member (greb_engine_set_member_forcing), keys co2_pattern (default -1: none), co2_ref (340),
+        solar_table (-1: the engine's own), solar_scale (1); None: no member is forced.  Acts in run / run_budget /
+        run_diag from the next call; flux_correction ignores it."""
+        if forcing is None:
+            _check(lib().greb_engine_set_member_forcing(self.h, None), self.h)
+            return
+        forcing = list(forcing)
+        if len(forcing) != self.nm:
+            raise GrebError(-1, f"set_member_forcing: {self.nm} entries expected")
+        arr = (abi.GrebMemberForcing * self.nm)()
+        for f, d in zip(arr, forcing):
+            d = dict(d or {})
+            f.co2_pattern = int(d.pop("co2_pattern", -1)); f.co2_ref = float(d.pop("co2_ref", 340.0))
+            f.solar_table = int(d.pop("solar_table", -1)); f.solar_scale = float(d.pop("solar_scale", 1.0))
+            if d:
+                raise GrebError(-1, f"set_member_forcing: unknown key {sorted(d)[0]!r}")
+        _check(lib().greb_engine_set_member_forcing(self.h, arr), self.h)
 
     def point_physics(self, ityr: int, co2: float, in5) -> np.ndarray:
         in5 = np.ascontiguousarray(in5, np.float32)

@@ -230,6 +230,43 @@ int greb_diag_reduce_dev(greb_diag* d, int device, const float* monthly_year_dev
 int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_diag* d, unsigned what, float* regions,
                          float* zonal, float* annual, float* yearly);
 
+/* ---- per-member forcing: regional and seasonal CO2, insolation tables and scale --------------------
+ * Members of one engine may differ in the forcing itself, not only in the CO2 level: CO2 raised in one hemisphere, over
+ * land or ocean only or in one half of the year, a changed solar constant, a changed latitudinal or seasonal distribution
+ * of insolation.  A few small tables shared by the engine, four words per member, all of it used in the point physics
+ * only; members that differ only in forcing still share one flux-correction set.  For member m, point p of row j, step
+ * ityr (1-based) of scenario year y, with k = co2_pattern and t = solar_table (fl: one fp32 rounding; no contraction, in
+ * both arithmetic modes):
+ *   k >= 0:  w   = fl(space[k][p] * season[k][ityr-1])
+ *            co2 = fl( fl(w * co2_ppm[m][y]) + fl( fl(1 - w) * co2_ref[m] ) )
+ *   k <  0:  co2 = co2_ppm[m][y]
+ *   S     = (t >= 0 ? sw_solar[t] : the engine's greb_fields.sw_solar)[ityr-1][j]
+ *   solar = fl(S * solar_scale[m]),   then sw = solar * (1 - albedo) as src/greb.f90:399
+ * so that w = 1 gives co2_ppm bit for bit, w = 0 gives co2_ref, and solar_scale = 1 gives S.
+ * Scope: the scenario phase -- greb_engine_run, greb_engine_run_budget, greb_engine_run_diag, whose signatures are
+ * unchanged.  greb_engine_flux_correction ignores it, as it ignores GREB_X_SST_PLUS1.  A launch with any forced member
+ * takes forcing-aware instantiations of the kernels for all its members; with no forced member the engine launches
+ * exactly the kernels it launches without any of this.
+ * GREB_E_INVALID, with a message that names the offender: n_patterns or n_solar outside 0 ... GREB_MAX_FORCING_TABLES, a
+ * weight that is not finite or lies outside [0, 1], a negative or non-finite table value, an index out of range, co2_ref
+ * not finite or <= 0, solar_scale not finite or < 0.  A failed call leaves the engine exactly as it was. */
+#define GREB_MAX_FORCING_TABLES 16
+/* Tables shared by all members; copied to the device; may be called again (replaces them).  Replacing them with fewer
+ * tables than a member's current forcing names is GREB_E_INVALID: change or clear the member forcing first. */
+int greb_engine_set_forcing_tables(greb_engine* e,
+      int n_patterns, const float* co2_space  /* [n_patterns][ny][nx], weights in [0,1] */,
+                      const float* co2_season /* [n_patterns][730] in [0,1]; NULL = 1 everywhere */,
+      int n_solar,    const float* sw_solar   /* [n_solar][730][ny], W/m2, >= 0 */);
+typedef struct greb_member_forcing {
+  int32_t co2_pattern;  /* -1: none, CO2 is the member's scalar as today; else 0 .. n_patterns-1 */
+  float   co2_ref;      /* CO2 where the weight is 0 */
+  int32_t solar_table;  /* -1: the engine's own sw_solar; else 0 .. n_solar-1 */
+  float   solar_scale;  /* multiplies the table; 1 = unchanged */
+} greb_member_forcing;
+/* f[n_members]; NULL = every member {-1, ., -1, 1}.  Cheap: four words per member.  Takes effect from the next run call.
+ * A member is forced when it names a pattern or a table or its scale is not 1 (greb_engine_describe: "forcing"). */
+int greb_engine_set_member_forcing(greb_engine* e, const greb_member_forcing* f);
+
 /* ---- sensitivity-experiment switches -----------------------------------------
  * Runtime switches on the same kernels that reproduce the `log_exp` experiments of the upstream model
  * variant (src/greb.original.model.f90:60,162-166,394,423-430,452-453,492-495,513-515,553-571; doc in its
