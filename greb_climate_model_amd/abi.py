@@ -58,6 +58,11 @@ class GrebMemberConfig(C.Structure):
     _fields_ = [("p", GrebParams), ("switches", C.c_uint32)]
 
 
+MAX_BOUNDARY_SETS = 16  # GREB_MAX_BOUNDARY_SETS: boundary sets of one engine besides its own data (set 0)
+BS_REINIT = 1           # GREB_BS_REINIT: set_member_boundary also puts every member into the initial state of its set
+# the fields of greb_fields a boundary set may replace, with their rank (sw_solar is forcing, not boundary data)
+BOUNDARY_FIELDS = {"z_topo": 2, "glacier": 2, "tclim": 3, "qclim": 3, "uclim": 3, "vclim": 3, "mldclim": 3, "cldclim": 3,
+                   "swetclim": 3}
 MAX_FORCING_TABLES = 16  # GREB_MAX_FORCING_TABLES: CO2 patterns, and insolation tables, of one engine
 
 

@@ -154,6 +154,20 @@ struct greb_engine {
   std::vector<greb_member_forcing> h_force;            // [nm], or empty: no member forcing set
   MemberForcing* force_dev = nullptr;                  // [nm], current whenever forced_members > 0
   int forced_members = 0;                              // members that name a pattern or a table or scale the insolation
+  // boundary sets (add_boundary_set, set_member_boundary): both phases
+  struct BoundSet {
+    float* dev[kBoundaryFields] = {};    // the set's thirteen device arrays in BoundarySet's order: its own or the engine's
+    bool own[kBoundaryFields] = {};      // which of them this set allocated
+    unsigned over = 0;                   // bit i: input field i (< kBoundaryInputs) is overridden
+    // what the initial state is made of (:190-197), np floats each: tclim[729], qclim[729], toclim, z_topo, mldclim[0]
+    std::vector<float> t_last, q_last, toclim, z_topo, mld0;
+  };
+  std::vector<BoundSet> bound;                         // [1 + sets made]; [0]: the engine's own data
+  std::vector<int> h_bset;                             // [nm] each member's set, or empty: every member 0
+  int members_on_sets = 0;                             // members that name a set above 0
+  BoundarySet* bsets_dev = nullptr;                    // [1 + GREB_MAX_BOUNDARY_SETS], made with the first set
+  int* bset_dev = nullptr;                             // [nm], current whenever members_on_sets > 0
+  MemberForcing* neutral_force_dev = nullptr;          // [nm] {-1, ., -1, 1}: what a BOUND scenario launch takes when no member is forced
   float* yearly_dev = nullptr; size_t yearly_cap = 0;
   float* diag_out = nullptr; size_t diag_out_cap = 0; // run_diag: zonal means and annual maps of two years (one per staging slot)
   float* diag_reg = nullptr; size_t diag_reg_cap = 0; // run_diag: the region series of the whole call
@@ -210,11 +224,15 @@ MemberArgs base_args(greb_engine* e) {
   unsigned all = GREB_X_NO_CIRCULATION;
   for (unsigned x : e->h_xsw) all &= x;
   if (all) a.nsub = 0;
+  // a member on a boundary set: the launch carries the set table and takes the boundary-aware kernels
+  if (e->members_on_sets > 0) { a.bsets = e->bsets_dev; a.bset_m = e->bset_dev; }
   return a;
 }
 
 // scenario launches only: with a forced member the launch carries the forcing and takes the forcing-aware kernels
 void apply_forcing(const greb_engine* e, MemberArgs& a) {
+  // (the boundary-aware scenario kernels are forcing-aware: without a forced member they get words that force nothing)
+  if (e->forced_members <= 0 && e->members_on_sets > 0) a.force_m = e->neutral_force_dev;
   if (e->forced_members <= 0) return;
   a.force_m = e->force_dev;
   a.f_space = e->f_space; a.f_season = e->f_season; a.f_solar = e->f_solar;
@@ -463,6 +481,72 @@ const char* greb_device_info(int device) {
 } // extern "C"
 
 namespace {
+// The derived fields of greb_model's preamble (host, once per engine and per boundary set that replaces their source):
+// Toclim :1088-1094 from tclim, z_ocean :179-183 from mldclim, wz_air / wz_vapor :201-202 from z_topo.  A null source
+// leaves its outputs alone.
+void derive_fields(const greb_params& p, size_t np, const float* z_topo, const float* tclim, const float* mldclim, float* toclim,
+                   float* z_ocean, float* wz_air, float* wz_vapor) {
+  for (size_t i = 0; i < np; ++i) {
+    if (tclim) {
+      float mn = tclim[i];
+      for (int t = 0; t < kNT; ++t) { const float v = tclim[(size_t)t * np + i]; if (v < mn) mn = v; }
+      if (mn - 273.15f < -1.7f) mn = -1.7f + 273.15f;
+      toclim[i] = mn;
+    }
+    if (mldclim) {
+      float mx = 0.f;
+      for (int t = 0; t < kNT; ++t) { const float d = mldclim[(size_t)t * np + i]; if (d > mx) mx = d; }
+      z_ocean[i] = 3.0f * mx;
+    }
+    if (z_topo) {
+      wz_air[i] = expf(-z_topo[i] / p.z_air);
+      wz_vapor[i] = expf(-z_topo[i] / p.z_vapor);
+    }
+  }
+}
+
+// the initial state of one member (:194-197) and its initial cap_surf (:190-191) on the data of one boundary set
+void initial_state(const greb_engine::BoundSet& b, const Phys& P, size_t np, float* st) {
+  for (size_t i = 0; i < np; ++i) {
+    st[i] = b.t_last[i]; st[np + i] = st[i]; st[2 * np + i] = b.toclim[i]; st[3 * np + i] = b.q_last[i];
+    float c = 0.f;
+    if (b.z_topo[i] > 0.f) c = P.cap_land;
+    if (b.z_topo[i] <= 0.f) c = P.cap_ocean * b.mld0[i];
+    st[4 * np + i] = c;
+  }
+}
+
+const char* const kBoundaryNames[kBoundaryFields] = {"z_topo", "glacier", "tclim", "qclim", "uclim", "vclim", "mldclim", "cldclim",
+                                                     "swetclim", "toclim", "z_ocean", "wz_air", "wz_vapor"};
+enum { kBfZtopo, kBfGlacier, kBfTclim, kBfQclim, kBfUclim, kBfVclim, kBfMld, kBfCld, kBfSwet, kBfToclim, kBfZocean, kBfWzAir, kBfWzVapor };
+size_t boundary_floats(int field, size_t np) { return (field >= kBfTclim && field <= kBfSwet) ? np * kNT : np; }
+
+// An engine whose members share one flux-correction set gives every member a copy of it -- on a NEW buffer: the engine is
+// untouched, and the caller frees the buffer if anything later fails.
+hipError_t copy_shared_corrections(greb_engine* e, float** corr, const char** what) {
+  const size_t nm = (size_t)e->nm, set = (size_t)3 * kNT * e->np;
+  hipError_t err = hipStreamSynchronize(e->stream);
+  *what = "hipStreamSynchronize";
+  if (err != hipSuccess) return err;
+  *what = "hipMalloc of the members' correction sets";
+  if ((err = dev_alloc(corr, nm * set)) != hipSuccess) return err;
+  *what = "hipMemcpy";
+  for (size_t m = 0; m < nm; ++m)
+    if ((err = hipMemcpy(*corr + m * set, e->corr, set * sizeof(float), hipMemcpyDeviceToDevice)) != hipSuccess) return err;
+  return hipSuccess;
+}
+// The engine takes them: its correction index -- one small copy, the LAST step of a call that can fail -- then the buffer.
+hipError_t adopt_member_corrections(greb_engine* e, float* corr) {
+  std::vector<int> corr_index((size_t)e->nm);
+  for (int m = 0; m < e->nm; ++m) corr_index[(size_t)m] = m;
+  hipError_t err = hipMemcpy(e->corr_index, corr_index.data(), corr_index.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (err != hipSuccess) return err;
+  (void)hipFree(e->corr);
+  e->corr = corr;
+  e->shared_corr = false;
+  return hipSuccess;
+}
+
 // greb_engine_create_members, and greb_engine_create through it (`who` names the entry in messages)
 int create_engine(const char* who, const greb_params* p, int nx, int ny, const greb_fields* f, int n_members,
                   const greb_member_config* members, int device, unsigned flags, greb_engine** out) {
@@ -515,22 +599,21 @@ int create_engine(const char* who, const greb_params* p, int nx, int ny, const g
 
   // derived fields (host, once): Toclim :1088-1094, z_ocean :179-183, wz_* :201-202
   std::vector<float> toclim(np), z_ocean(np), wz_air(np), wz_vapor(np);
-  for (size_t i = 0; i < np; ++i) {
-    float mn = f->tclim[i], mx = 0.f;
-    for (int t = 0; t < kNT; ++t) {
-      const float v = f->tclim[(size_t)t * np + i]; if (v < mn) mn = v;
-      const float d = f->mldclim[(size_t)t * np + i]; if (d > mx) mx = d;
-    }
-    if (mn - 273.15f < -1.7f) mn = -1.7f + 273.15f;
-    toclim[i] = mn;
-    z_ocean[i] = 3.0f * mx;
-    wz_air[i] = expf(-f->z_topo[i] / p->z_air);
-    wz_vapor[i] = expf(-f->z_topo[i] / p->z_vapor);
-  }
+  derive_fields(*p, np, f->z_topo, f->tclim, f->mldclim, toclim.data(), z_ocean.data(), wz_air.data(), wz_vapor.data());
   HIP_TRY(e, up(&e->toclim, toclim.data(), np));
   HIP_TRY(e, up(&e->z_ocean, z_ocean.data(), np));
   HIP_TRY(e, up(&e->wz_air, wz_air.data(), np));
   HIP_TRY(e, up(&e->wz_vapor, wz_vapor.data(), np));
+  { // boundary set 0: the engine's own data
+    const size_t last = (size_t)(kNT - 1) * np;
+    greb_engine::BoundSet b0;
+    float* const dev[kBoundaryFields] = {e->z_topo, e->glacier, e->tclim, e->qclim, e->uclim, e->vclim, e->mldclim, e->cldclim,
+                                         e->swetclim, e->toclim, e->z_ocean, e->wz_air, e->wz_vapor};
+    for (int i = 0; i < kBoundaryFields; ++i) b0.dev[i] = dev[i];
+    b0.t_last.assign(f->tclim + last, f->tclim + last + np); b0.q_last.assign(f->qclim + last, f->qclim + last + np);
+    b0.toclim = toclim; b0.z_topo.assign(f->z_topo, f->z_topo + np); b0.mld0.assign(f->mldclim, f->mldclim + np);
+    e->bound.push_back(std::move(b0));
+  }
 
   // per-member physics, grid tables (deduplicated by kappa), correction-set mapping
   e->h_phys.resize(nm);
@@ -586,17 +669,9 @@ int create_engine(const char* who, const greb_params* p, int nx, int ny, const g
 
   // initial state :194-197 and initial cap_surf :190-191
   std::vector<float> st(5 * np);
-  const size_t last = (size_t)(kNT - 1) * np;
   HIP_TRY(e, dev_alloc(&e->state, nm * 5 * np));
   for (size_t m = 0; m < nm; ++m) {
-    const Phys& P = e->h_phys[m];
-    for (size_t i = 0; i < np; ++i) {
-      st[i] = f->tclim[last + i]; st[np + i] = st[i]; st[2 * np + i] = toclim[i]; st[3 * np + i] = f->qclim[last + i];
-      float c = 0.f;
-      if (f->z_topo[i] > 0.f) c = P.cap_land;
-      if (f->z_topo[i] <= 0.f) c = P.cap_ocean * f->mldclim[i];
-      st[4 * np + i] = c;
-    }
+    initial_state(e->bound[0], e->h_phys[m], np, st.data());
     HIP_TRY(e, hipMemcpy(e->state + m * 5 * np, st.data(), 5 * np * sizeof(float), hipMemcpyHostToDevice));
   }
   if (!e->fused) { // the member does not fit one CU (or has another sub-cycling layout): multi-launch engine
@@ -747,8 +822,10 @@ int greb_engine_destroy(greb_engine* e) {
                   e->cldclim, e->swetclim, e->toclim, e->z_ocean, e->wz_air, e->wz_vapor, e->state, e->acc,
                   e->corr, e->corr_index, e->tab_index, e->tabs, e->phys, e->co2_dev, e->monthly_dev, e->yearly_dev,
                   e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev, e->diag_out, e->diag_reg, e->bsum, e->budget_dev,
-                  e->f_space, e->f_season, e->f_solar, e->force_dev};
+                  e->f_space, e->f_season, e->f_solar, e->force_dev, e->bsets_dev, e->bset_dev, e->neutral_force_dev};
   for (void* q : ptrs) if (q) (void)hipFree(q);
+  for (size_t k = 1; k < e->bound.size(); ++k)
+    for (int i = 0; i < kBoundaryFields; ++i) if (e->bound[k].own[i]) (void)hipFree(e->bound[k].dev[i]);
   for (auto& kv : e->plans) free_plan(kv.second);
   if (e->call != greb_engine::kCallNever) ledger_release(e);
   for (int i = 0; i < 2; ++i) {
@@ -1066,6 +1143,26 @@ const char* greb_engine_describe(greb_engine* e) {
   std::snprintf(buf, sizeof(buf), ", \"forcing\": {\"patterns\": %d, \"solar_tables\": %d, \"forced_members\": %d}", e->n_patterns,
                 e->n_solar, e->forced_members);
   s += buf;
+  std::snprintf(buf, sizeof(buf), ", \"boundary\": {\"sets\": %d, \"members_on_sets\": %d, \"fields\": [", (int)e->bound.size() - 1,
+                e->members_on_sets);
+  s += buf;
+  for (size_t k = 1; k < e->bound.size(); ++k) {
+    s += k > 1 ? ", [" : "[";
+    bool first = true;
+    for (int i = 0; i < kBoundaryInputs; ++i)
+      if (e->bound[k].over & (1u << i)) { s += std::string(first ? "\"" : ", \"") + kBoundaryNames[i] + "\""; first = false; }
+    s += "]";
+  }
+  s += "]}";
+  { // the kernel family the next launch of each phase takes (budget output is chosen per call, on top of it)
+    bool any_x = false;
+    for (unsigned x : e->h_xsw) any_x = any_x || x != 0;
+    const char* sw = any_x || !e->xsw_uniform ? "switches" : "default";
+    std::snprintf(buf, sizeof(buf), ", \"kernel_family\": {\"flux_correction\": \"%s\", \"scenario\": \"%s\"}",
+                  e->members_on_sets > 0 ? "boundary" : sw,
+                  e->members_on_sets > 0 ? "boundary" : (e->forced_members > 0 ? "forcing" : sw));
+    s += buf;
+  }
   if (e->call != greb_engine::kCallNever) {
     std::snprintf(buf, sizeof(buf), ", \"wavefront_slots_granted\": %d, \"circulation\": [", e->slots_granted);
     s += buf;
@@ -1142,7 +1239,6 @@ int greb_engine_set_member_experiments(greb_engine* e, const uint32_t* switches)
   // index, one small copy, is the last step that can fail).
   unsigned* xsw_dev = nullptr;
   float* corr = nullptr;
-  const size_t set = (size_t)3 * kNT * e->np;
   auto step = [&](hipError_t err, const char* what) -> int {
     if (err == hipSuccess) return 0;
     if (corr) (void)hipFree(corr);
@@ -1153,19 +1249,11 @@ int greb_engine_set_member_experiments(greb_engine* e, const uint32_t* switches)
     if (int rc = step(dev_alloc(&xsw_dev, nm), "hipMalloc")) return rc;
     if (int rc = step(hipMemcpy(xsw_dev, sw.data(), nm * sizeof(unsigned), hipMemcpyHostToDevice), "hipMemcpy")) return rc;
     if (e->shared_corr && nm > 1) { // members that now differ need a correction set each: copies of the shared one
-      if (int rc = step(hipStreamSynchronize(e->stream), "hipStreamSynchronize")) return rc;
-      if (int rc = step(dev_alloc(&corr, nm * set), "hipMalloc of the members' correction sets")) return rc;
-      for (size_t m = 0; m < nm; ++m)
-        if (int rc = step(hipMemcpy(corr + m * set, e->corr, set * sizeof(float), hipMemcpyDeviceToDevice), "hipMemcpy")) return rc;
-      std::vector<int> corr_index(nm);
-      for (size_t m = 0; m < nm; ++m) corr_index[m] = (int)m;
-      if (int rc = step(hipMemcpy(e->corr_index, corr_index.data(), nm * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy")) return rc;
+      const char* what = "";
+      const hipError_t err = copy_shared_corrections(e, &corr, &what);
+      if (int rc = step(err, what)) return rc;
+      if (int rc = step(adopt_member_corrections(e, corr), "hipMemcpy")) return rc;
     }
-  }
-  if (corr) {
-    (void)hipFree(e->corr);
-    e->corr = corr;
-    e->shared_corr = false;
   }
   if (xsw_dev) {
     if (e->xsw_dev) (void)hipFree(e->xsw_dev);
@@ -1300,6 +1388,160 @@ int greb_engine_set_member_forcing(greb_engine* e, const greb_member_forcing* f)
   }
   e->h_force.assign(f, f + nm);
   e->forced_members = forced;
+  return 0;
+}
+
+static_assert(GREB_MAX_BOUNDARY_SETS == kMaxBoundarySets, "the set table's size mirrors the ABI");
+
+int greb_engine_add_boundary_set(greb_engine* e, const greb_fields* over, int* set_id) {
+  const char* who = "add_boundary_set: ";
+  if (!e) return fail(nullptr, GREB_E_INVALID, std::string(who) + "no engine (greb_engine is NULL)");
+  if (!over || !set_id) return fail(e, GREB_E_INVALID, std::string(who) + (over ? "set_id is NULL" : "`over` is NULL"));
+  if (over->sw_solar)
+    return fail(e, GREB_E_INVALID, std::string(who) + "sw_solar is not part of a boundary set: insolation tables are per-member forcing "
+                                   "(greb_engine_set_forcing_tables, greb_engine_set_member_forcing)");
+  const float* const src[kBoundaryInputs] = {over->z_topo, over->glacier, over->tclim, over->qclim, over->uclim, over->vclim,
+                                             over->mldclim, over->cldclim, over->swetclim};
+  unsigned mask = 0;
+  for (int i = 0; i < kBoundaryInputs; ++i) if (src[i]) mask |= 1u << i;
+  if (!mask) return fail(e, GREB_E_INVALID, std::string(who) + "every field of `over` is NULL: the set would be the engine's own data (set 0)");
+  if ((int)e->bound.size() - 1 >= GREB_MAX_BOUNDARY_SETS)
+    return fail(e, GREB_E_INVALID, who + ("the engine already has " + std::to_string(GREB_MAX_BOUNDARY_SETS)) + " boundary sets (GREB_MAX_BOUNDARY_SETS)");
+  const size_t np = (size_t)e->np;
+  for (int i = 0; i < kBoundaryInputs; ++i)
+    for (size_t j = 0, n = src[i] ? boundary_floats(i, np) : 0; j < n; ++j)
+      if (!std::isfinite(src[i][j])) {
+        char buf[160];
+        std::snprintf(buf, sizeof(buf), "%s%s: value %g at index %zu is not finite", who, kBoundaryNames[i], (double)src[i][j], j);
+        return fail(e, GREB_E_INVALID, buf);
+      }
+  HIP_TRY(e, hipSetDevice(e->device));
+  // the set on NEW buffers; the engine changes only once it is complete
+  greb_engine::BoundSet b = e->bound[0]; // everything inherited: aliases of the engine's arrays, its host slices
+  for (bool& o : b.own) o = false;
+  b.over = mask;
+  auto step = [&](hipError_t err, const char* what) -> int {
+    if (err == hipSuccess) return 0;
+    for (int i = 0; i < kBoundaryFields; ++i) if (b.own[i]) (void)hipFree(b.dev[i]);
+    return fail(e, (int)err, std::string(who) + what + ": " + hipGetErrorString(err));
+  };
+  auto put = [&](int field, const float* host) -> int { // the set's own copy of one field
+    float* d = nullptr;
+    if (int rc = step(dev_alloc(&d, boundary_floats(field, np)), "hipMalloc")) return rc;
+    b.dev[field] = d; b.own[field] = true;
+    return step(hipMemcpy(d, host, boundary_floats(field, np) * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
+  };
+  for (int i = 0; i < kBoundaryInputs; ++i)
+    if (src[i]) if (int rc = put(i, src[i])) return rc;
+  // derived fields whose source the set replaces, exactly as greb_engine_create makes them
+  std::vector<float> toclim(over->tclim ? np : 0), z_ocean(over->mldclim ? np : 0), wz_air(over->z_topo ? np : 0), wz_vapor(over->z_topo ? np : 0);
+  derive_fields(e->p, np, over->z_topo, over->tclim, over->mldclim, toclim.data(), z_ocean.data(), wz_air.data(), wz_vapor.data());
+  if (over->tclim) { if (int rc = put(kBfToclim, toclim.data())) return rc; }
+  if (over->mldclim) { if (int rc = put(kBfZocean, z_ocean.data())) return rc; }
+  if (over->z_topo) {
+    if (int rc = put(kBfWzAir, wz_air.data())) return rc;
+    if (int rc = put(kBfWzVapor, wz_vapor.data())) return rc;
+  }
+  const size_t last = (size_t)(kNT - 1) * np;
+  if (over->tclim) { b.t_last.assign(over->tclim + last, over->tclim + last + np); b.toclim = toclim; }
+  if (over->qclim) b.q_last.assign(over->qclim + last, over->qclim + last + np);
+  if (over->z_topo) b.z_topo.assign(over->z_topo, over->z_topo + np);
+  if (over->mldclim) b.mld0.assign(over->mldclim, over->mldclim + np);
+  // the table: made with the first set (entry 0: the engine's own); a new set fills the next entry, which no launch in
+  // flight reads
+  auto entry = [](const greb_engine::BoundSet& x) {
+    return BoundarySet{x.dev[0], x.dev[1], x.dev[2], x.dev[3], x.dev[4], x.dev[5], x.dev[6], x.dev[7], x.dev[8], x.dev[9], x.dev[10],
+                       x.dev[11], x.dev[12]};
+  };
+  BoundarySet* table = e->bsets_dev;
+  if (!table) {
+    if (int rc = step(dev_alloc(&table, (size_t)1 + GREB_MAX_BOUNDARY_SETS), "hipMalloc")) return rc;
+    const BoundarySet own = entry(e->bound[0]);
+    if (int rc = step(hipMemcpy(table, &own, sizeof(own), hipMemcpyHostToDevice), "hipMemcpy")) { (void)hipFree(table); return rc; }
+  }
+  const BoundarySet mine = entry(b);
+  if (int rc = step(hipMemcpy(table + e->bound.size(), &mine, sizeof(mine), hipMemcpyHostToDevice), "hipMemcpy")) {
+    if (!e->bsets_dev) (void)hipFree(table);
+    return rc;
+  }
+  e->bsets_dev = table;
+  e->bound.push_back(std::move(b));
+  *set_id = (int)e->bound.size() - 1;
+  return 0;
+}
+
+int greb_engine_set_member_boundary(greb_engine* e, const int32_t* set, unsigned flags) {
+  const char* who = "set_member_boundary: ";
+  if (!e) return fail(nullptr, GREB_E_INVALID, std::string(who) + "no engine (greb_engine is NULL)");
+  if (flags & ~GREB_BS_REINIT) return fail(e, GREB_E_INVALID, who + ("unknown flag bits in " + std::to_string(flags)));
+  const size_t nm = (size_t)e->nm, np = (size_t)e->np;
+  const int made = (int)e->bound.size() - 1;
+  std::vector<int> bs(nm, 0);
+  int on_sets = 0;
+  bool uniform = true;
+  for (size_t m = 0; set && m < nm; ++m) {
+    if (set[m] < 0 || set[m] > made)
+      return fail(e, GREB_E_INVALID, who + ("member " + std::to_string(m)) + ": set " + std::to_string(set[m]) + " is outside 0 ... " +
+                                         std::to_string(made) + " (add_boundary_set made " + std::to_string(made) + ")");
+    bs[m] = set[m];
+    on_sets += bs[m] > 0;
+    uniform = uniform && bs[m] == bs[0];
+  }
+  // the transport kernels of the any-grid engine run all members of a launch with one W2 and one wind slice
+  for (size_t m = 0; !e->fused && m < nm; ++m) {
+    const unsigned t = e->bound[(size_t)bs[m]].over & ((1u << kBfZtopo) | (1u << kBfUclim) | (1u << kBfVclim));
+    if (t)
+      return fail(e, GREB_E_UNSUPPORTED,
+                  who + ("member " + std::to_string(m)) + ": set " + std::to_string(bs[m]) + " overrides " +
+                      kBoundaryNames[(t & (1u << kBfZtopo)) ? kBfZtopo : ((t & (1u << kBfUclim)) ? kBfUclim : kBfVclim)] +
+                      ", which the any-grid engine (latitude bands, row strips) transports all members of a launch with -- create an "
+                      "engine with those fields or run the groups beside each other (ensemble.run_beside)");
+  }
+  HIP_TRY(e, hipSetDevice(e->device));
+  // Everything that can fail is done on NEW buffers; the engine changes only once they are complete.
+  int* bset_dev = nullptr;
+  MemberForcing* neutral = nullptr;
+  float *corr = nullptr, *state = nullptr;
+  auto step = [&](hipError_t err, const char* what) -> int {
+    if (err == hipSuccess) return 0;
+    if (bset_dev) (void)hipFree(bset_dev);
+    if (neutral) (void)hipFree(neutral);
+    if (corr) (void)hipFree(corr);
+    if (state) (void)hipFree(state);
+    return fail(e, (int)err, std::string(who) + what + ": " + hipGetErrorString(err));
+  };
+  if (on_sets > 0) {
+    if (int rc = step(dev_alloc(&bset_dev, nm), "hipMalloc")) return rc;
+    if (int rc = step(hipMemcpy(bset_dev, bs.data(), nm * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy")) return rc;
+    if (!e->neutral_force_dev) {
+      const std::vector<MemberForcing> w(nm, MemberForcing{-1, 1.f, -1, 1.f});
+      if (int rc = step(dev_alloc(&neutral, nm), "hipMalloc")) return rc;
+      if (int rc = step(hipMemcpy(neutral, w.data(), nm * sizeof(MemberForcing), hipMemcpyHostToDevice), "hipMemcpy")) return rc;
+    }
+  }
+  if (flags & GREB_BS_REINIT) { // every member's state: the initial state of its set (:190-197) under its own physics
+    std::vector<float> st(5 * np);
+    if (int rc = step(dev_alloc(&state, nm * 5 * np), "hipMalloc of the members' states")) return rc;
+    for (size_t m = 0; m < nm; ++m) {
+      initial_state(e->bound[(size_t)bs[m]], e->h_phys[m], np, st.data());
+      if (int rc = step(hipMemcpy(state + m * 5 * np, st.data(), 5 * np * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy")) return rc;
+    }
+  }
+  if (int rc = step(hipStreamSynchronize(e->stream), "hipStreamSynchronize")) return rc; // nothing in flight reads what is replaced
+  if (!uniform && e->shared_corr && nm > 1) { // members whose sets differ need a correction set each
+    const char* what = "";
+    const hipError_t err = copy_shared_corrections(e, &corr, &what);
+    if (int rc = step(err, what)) return rc;
+    if (int rc = step(adopt_member_corrections(e, corr), "hipMemcpy")) return rc;
+  }
+  if (state) { (void)hipFree(e->state); e->state = state; }
+  if (neutral) e->neutral_force_dev = neutral;
+  if (bset_dev) {
+    if (e->bset_dev) (void)hipFree(e->bset_dev);
+    e->bset_dev = bset_dev;
+  }
+  if (set) e->h_bset = bs; else e->h_bset.clear();
+  e->members_on_sets = on_sets;
   return 0;
 }
 

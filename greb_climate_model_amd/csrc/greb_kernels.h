@@ -38,6 +38,18 @@ struct MemberForcing {
   float solar_scale; // multiplies the table
 };
 
+// One boundary set (greb_engine_add_boundary_set) as the kernels read it: the nine input fields of greb_fields that a set
+// may replace and the four derived from them, each pointer either the set's own array or the engine's.  Entry 0 of the
+// table is the engine's own data.
+struct BoundarySet {
+  const float *z_topo, *glacier;
+  const float *tclim, *qclim, *uclim, *vclim, *mldclim, *cldclim, *swetclim;
+  const float *toclim, *z_ocean, *wz_air, *wz_vapor;
+};
+constexpr int kBoundaryFields = 13; // pointers of a BoundarySet; the first kBoundaryInputs are inputs, the rest derived
+constexpr int kBoundaryInputs = 9;
+constexpr int kMaxBoundarySets = 16;
+
 // Everything the fused member kernel needs (passed by value as a kernel argument).
 struct MemberArgs {
   int nx, ny, np;
@@ -88,6 +100,10 @@ struct MemberArgs {
   const float* f_space;         // [n_patterns][np]  CO2 weights in [0, 1]
   const float* f_season;        // [n_patterns][730] their seasonal factor (all ones where the caller gave none)
   const float* f_solar;         // [n_solar][730][ny] insolation tables
+  // boundary sets (read by the BOUND instantiations only, which a launch takes when bset_m is set; both phases:
+  // greb_physics_step.h, member_boundary).  Appended likewise.
+  const BoundarySet* bsets;     // [1 + sets made]; entry 0 holds the thirteen pointers above
+  const int* bset_m;            // [nm] each member's set; null: every member of the launch is on the engine's own data
 };
 
 // GREB_NBUDGET, GREB_B_*: the flux terms of one step in the order of include/greb_engine.h

@@ -900,7 +900,11 @@ hipError_t launch_circulation_g96(const float* X, const float* wz, const float* 
 // FORCE (scenario phase, with EXP: a launch with any forced member, greb_engine_set_member_forcing): the member's CO2 pattern,
 // insolation table and scale act in the point physics (greb_physics_step.h: member_force).  Its words are read anew every
 // model step, into scalar registers, so that nothing of it lives across the sub-steps.  No other instantiation contains it.
-template <bool STRICT, bool FLUX, bool EXP, bool BUDGET = false, bool FORCE = false>
+// BOUND (both phases, with EXP and -- in the scenario phase -- FORCE: a launch in which any member names a boundary set,
+// greb_engine_set_member_boundary): the thirteen boundary fields are those of the member's set.  Only the set index, one
+// scalar register, lives across the sub-steps: the pointers are fetched from the set table where they are used
+// (greb_physics_step.h: member_boundary), as the other instantiations fetch theirs from the kernel arguments.
+template <bool STRICT, bool FLUX, bool EXP, bool BUDGET = false, bool FORCE = false, bool BOUND = false>
 __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
   extern __shared__ __align__(16) float lds_raw[];
   lfloat* lds = (lfloat*)lds_raw;
@@ -916,7 +920,11 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
   for (int i = 0; i < (a.dbg >> 8) * (m & 7); ++i) __builtin_amdgcn_s_sleep(16);
 #endif
   Circ<STRICT> circ;
-  circ.init(lds, a.wz_air, a.wz_vapor, tab);
+  const int bset = member_bset<BOUND>(a, m);
+  {
+    const BoundPtr B = member_boundary<BOUND>(a, bset);
+    circ.init(lds, BOUND ? (const float*)B->wz_air : a.wz_air, BOUND ? (const float*)B->wz_vapor : a.wz_vapor, tab);
+  }
   for (int i = tid; i < NP / 4; i += kThreads)
     st8(lds + kOffX + (i / NQ) * RS, i % NQ, zip(ld4(state + NP + 4 * i), ld4(state + 3 * NP + 4 * i))); // (Tair, q)
   int cur = 0;
@@ -945,7 +953,11 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
     const size_t off = ck.off;
 
     GREB_STAMP(t_a);
-    stage_winds<STRICT, EXP && !STRICT>(lds, a.uclim + off, a.vclim + off, tab);
+    {
+      const BoundPtr B = member_boundary<BOUND>(a, bset);
+      stage_winds<STRICT, EXP && !STRICT>(lds, (BOUND ? (const float*)B->uclim : a.uclim) + off,
+                                          (BOUND ? (const float*)B->vclim : a.vclim) + off, tab);
+    }
     __syncthreads();
     GREB_STAMP(t_b);
 
@@ -962,6 +974,7 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
     const Phys P = a.phys[m];
     const float co2 = FLUX ? co2_flux : a.co2[(size_t)m * a.co2_stride + a.co2_year0 + yr_rel]; // :924
     const MemberForce mf = member_force<FORCE>(a, m, ck);
+    const BoundPtr B = member_boundary<BOUND>(a, bset);
     lfloat* Xf = lds + kOffX + cur * XB;       // the tracers after the 24 sub-steps
     lfloat* red = lds + kOffX + (cur ^ 1) * XB; // idle buffer: annual-mean reduction scratch
     // Each thread takes whole quads (4 consecutive longitudes): every load/store of the ~26
@@ -990,7 +1003,7 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 #pragma unroll 1
       for (int qd = tid; qd < NP / 4; qd += kThreads) {
         const q8 xpair = ld8(Xf + (qd / NQ) * RS, qd % NQ);
-        const PhysIn in = physics_load<FLUX, EXP, FORCE>(a, qd, ck, state, acc, corr, xsw, mf);
+        const PhysIn in = physics_load<FLUX, EXP, FORCE, BOUND>(a, qd, ck, state, acc, corr, xsw, mf, B);
         (void)physics_compute<STRICT, FLUX, EXP, true, FORCE>(a, P, in, co2, comp(xpair, 0), comp(xpair, 1), xsw, bs, 4 * qd, mf);
       }
     }
@@ -1001,7 +1014,7 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 #endif
       const q8 xpair = ld8(Xf + (qd / NQ) * RS, qd % NQ);
       f4 oTa, oq, tsm;
-      physics_quad<STRICT, FLUX, EXP, false, FORCE>(a, P, m, qd, ck, co2, state, acc, corr, comp(xpair, 0), comp(xpair, 1), oTa, oq, tsm, xsw, mf);
+      physics_quad<STRICT, FLUX, EXP, false, FORCE, BOUND>(a, P, m, qd, ck, co2, state, acc, corr, comp(xpair, 0), comp(xpair, 1), oTa, oq, tsm, xsw, mf, B);
       st8(Xf + (qd / NQ) * RS, qd % NQ, zip(oTa, oq));
       if (ityr == kNT) st4(red + 4 * qd, tsm);
     }
@@ -1056,7 +1069,13 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 hipError_t launch_member_kernel(const MemberArgs& a, int n_members, bool strict, hipStream_t s) {
   if (a.nx != NX || a.ny != NY) return hipErrorInvalidValue;
   void (*kern)(MemberArgs);
-  if (a.force_m) { // a forced member (scenario phase only): every member of the launch takes the forcing-aware instantiation
+  if (a.bset_m) { // a member on a boundary set: every member of the launch takes the boundary-aware instantiation, which is
+                  // switch-aware and, in the scenario phase, forcing-aware (the engine passes neutral forcing words)
+    if (!a.bsets || (!a.flux_phase && !a.force_m) || (a.bsum && (a.flux_phase || !a.brec))) return hipErrorInvalidValue;
+    if (a.flux_phase) kern = strict ? member_kernel<true, true, true, false, false, true> : member_kernel<false, true, true, false, false, true>;
+    else if (a.bsum) kern = strict ? member_kernel<true, false, true, true, true, true> : member_kernel<false, false, true, true, true, true>;
+    else kern = strict ? member_kernel<true, false, true, false, true, true> : member_kernel<false, false, true, false, true, true>;
+  } else if (a.force_m) { // a forced member (scenario phase only): every member of the launch takes the forcing-aware instantiation
     if (a.flux_phase || (a.bsum && !a.brec)) return hipErrorInvalidValue;
     if (a.bsum) kern = strict ? member_kernel<true, false, true, true, true> : member_kernel<false, false, true, true, true>;
     else kern = strict ? member_kernel<true, false, true, false, true> : member_kernel<false, false, true, false, true>;

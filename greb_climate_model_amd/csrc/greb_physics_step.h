@@ -70,6 +70,28 @@ __device__ __forceinline__ float forced_co2(const MemberForce& f, float w_space,
   return part + rest;
 }
 
+// Boundary sets (BOUND instantiations, both phases; greb_engine_set_member_boundary): the member's entry of the set table.
+// The set index is block-uniform and read once into a scalar register; the entry's pointers are fetched where they are
+// used, by scalar loads through a constant-address-space pointer -- as the default kernels fetch theirs from the kernel
+// arguments -- so that none of the thirteen lives across the circulation sub-steps.  member_boundary makes the entry's
+// address opaque at every call: loads through it stay behind the call.
+typedef const BoundarySet __attribute__((address_space(4)))* BoundPtr;
+template <bool BOUND>
+__device__ __forceinline__ int member_bset(const MemberArgs& a, int m) {
+  return BOUND ? __builtin_amdgcn_readfirstlane(a.bset_m[m]) : 0;
+}
+template <bool BOUND>
+__device__ __forceinline__ BoundPtr member_boundary(const MemberArgs& a, int bset) {
+  unsigned long long p = 0;
+  if (BOUND) {
+    p = (unsigned long long)(a.bsets + bset);
+    asm volatile("" : "+s"(p));
+  }
+  return (BoundPtr)p;
+}
+// field `f` of the member's set, or the launch's own
+#define GREB_BF(f) (BOUND ? (const float*)B->f : a.f)
+
 // One quad in three pieces -- load, compute, store -- so that a caller with several quads per thread can request the
 // next quad's operands BETWEEN the arithmetic of the current one and its stores (vector-memory operations retire in
 // order: loads issued behind a quad's stores wait for those stores as well).
@@ -90,26 +112,27 @@ struct PhysOut { // everything the stores need: the inputs are dead once this ex
   f4 s0, s1, s2, s3, s4; // the monthly sums including this step (:974)
 };
 
-template <bool FLUX, bool EXP, bool FORCE = false>
+template <bool FLUX, bool EXP, bool FORCE = false, bool BOUND = false>
 __device__ __forceinline__ PhysIn physics_load(const MemberArgs& a, int qd, const StepClock& ck, const float* __restrict__ state,
                                                const float* __restrict__ acc, const float* __restrict__ corr, unsigned xsw_member,
-                                               const MemberForce& F = MemberForce{}) {
+                                               const MemberForce& F = MemberForce{}, BoundPtr B = BoundPtr{}) {
   static_assert(!FORCE || (EXP && !FLUX), "forcing: scenario phase, switch-aware instantiations only");
+  static_assert(!BOUND || (EXP && (FLUX || FORCE)), "boundary sets: switch-aware, and in the scenario phase forcing-aware, instantiations only");
   const int nx = a.nx, ny = a.ny, np = a.np, p0 = 4 * qd;
   const size_t off = ck.off, offm = ck.offm;
   const unsigned xsw = EXP ? xsw_member : 0u;
   PhysIn i;
   i.Ts = ld4(state + p0); i.Ta = ld4(state + np + p0); i.To = ld4(state + 2 * np + p0); i.q = ld4(state + 3 * np + p0);
   i.cap = ld4(state + 4 * np + p0);
-  i.zt = ld4(a.z_topo + p0); i.gl = ld4(a.glacier + p0); i.zo = ld4(a.z_ocean + p0); i.ez = ld4(a.wz_air + p0);
-  i.tcl = ld4(a.tclim + off + p0); i.cld = ld4(a.cldclim + off + p0); i.mld = ld4(a.mldclim + off + p0);
-  i.mldm = ld4(a.mldclim + offm + p0); i.swet = ld4(a.swetclim + off + p0); i.u = ld4(a.uclim + off + p0);
-  i.v = ld4(a.vclim + off + p0);
+  i.zt = ld4(GREB_BF(z_topo) + p0); i.gl = ld4(GREB_BF(glacier) + p0); i.zo = ld4(GREB_BF(z_ocean) + p0); i.ez = ld4(GREB_BF(wz_air) + p0);
+  i.tcl = ld4(GREB_BF(tclim) + off + p0); i.cld = ld4(GREB_BF(cldclim) + off + p0); i.mld = ld4(GREB_BF(mldclim) + off + p0);
+  i.mldm = ld4(GREB_BF(mldclim) + offm + p0); i.swet = ld4(GREB_BF(swetclim) + off + p0); i.u = ld4(GREB_BF(uclim) + off + p0);
+  i.v = ld4(GREB_BF(vclim) + off + p0);
   if (FORCE) {
 #pragma clang fp contract(off)
     i.solar = F.solar[(size_t)(ck.ityr - 1) * ny + p0 / nx] * F.scale; // one rounding, then sw = solar * (1 - albedo)
   } else i.solar = a.sw_solar[(size_t)(ck.ityr - 1) * ny + p0 / nx]; // a quad never straddles rows
-  if (FLUX) { i.c0 = ld4(a.toclim + p0); i.c1 = ld4(a.qclim + off + p0); i.c2 = zero4(); }
+  if (FLUX) { i.c0 = ld4(GREB_BF(toclim) + p0); i.c1 = ld4(GREB_BF(qclim) + off + p0); i.c2 = zero4(); }
   else { i.c0 = ld4(corr + off + p0); i.c1 = ld4(corr + (size_t)kNT * np + off + p0); i.c2 = ld4(corr + (size_t)2 * kNT * np + off + p0); }
   i.acc0 = i.acc1 = i.acc2 = i.acc3 = i.acc4 = zero4();
 #ifdef GREB_TUNING
@@ -123,8 +146,8 @@ __device__ __forceinline__ PhysIn physics_load(const MemberArgs& a, int qd, cons
     i.acc4 = ld4(acc + 4 * np + p0);
   }
   i.qcl = zero4(); i.tclp = zero4(); // experiments only: qclim(ityr) for the linear emissivity, Tclim of the previous step
-  if (EXP && (xsw & kXLwLinear)) i.qcl = FLUX ? i.c1 : ld4(a.qclim + off + p0);
-  if (EXP && !FLUX && (xsw & kXSstPlus1)) i.tclp = ld4(a.tclim + offm + p0);
+  if (EXP && (xsw & kXLwLinear)) i.qcl = FLUX ? i.c1 : ld4(GREB_BF(qclim) + off + p0);
+  if (EXP && !FLUX && (xsw & kXSstPlus1)) i.tclp = ld4(GREB_BF(tclim) + offm + p0);
   i.fw = zero4();
   if (FORCE && F.space) i.fw = ld4(F.space + p0);
   return i;
@@ -294,15 +317,17 @@ __device__ __forceinline__ void physics_store(const MemberArgs& a, int m, int qd
 }
 
 // the three pieces in a row (one quad per thread: the any-grid engine)
-template <bool STRICT, bool FLUX, bool EXP = false, bool BUDGET = false, bool FORCE = false>
+template <bool STRICT, bool FLUX, bool EXP = false, bool BUDGET = false, bool FORCE = false, bool BOUND = false>
 __device__ __forceinline__ void physics_quad(const MemberArgs& a, const Phys& P, int m, int qd, const StepClock& ck,
                                              float co2, float* __restrict__ state, float* __restrict__ acc,
                                              float* __restrict__ corr, const f4& xTa, const f4& xq, f4& oTa_out,
-                                             f4& oq_out, f4& tsmn_mean, unsigned xsw = 0u, const MemberForce& F = MemberForce{}) {
-  const PhysIn in = physics_load<FLUX, EXP, FORCE>(a, qd, ck, state, acc, corr, xsw, F);
+                                             f4& oq_out, f4& tsmn_mean, unsigned xsw = 0u, const MemberForce& F = MemberForce{},
+                                             BoundPtr B = BoundPtr{}) {
+  const PhysIn in = physics_load<FLUX, EXP, FORCE, BOUND>(a, qd, ck, state, acc, corr, xsw, F, B);
   const PhysOut o = physics_compute<STRICT, FLUX, EXP, BUDGET, FORCE>(a, P, in, co2, xTa, xq, xsw, budget_sink<BUDGET>(a, m, ck), 4 * qd, F);
   physics_store<FLUX>(a, m, qd, ck, o, state, acc, corr, tsmn_mean);
   oTa_out = o.Ta; oq_out = o.q;
 }
+#undef GREB_BF
 
 } // namespace greb

@@ -58,7 +58,8 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_substep_launch_order", "greb_circulation_launch_plan", "greb_engine_describe",
            "greb_engine_create_members", "greb_engine_set_member_experiments", "greb_diag_create", "greb_diag_destroy",
            "greb_diag_reduce_dev", "greb_engine_run_diag", "greb_engine_run_budget", "greb_budget_name",
-           "greb_member_deal_cover", "greb_engine_set_forcing_tables", "greb_engine_set_member_forcing"]
+           "greb_member_deal_cover", "greb_engine_set_forcing_tables", "greb_engine_set_member_forcing",
+           "greb_engine_add_boundary_set", "greb_engine_set_member_boundary"]
 
 
 def _check(rc: int, h=None):
@@ -111,6 +112,31 @@ def member_configs(params: abi.GrebParams, members):
             else:
                 raise GrebError(-1, f"members: unknown key {k!r}")
     return arr
+
+
+def boundary_fields(nx: int, ny: int, fields: dict) -> dict:
+    """The keyword arguments of Engine.add_boundary_set, checked: names are those of greb_fields that a boundary set may
+    replace (abi.BOUNDARY_FIELDS), arrays real-valued with shape [ny][nx] (z_topo, glacier) or [730][ny][nx]; returns
+    them as C-contiguous float32.  None values are dropped (inherit)."""
+    out = {}
+    for name, x in fields.items():
+        if name == "sw_solar":
+            raise GrebError(-1, "add_boundary_set: sw_solar is not part of a boundary set: insolation tables are per-member "
+                                "forcing (set_forcing_tables, set_member_forcing)")
+        if name not in abi.BOUNDARY_FIELDS:
+            raise GrebError(-1, f"add_boundary_set: unknown field {name!r} (one of {', '.join(abi.BOUNDARY_FIELDS)})")
+        if x is None:
+            continue
+        x = np.asarray(x)
+        if x.dtype.kind not in "fiu":
+            raise GrebError(-1, f"add_boundary_set: {name} has dtype {x.dtype}, expected real numbers (float32)")
+        want = (ny, nx) if abi.BOUNDARY_FIELDS[name] == 2 else (abi.NSTEP_YR, ny, nx)
+        if x.shape != want:
+            raise GrebError(-1, f"add_boundary_set: {name} has shape {x.shape}, expected {list(want)}")
+        out[name] = np.ascontiguousarray(x, np.float32)
+    if not out:
+        raise GrebError(-1, "add_boundary_set: no field given: the set would be the engine's own data (set 0)")
+    return out
 
 
 def params_default() -> abi.GrebParams:
@@ -314,6 +340,32 @@ class Engine:
             if d:
                 raise GrebError(-1, f"set_member_forcing: unknown key {sorted(d)[0]!r}")
         _check(lib().greb_engine_set_member_forcing(self.h, arr), self.h)
+
+    def add_boundary_set(self, **fields) -> int:
+        """A boundary set (greb_engine_add_boundary_set): the given fields -- keyword names as in greb_fields, arrays
+        [ny][nx] (z_topo, glacier) or [730][ny][nx] -- replace the engine's own for the members that name the set; the
+        others are inherited.  Returns the set's id, 1 ... abi.MAX_BOUNDARY_SETS (0 is the engine's own data)."""
+        arrs = boundary_fields(self.nx, self.ny, fields)
+        f = abi.GrebFields()
+        for name, x in arrs.items():
+            setattr(f, name, abi.fptr(x))
+        sid = C.c_int(0)
+        _check(lib().greb_engine_add_boundary_set(self.h, C.byref(f), C.byref(sid)), self.h)
+        return int(sid.value)
+
+    def set_member_boundary(self, sets, reinit: bool = False):
+        """One set id per member (greb_engine_set_member_boundary; 0 = the engine's own data, None = every member 0),
+        from the next flux_correction / run call.  reinit: every member also starts from the initial state of its set
+        (call it before flux_correction); without it the state stays -- spin up under the control data, then change a
+        member's boundary data.  Members whose sets differ each get their own flux-correction set."""
+        flags = abi.BS_REINIT if reinit else 0
+        if sets is None:
+            _check(lib().greb_engine_set_member_boundary(self.h, None, C.c_uint(flags)), self.h)
+            return
+        ids = np.ascontiguousarray(sets, np.int32)
+        if ids.shape != (self.nm,):
+            raise GrebError(-1, f"set_member_boundary: {self.nm} set ids expected")
+        _check(lib().greb_engine_set_member_boundary(self.h, ids.ctypes.data_as(C.POINTER(C.c_int32)), C.c_uint(flags)), self.h)
 
     def point_physics(self, ityr: int, co2: float, in5) -> np.ndarray:
         in5 = np.ascontiguousarray(in5, np.float32)

@@ -267,13 +267,46 @@ typedef struct greb_member_forcing {
  * A member is forced when it names a pattern or a table or its scale is not 1 (greb_engine_describe: "forcing"). */
 int greb_engine_set_member_forcing(greb_engine* e, const greb_member_forcing* f);
 
+/* ---- boundary sets: members of one engine on different boundary data --------------------------------
+ * Members of one engine may differ in the boundary fields themselves: a changed cloud, wind, soil-moisture or vapour
+ * climatology, a removed ice sheet, flat topography, a constant mixed layer -- each beside an unchanged control member.
+ * A boundary set replaces some of the engine's fields; a member names one set (0 = the engine's own data).  Only the
+ * replaced fields are copied to the device, the others alias the engine's.  The derived fields follow their source as
+ * greb_engine_create makes them: wz_air / wz_vapor where z_topo is replaced, Toclim where tclim is, z_ocean where mldclim
+ * is.  Both phases: a member integrates its flux corrections towards its own set's tclim, qclim and Toclim, and
+ * GREB_X_SST_PLUS1 / GREB_X_LW_LINEAR_VAPOR read the member's set.  sw_solar is not part of a set (per-member insolation is
+ * forcing: greb_engine_set_forcing_tables); a non-NULL over->sw_solar is GREB_E_INVALID.
+ * A launch in which any member names a set above 0 takes boundary-aware instantiations of the kernels for all its members;
+ * with every member on set 0 the engine launches exactly the kernels it launches without any of this.
+ * On the any-grid engine (latitude bands, row strips) the transport kernels run all members of a launch with one pair of
+ * weights and one wind slice: a member that names a set which replaces z_topo, uclim or vclim is GREB_E_UNSUPPORTED there
+ * (create an engine with those fields, or ensemble.run_beside); sets of glacier, tclim, qclim, mldclim, cldclim, swetclim
+ * work on every engine.
+ * GREB_E_INVALID, with a message that names the offender: `over` NULL or all-NULL, more than GREB_MAX_BOUNDARY_SETS sets,
+ * a value that is not finite (field and index of the first), a set index outside 0 ... sets made, unknown flag bits.
+ * A failed call of either function leaves the engine exactly as it was (and consumes no set id). */
+#define GREB_MAX_BOUNDARY_SETS 16
+/* over: a greb_fields whose non-NULL pointers replace the engine's own field of that name for the members that name
+ * this set; NULL = inherit.  Shapes as in greb_engine_create.  *set_id = 1 .. GREB_MAX_BOUNDARY_SETS (0 is the
+ * engine's own data). */
+int greb_engine_add_boundary_set(greb_engine* e, const greb_fields* over, int* set_id);
+/* also set each member's state to the initial state of its set (src/greb.f90:190-197): Ts = Ta = tclim[729], To = Toclim,
+ * q = qclim[729], cap_surf from the set's z_topo / mldclim[0] and the member's own physics.  The deconstruction use: call
+ * it before flux_correction.  Without it the state is untouched -- the response use: spin up under the control data, then
+ * change a member's clouds. */
+#define GREB_BS_REINIT 1u
+/* set[n_members], 0 = the engine's own; NULL = every member 0.  Takes effect from the next flux_correction / run call.
+ * Members whose sets differ need a flux-correction set each: an engine that shared one gives every member a copy, as
+ * greb_engine_set_member_experiments does; members that all name the same set keep sharing one. */
+int greb_engine_set_member_boundary(greb_engine* e, const int32_t* set, unsigned flags);
+
 /* ---- sensitivity-experiment switches -----------------------------------------
  * Runtime switches on the same kernels that reproduce the `log_exp` experiments of the upstream model
  * variant (src/greb.original.model.f90:60,162-166,394,423-430,452-453,492-495,513-515,553-571; doc in its
  * namelist_original).  greb_log_exp_switches() maps a log_exp value to the process switches below; the
- * experiment's changes to the BOUNDARY DATA (constant topography / clouds / vapour / mixed layer, :162-166),
- * its CO2 series (A1B ramp, :939-951) and the run sequencing (control run, :208-215) stay with the host
- * (greb_climate_model_amd/original.py shows them).  Default 0 = the complete model = src/greb.f90. */
+ * experiment's changes to the BOUNDARY DATA (constant topography / clouds / vapour / mixed layer, :162-166) are a boundary
+ * set (above) or an engine created on the changed fields; its CO2 series (A1B ramp, :939-951) and the run sequencing
+ * (control run, :208-215) stay with the host (greb_climate_model_amd/original.py shows all three).  Default 0 = the complete model = src/greb.f90. */
 #define GREB_X_NO_ICE            (1u << 0) /* log_exp <= 5: a_surf = a_no_ice (:394); heat capacity ignores sea ice (:492-495) */
 #define GREB_X_NO_HYDRO          (1u << 1) /* <= 6, 13, 15: no latent heat, evaporation, rain (:452-453) */
 #define GREB_X_NO_DEEP_OCEAN     (1u << 2) /* <= 9, 11, 14-16: dT_ocean = dTo = 0 (:513-515) */
