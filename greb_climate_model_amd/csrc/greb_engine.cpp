@@ -238,6 +238,21 @@ void apply_forcing(const greb_engine* e, MemberArgs& a) {
   a.f_space = e->f_space; a.f_season = e->f_season; a.f_solar = e->f_solar;
 }
 
+// Scenario year y of a run of `years` (greb_engine_run, _run_budget, _run_diag): its five records go to year mon_y of
+// mon_years in `mon` and, where the run has a budget, its budget records to year bud_y of bud_years in `bud`.
+MemberArgs scenario_args(greb_engine* e, int years, int y, float* mon, int mon_years, int mon_y, float* bud = nullptr,
+                         int bud_years = 0, int bud_y = 0) {
+  MemberArgs a = base_args(e);
+  a.flux_phase = 0;
+  a.it0 = e->it_scnr + 1 + (long long)y * kNT; a.nsteps = kNT;
+  a.co2 = e->co2_dev; a.co2_stride = years; a.co2_year0 = y;
+  a.monthly = mon; a.monthly_years = mon_years; a.year_out0 = mon_y;
+  a.yearly = e->yearly_dev; a.yearly_years = years; a.yearly_year0 = y;
+  if (bud) { a.bsum = e->bsum; a.brec = bud; a.brec_years = bud_years; a.brec_year0 = bud_y; }
+  apply_forcing(e, a);
+  return a;
+}
+
 bool is_forced(const greb_member_forcing& f) { return f.co2_pattern >= 0 || f.solar_table >= 0 || !(f.solar_scale == 1.f); }
 
 // vapour diffused but not advected (GREB_X_VAPOR_DIFFUSION_ONLY): on the any-grid engine a property of the launch, so
@@ -712,24 +727,12 @@ int run_scenario(greb_engine* e, int years, const float* co2_ppm, float* monthly
   if (int rc = ensure(e, &e->yearly_dev, &e->yearly_cap, nm * years * 2)) return rc;
   HIP_TRY(e, hipMemsetAsync(e->yearly_dev, 0, nm * years * 2 * sizeof(float), e->stream));
   const size_t slot = nm * rec_year, bslot = nm * bud_year;
-  // scenario year y of this call: its records go to year mon_y of mon_years in `mon`, and bud_y of bud_years in `bud`
-  auto year_args = [&](int y, float* mon, int mon_years, int mon_y, float* bud, int bud_years, int bud_y) {
-    MemberArgs a = base_args(e);
-    a.flux_phase = 0;
-    a.it0 = e->it_scnr + 1 + (long long)y * kNT; a.nsteps = kNT;
-    a.co2 = e->co2_dev; a.co2_stride = years; a.co2_year0 = y;
-    a.monthly = mon; a.monthly_years = mon_years; a.year_out0 = mon_y;
-    a.yearly = e->yearly_dev; a.yearly_years = years; a.yearly_year0 = y;
-    if (budget) { a.bsum = e->bsum; a.brec = bud; a.brec_years = bud_years; a.brec_year0 = bud_y; }
-    apply_forcing(e, a);
-    return a;
-  };
   if (dev_out) {
     // (a budget-only run: the kernels write their five records regardless -- into one staging slot nobody reads)
     if (!monthly) if (int rc = ensure(e, &e->monthly_dev, &e->monthly_cap, slot)) return rc;
     for (int y = 0; y < years; ++y) {
-      const MemberArgs a = monthly ? year_args(y, monthly, years, y, budget, years, y)
-                                   : year_args(y, e->monthly_dev, 1, 0, budget, years, y);
+      const MemberArgs a = monthly ? scenario_args(e, years, y, monthly, years, y, budget, years, y)
+                                   : scenario_args(e, years, y, e->monthly_dev, 1, 0, budget, years, y);
       if (int rc = run_year(e, a, e->nm)) return rc;
     }
   } else {
@@ -766,8 +769,8 @@ int run_scenario(greb_engine* e, int years, const float* co2_ppm, float* monthly
     for (int y = 0; y < years; ++y) {
       const int sl = y & 1;
       if (y >= 2) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_free[sl], 0)); // slot's previous year has left
-      const MemberArgs a = year_args(y, e->monthly_dev + (size_t)sl * slot, 1, 0,
-                                     budget ? e->budget_dev + (size_t)sl * bslot : nullptr, 1, 0);
+      const MemberArgs a = scenario_args(e, years, y, e->monthly_dev + (size_t)sl * slot, 1, 0,
+                                         budget ? e->budget_dev + (size_t)sl * bslot : nullptr, 1, 0);
       if (int rc = run_year(e, a, e->nm)) return rc;
       HIP_TRY(e, hipEventRecord(e->ev_done[sl], e->stream));
       if (y > 0) if (int rc = deliver(y - 1)) return rc;
@@ -1095,13 +1098,7 @@ int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_d
   const int rc_years = [&]() -> int {
     for (int y = 0; y < years; ++y) {
       const int sl = y & 1;
-      MemberArgs a = base_args(e);
-      a.flux_phase = 0;
-      a.it0 = e->it_scnr + 1 + (long long)y * kNT; a.nsteps = kNT;
-      a.co2 = e->co2_dev; a.co2_stride = years; a.co2_year0 = y;
-      a.monthly = e->monthly_dev + (size_t)sl * slot; a.monthly_years = 1; a.year_out0 = 0;
-      a.yearly = e->yearly_dev; a.yearly_years = years; a.yearly_year0 = y;
-      apply_forcing(e, a);
+      const MemberArgs a = scenario_args(e, years, y, e->monthly_dev + (size_t)sl * slot, 1, 0);
       if (int rc = run_year(e, a, e->nm)) return rc;
       if (y >= 2) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_free[sl], 0)); // the slot's products of year y - 2 have left
       float* out = out_slot ? e->diag_out + (size_t)sl * out_slot : nullptr;
@@ -1155,12 +1152,13 @@ const char* greb_engine_describe(greb_engine* e) {
   }
   s += "]}";
   { // the kernel family the next launch of each phase takes (budget output is chosen per call, on top of it)
-    bool any_x = false;
-    for (unsigned x : e->h_xsw) any_x = any_x || x != 0;
-    const char* sw = any_x || !e->xsw_uniform ? "switches" : "default";
-    std::snprintf(buf, sizeof(buf), ", \"kernel_family\": {\"flux_correction\": \"%s\", \"scenario\": \"%s\"}",
-                  e->members_on_sets > 0 ? "boundary" : sw,
-                  e->members_on_sets > 0 ? "boundary" : (e->forced_members > 0 ? "forcing" : sw));
+    unsigned v;
+    auto family = [&v](const MemberArgs& a) { return select_variant(a, &v) == hipSuccess ? variant_family(v) : "none"; };
+    MemberArgs flux = base_args(e), scenario = base_args(e);
+    flux.flux_phase = 1;
+    apply_forcing(e, scenario);
+    std::snprintf(buf, sizeof(buf), ", \"kernel_family\": {\"flux_correction\": \"%s\", \"scenario\": \"%s\"}", family(flux),
+                  family(scenario));
     s += buf;
   }
   if (e->call != greb_engine::kCallNever) {
@@ -1198,6 +1196,8 @@ int greb_engine_get_corrections(greb_engine* e, int member, float* corr, float* 
   return 0;
 }
 
+static_assert(GREB_V_FLUX == kVFlux && GREB_V_SWITCHES == kVExp && GREB_V_BUDGET == kVBudget && GREB_V_FORCING == kVForce &&
+              GREB_V_BOUNDARY == kVBound, "variant bits mirror the ABI");
 static_assert(GREB_X_NO_ICE == kXNoIce && GREB_X_NO_HYDRO == kXNoHydro && GREB_X_NO_DEEP_OCEAN == kXNoDeepOcean &&
               GREB_X_LW_LINEAR_VAPOR == kXLwLinear && GREB_X_NO_CIRCULATION == kXNoCirc &&
               GREB_X_NO_VAPOR_TRANSPORT == kXNoQTransport && GREB_X_VAPOR_DIFFUSION_ONLY == kXQDiffOnly &&
@@ -1676,6 +1676,29 @@ int greb_diffusion_launch_order(const greb_params* p, int nx, int ny, int batch,
     up[i] = (tasks[i].rows & kRowsUp) != 0;
   }
   return (int)tasks.size();
+}
+
+int greb_step_variant(int flux_phase, int switches, int budget, int forced, int on_sets, unsigned* variant) {
+  if (!variant) return fail(nullptr, GREB_E_INVALID, "step_variant: bad argument");
+  static float budget_words[1];
+  static const MemberForcing force_words[1] = {};
+  static const BoundarySet sets[1] = {};
+  static const int set_of_member[1] = {};
+  MemberArgs a{}; // non-null pointers for the flags set, as the engine's launches carry them; nothing reads through them
+  a.flux_phase = flux_phase != 0;
+  a.xsw = switches ? 1u : 0u;
+  if (budget) a.bsum = a.brec = budget_words;
+  if (on_sets) { a.bsets = sets; a.bset_m = set_of_member; }
+  // a forced member, or -- scenario launches with members on sets -- the words that force nothing (apply_forcing)
+  if (forced || (on_sets && !flux_phase)) a.force_m = force_words;
+  if (select_variant(a, variant) != hipSuccess) return fail(nullptr, GREB_E_INVALID, "step_variant: no launch carries this combination");
+  return 0;
+}
+
+int greb_step_variants(unsigned* out, int capacity) {
+  if (capacity < 0 || (capacity > 0 && !out)) return fail(nullptr, GREB_E_INVALID, "step_variants: bad argument");
+  for (int i = 0; i < kNVariants && i < capacity; ++i) out[i] = kVariants[i];
+  return kNVariants;
 }
 
 int greb_member_deal_cover(int strict, int* counts) {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <utility>
 #include <vector>
 
 #include "greb_device.h"
@@ -86,21 +87,21 @@ struct MemberArgs {
   unsigned long long* stamps;
   int dbg;               // -DGREB_TUNING builds only: timing experiments (results wrong): bit 0 point physics without the
                          // accumulators, bit 1 without the state write-back, bit 2 a single pass instead of three
-  // per-member experiment control (read by the switch-aware instantiations only; greb_physics_step.h: member_switches)
+  // per-member experiment control (read by the kVExp variants only; greb_physics_step.h: member_switches)
   const unsigned* xsw_m;   // [nm] experiment switches of each member; null: xsw applies to all
   const float* co2_flux_m; // [nm] flux-phase CO2 of each member; null: co2_flux applies to all
-  // budget output (read by the BUDGET instantiations only; null otherwise: greb_physics_step.h, budget_sink)
+  // budget output (read by the kVBudget variants only; null otherwise: greb_physics_step.h, budget_sink)
   float* bsum;             // [nm][kNBudget][np] running sums of the month's flux terms
   float* brec;             // [nm][brec_years][12][kNBudget][np] monthly means of the terms
   int brec_years;          // years per member in `brec`
   int brec_year0;          // index there of the year containing it0
-  // per-member forcing (read by the FORCE instantiations only, which a launch takes when force_m is set; scenario phase
+  // per-member forcing (read by the kVForce variants only, which a launch takes when force_m is set; scenario phase
   // only: greb_physics_step.h, member_force).  Appended: the offsets of everything above are those of a build without it.
   const MemberForcing* force_m; // [nm] each member's four words; null: no member of the launch is forced
   const float* f_space;         // [n_patterns][np]  CO2 weights in [0, 1]
   const float* f_season;        // [n_patterns][730] their seasonal factor (all ones where the caller gave none)
   const float* f_solar;         // [n_solar][730][ny] insolation tables
-  // boundary sets (read by the BOUND instantiations only, which a launch takes when bset_m is set; both phases:
+  // boundary sets (read by the kVBound variants only, which a launch takes when bset_m is set; both phases:
   // greb_physics_step.h, member_boundary).  Appended likewise.
   const BoundarySet* bsets;     // [1 + sets made]; entry 0 holds the thirteen pointers above
   const int* bset_m;            // [nm] each member's set; null: every member of the launch is on the engine's own data
@@ -109,6 +110,56 @@ struct MemberArgs {
 // GREB_NBUDGET, GREB_B_*: the flux terms of one step in the order of include/greb_engine.h
 enum { kBsw, kBLWsurf, kBLWdown, kBLWabs, kBQsens, kBQlat, kBQlatAir, kBdqEva, kBdqRain, kBdTocean, kBdTo, kBdTaCrcl, kBdqCrcl, kNBudget };
 
+// ---- Variants of the step kernels.  member_kernel (greb_member.hip) and physics_step_kernel (greb_kernels.hip) are
+// templates over <bool STRICT, unsigned V>: V is a mask of the features compiled in, and a launch takes the instantiation
+// whose features its MemberArgs ask for (select_variant).  A new variant is one entry of kVariants and its branch there.
+// kVFlux: flux-correction phase (:311-364), else scenario; kVExp: honours the experiment switches (xsw, xsw_m);
+// kVBudget: budget output (bsum, brec); kVForce: per-member forcing (force_m); kVBound: boundary sets (bsets, bset_m)
+enum : unsigned { kVFlux = 1, kVExp = 2, kVBudget = 4, kVForce = 8, kVBound = 16 };
+// The flux-correction phase delivers no budget and is not forced; forcing and boundary sets exist in the switch-aware
+// kernels only; a boundary-aware scenario kernel is forcing-aware (without a forced member its launch carries words that
+// force nothing).
+constexpr bool variant_valid(unsigned v) {
+  const bool flux = v & kVFlux, exp = v & kVExp, budget = v & kVBudget, force = v & kVForce, bound = v & kVBound;
+  return v < 32u && !(budget && flux) && (!force || (exp && !flux)) && (!bound || (exp && (flux || force)));
+}
+// every variant that is built
+constexpr unsigned kVariants[] = {0u, kVFlux, kVExp, kVFlux | kVExp, kVBudget, kVExp | kVBudget, kVExp | kVForce,
+                                  kVExp | kVBudget | kVForce, kVFlux | kVExp | kVBound, kVExp | kVForce | kVBound,
+                                  kVExp | kVBudget | kVForce | kVBound};
+constexpr int kNVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
+
+// The variant a launch takes, decided by what it carries, in this order: a member on a boundary set, a forced member, budget
+// output, experiment switches (of every member or of some), the phase.  Every member of the launch runs that one kernel.
+// hipErrorInvalidValue, *v unwritten, for arguments that contradict each other.
+inline hipError_t select_variant(const MemberArgs& a, unsigned* v) {
+  const bool flux = a.flux_phase != 0, budget = a.bsum != nullptr;
+  if (budget && (flux || !a.brec)) return hipErrorInvalidValue;
+  unsigned r = (flux ? kVFlux : 0u) | (budget ? kVBudget : 0u);
+  if (a.bset_m) {
+    if (!a.bsets || (!flux && !a.force_m)) return hipErrorInvalidValue;
+    r |= kVExp | kVBound | (flux ? 0u : kVForce);
+  } else if (a.force_m) {
+    if (flux) return hipErrorInvalidValue;
+    r |= kVExp | kVForce;
+  } else if (a.xsw || a.xsw_m) r |= kVExp;
+  *v = r;
+  return hipSuccess;
+}
+// greb_engine_describe's name for it (budget output is chosen per call, on top of the family)
+inline const char* variant_family(unsigned v) {
+  return (v & kVBound) ? "boundary" : (v & kVForce) ? "forcing" : (v & kVExp) ? "switches" : "default";
+}
+// The instantiation of a kernel family for (strict, v), or null where v is not in kVariants: Family<STRICT, V>::kernel() is
+// the address of the family's kernel<STRICT, V>, and the walk compares v with the very constant it instantiates with.
+template <template <bool, unsigned> class Family, size_t... I>
+auto pick_variant(bool strict, unsigned v, std::index_sequence<I...>) {
+  decltype(Family<false, 0u>::kernel()) k = nullptr;
+  ((kVariants[I] == v ? (void)(k = strict ? Family<true, kVariants[I]>::kernel() : Family<false, kVariants[I]>::kernel()) : (void)0), ...);
+  return k;
+}
+template <template <bool, unsigned> class Family>
+auto pick_variant(bool strict, unsigned v) { return pick_variant<Family>(strict, v, std::make_index_sequence<kNVariants>{}); }
 
 // fused engine (greb_member.hip): 96x48 with the default sub-cycling layout -- rows 0-9 and 38-47
 // sub-cycled, only the two polar rows iterating; whole member resident in one CU

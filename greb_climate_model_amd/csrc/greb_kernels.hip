@@ -397,12 +397,13 @@ hipError_t launch_substep_fused(const float* X, const float* W2, const float* u,
   return launch_sweep<kChainFused>(X, W2, u, v, Xnew, tabs, nx, ny, 2 * n_members, strict, s, 2, 1, tab_index, 2, calm_vapor ? 1 : 0);
 }
 
-template <bool STRICT, bool FLUX, bool EXP, bool BUDGET = false, bool FORCE = false, bool BOUND = false>
+template <bool STRICT, unsigned V>
 // X and Xout may be the SAME buffer (run_year passes the current tracer buffer as both when the sub-step count is
 // even): every thread reads its own quad before it writes it and touches no other, so in-place is safe -- and the
 // pointers are therefore not __restrict__.
 __global__ __launch_bounds__(256) void physics_step_kernel(MemberArgs a, const float* X, float* Xout,
                                                            float* __restrict__ red) {
+  constexpr bool FLUX = V & kVFlux, EXP = V & kVExp, FORCE = V & kVForce, BOUND = V & kVBound;
   const int m = blockIdx.y, np = a.np;
   const int qd = blockIdx.x * blockDim.x + threadIdx.x;
   if (qd >= np / 4) return;
@@ -414,34 +415,22 @@ __global__ __launch_bounds__(256) void physics_step_kernel(MemberArgs a, const f
   float* corr = a.corr + (size_t)a.corr_index[m] * 3 * kNT * np;
   const f4 xTa = ld4(X + ((size_t)m * 2) * np + 4 * qd), xq = ld4(X + ((size_t)m * 2 + 1) * np + 4 * qd);
   f4 oTa, oq, tsm;
-  physics_quad<STRICT, FLUX, EXP, BUDGET, FORCE, BOUND>(a, P, m, qd, ck, co2, state, acc, corr, xTa, xq, oTa, oq, tsm, EXP ? member_switches(a, m) : 0u,
-                                                        member_force<FORCE>(a, m, ck), member_boundary<BOUND>(a, member_bset<BOUND>(a, m)));
+  physics_quad<STRICT, V>(a, P, m, qd, ck, co2, state, acc, corr, xTa, xq, oTa, oq, tsm, EXP ? member_switches(a, m) : 0u,
+                          member_force<FORCE>(a, m, ck), member_boundary<BOUND>(a, member_bset<BOUND>(a, m)));
   st4(Xout + ((size_t)m * 2) * np + 4 * qd, oTa);
   st4(Xout + ((size_t)m * 2 + 1) * np + 4 * qd, oq);
   if (ck.ityr == kNT) st4(red + (size_t)m * np + 4 * qd, tsm);
 }
 
+template <bool STRICT, unsigned V>
+struct PhysicsStepFamily { static auto kernel() { return &physics_step_kernel<STRICT, V>; } };
+
 hipError_t launch_physics_step(const MemberArgs& a, const float* X, float* Xout, float* red, int n_members,
                                bool strict, hipStream_t s) {
-  void (*kern)(MemberArgs, const float*, float*, float*);
-  if (a.bset_m) { // a member on a boundary set: the boundary-aware instantiations, for every member of the launch
-    if (!a.bsets || (!a.flux_phase && !a.force_m) || (a.bsum && (a.flux_phase || !a.brec))) return hipErrorInvalidValue;
-    if (a.flux_phase) kern = strict ? physics_step_kernel<true, true, true, false, false, true> : physics_step_kernel<false, true, true, false, false, true>;
-    else if (a.bsum) kern = strict ? physics_step_kernel<true, false, true, true, true, true> : physics_step_kernel<false, false, true, true, true, true>;
-    else kern = strict ? physics_step_kernel<true, false, true, false, true, true> : physics_step_kernel<false, false, true, false, true, true>;
-  } else if (a.force_m) { // a forced member (scenario phase only): the forcing-aware instantiations, for every member of the launch
-    if (a.flux_phase || (a.bsum && !a.brec)) return hipErrorInvalidValue;
-    if (a.bsum) kern = strict ? physics_step_kernel<true, false, true, true, true> : physics_step_kernel<false, false, true, true, true>;
-    else kern = strict ? physics_step_kernel<true, false, true, false, true> : physics_step_kernel<false, false, true, false, true>;
-  } else if (a.bsum) { // budget output (scenario phase only)
-    if (a.flux_phase || !a.brec) return hipErrorInvalidValue;
-    if (a.xsw || a.xsw_m) kern = strict ? physics_step_kernel<true, false, true, true> : physics_step_kernel<false, false, true, true>;
-    else kern = strict ? physics_step_kernel<true, false, false, true> : physics_step_kernel<false, false, false, true>;
-  } else if (a.xsw || a.xsw_m) {
-    if (a.flux_phase) kern = strict ? physics_step_kernel<true, true, true> : physics_step_kernel<false, true, true>;
-    else kern = strict ? physics_step_kernel<true, false, true> : physics_step_kernel<false, false, true>;
-  } else if (a.flux_phase) kern = strict ? physics_step_kernel<true, true, false> : physics_step_kernel<false, true, false>;
-  else kern = strict ? physics_step_kernel<true, false, false> : physics_step_kernel<false, false, false>;
+  unsigned v;
+  if (hipError_t e = select_variant(a, &v); e != hipSuccess) return e;
+  const auto kern = pick_variant<PhysicsStepFamily>(strict, v);
+  if (!kern) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kern, dim3((a.np / 4 + 255) / 256, n_members), dim3(256), 0, s, a, X, Xout, red);
   return hipGetLastError();
 }

@@ -890,22 +890,21 @@ hipError_t launch_circulation_g96(const float* X, const float* wz, const float* 
 // ---------------------------------------------------------------------------------------------
 // the member kernel
 // ---------------------------------------------------------------------------------------------
-// EXP: honour the member's sensitivity-experiment switches (a.xsw, or a.xsw_m[m] where the members of a
-// launch differ); the default instantiation has none of it.  The switch word is read once and is block-uniform: it drives
-// the point physics, the vapour-diffusion-only form of the sub-steps and the member's OWN sub-step count -- a member
-// without circulation does none while its neighbours do 24 (every wave of a workgroup runs the same count, so the
-// barriers inside Circ::substeps stay matched).
-// BUDGET (scenario phase, opt-in: greb_engine_run_budget): the monthly means of the step's thirteen flux terms go out
-// beside the five standard records.  The default instantiations contain none of it.
-// FORCE (scenario phase, with EXP: a launch with any forced member, greb_engine_set_member_forcing): the member's CO2 pattern,
-// insolation table and scale act in the point physics (greb_physics_step.h: member_force).  Its words are read anew every
-// model step, into scalar registers, so that nothing of it lives across the sub-steps.  No other instantiation contains it.
-// BOUND (both phases, with EXP and -- in the scenario phase -- FORCE: a launch in which any member names a boundary set,
-// greb_engine_set_member_boundary): the thirteen boundary fields are those of the member's set.  Only the set index, one
-// scalar register, lives across the sub-steps: the pointers are fetched from the set table where they are used
-// (greb_physics_step.h: member_boundary), as the other instantiations fetch theirs from the kernel arguments.
-template <bool STRICT, bool FLUX, bool EXP, bool BUDGET = false, bool FORCE = false, bool BOUND = false>
+// V: the variant (greb_kernels.h: which exist, which are legal, which one a launch takes); a variant contains nothing of a
+// feature it does not name.  What each feature means here:
+// kVExp: the member's switch word (a.xsw, or a.xsw_m[m] where the members of a launch differ) is read once
+// and is block-uniform: it drives the point physics, the vapour-diffusion-only form of the sub-steps and the member's OWN
+// sub-step count -- a member without circulation does none while its neighbours do 24 (every wave of a workgroup runs the
+// same count, so the barriers inside Circ::substeps stay matched).
+// kVBudget: the monthly means of the step's thirteen flux terms go out beside the five standard records (a pass of their own).
+// kVForce: the member's CO2 pattern, insolation table and scale act in the point physics (greb_physics_step.h: member_force).
+// Its words are read anew every model step, into scalar registers, so that nothing of it lives across the sub-steps.
+// kVBound: the thirteen boundary fields are those of the member's set.  Only the set index, one scalar register, lives
+// across the sub-steps: the pointers are fetched from the set table where they are used (greb_physics_step.h:
+// member_boundary), as the other variants fetch theirs from the kernel arguments.
+template <bool STRICT, unsigned V>
 __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
+  constexpr bool FLUX = V & kVFlux, EXP = V & kVExp, BUDGET = V & kVBudget, FORCE = V & kVForce, BOUND = V & kVBound;
   extern __shared__ __align__(16) float lds_raw[];
   lfloat* lds = (lfloat*)lds_raw;
   const int m = blockIdx.x, tid = threadIdx.x;
@@ -1003,8 +1002,8 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 #pragma unroll 1
       for (int qd = tid; qd < NP / 4; qd += kThreads) {
         const q8 xpair = ld8(Xf + (qd / NQ) * RS, qd % NQ);
-        const PhysIn in = physics_load<FLUX, EXP, FORCE, BOUND>(a, qd, ck, state, acc, corr, xsw, mf, B);
-        (void)physics_compute<STRICT, FLUX, EXP, true, FORCE>(a, P, in, co2, comp(xpair, 0), comp(xpair, 1), xsw, bs, 4 * qd, mf);
+        const PhysIn in = physics_load<V>(a, qd, ck, state, acc, corr, xsw, mf, B);
+        (void)physics_compute<STRICT, V | kVBudget>(a, P, in, co2, comp(xpair, 0), comp(xpair, 1), xsw, bs, 4 * qd, mf);
       }
     }
 #pragma unroll 1
@@ -1014,7 +1013,7 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 #endif
       const q8 xpair = ld8(Xf + (qd / NQ) * RS, qd % NQ);
       f4 oTa, oq, tsm;
-      physics_quad<STRICT, FLUX, EXP, false, FORCE, BOUND>(a, P, m, qd, ck, co2, state, acc, corr, comp(xpair, 0), comp(xpair, 1), oTa, oq, tsm, xsw, mf, B);
+      physics_quad<STRICT, V & ~kVBudget>(a, P, m, qd, ck, co2, state, acc, corr, comp(xpair, 0), comp(xpair, 1), oTa, oq, tsm, xsw, mf, B);
       st8(Xf + (qd / NQ) * RS, qd % NQ, zip(oTa, oq));
       if (ityr == kNT) st4(red + 4 * qd, tsm);
     }
@@ -1066,28 +1065,15 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
   // all five state fields were written back every step
 }
 
+template <bool STRICT, unsigned V>
+struct MemberFamily { static auto kernel() { return &member_kernel<STRICT, V>; } };
+
 hipError_t launch_member_kernel(const MemberArgs& a, int n_members, bool strict, hipStream_t s) {
   if (a.nx != NX || a.ny != NY) return hipErrorInvalidValue;
-  void (*kern)(MemberArgs);
-  if (a.bset_m) { // a member on a boundary set: every member of the launch takes the boundary-aware instantiation, which is
-                  // switch-aware and, in the scenario phase, forcing-aware (the engine passes neutral forcing words)
-    if (!a.bsets || (!a.flux_phase && !a.force_m) || (a.bsum && (a.flux_phase || !a.brec))) return hipErrorInvalidValue;
-    if (a.flux_phase) kern = strict ? member_kernel<true, true, true, false, false, true> : member_kernel<false, true, true, false, false, true>;
-    else if (a.bsum) kern = strict ? member_kernel<true, false, true, true, true, true> : member_kernel<false, false, true, true, true, true>;
-    else kern = strict ? member_kernel<true, false, true, false, true, true> : member_kernel<false, false, true, false, true, true>;
-  } else if (a.force_m) { // a forced member (scenario phase only): every member of the launch takes the forcing-aware instantiation
-    if (a.flux_phase || (a.bsum && !a.brec)) return hipErrorInvalidValue;
-    if (a.bsum) kern = strict ? member_kernel<true, false, true, true, true> : member_kernel<false, false, true, true, true>;
-    else kern = strict ? member_kernel<true, false, true, false, true> : member_kernel<false, false, true, false, true>;
-  } else if (a.bsum) { // budget output (scenario phase only): the opt-in instantiations
-    if (a.flux_phase || !a.brec) return hipErrorInvalidValue;
-    if (a.xsw || a.xsw_m) kern = strict ? member_kernel<true, false, true, true> : member_kernel<false, false, true, true>;
-    else kern = strict ? member_kernel<true, false, false, true> : member_kernel<false, false, false, true>;
-  } else if (a.xsw || a.xsw_m) { // sensitivity experiment (of every member or of some): the switch-aware instantiation
-    if (a.flux_phase) kern = strict ? member_kernel<true, true, true> : member_kernel<false, true, true>;
-    else kern = strict ? member_kernel<true, false, true> : member_kernel<false, false, true>;
-  } else if (a.flux_phase) kern = strict ? member_kernel<true, true, false> : member_kernel<false, true, false>;
-  else kern = strict ? member_kernel<true, false, false> : member_kernel<false, false, false>;
+  unsigned v;
+  if (hipError_t e = select_variant(a, &v); e != hipSuccess) return e;
+  const auto kern = pick_variant<MemberFamily>(strict, v);
+  if (!kern) return hipErrorInvalidValue;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
   if (e != hipSuccess) return e;

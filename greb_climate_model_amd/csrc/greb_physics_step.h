@@ -35,7 +35,7 @@ __device__ __forceinline__ unsigned member_switches(const MemberArgs& a, int m) 
   return (unsigned)__builtin_amdgcn_readfirstlane((int)(a.xsw_m ? a.xsw_m[m] : a.xsw));
 }
 
-// Per-member forcing (FORCE instantiations, scenario phase only; greb_engine_set_member_forcing): the member's four words
+// Per-member forcing (kVForce variants, scenario phase only; greb_engine_set_member_forcing): the member's four words
 // and what they select from the engine's shared tables, for one model step.  Everything here is block-uniform and read
 // once per step into scalar registers -- nothing of it lives across the circulation sub-steps; what is per point is the
 // pattern's weight quad (PhysIn::fw) and the three operations of forced_co2.
@@ -70,7 +70,7 @@ __device__ __forceinline__ float forced_co2(const MemberForce& f, float w_space,
   return part + rest;
 }
 
-// Boundary sets (BOUND instantiations, both phases; greb_engine_set_member_boundary): the member's entry of the set table.
+// Boundary sets (kVBound variants, both phases; greb_engine_set_member_boundary): the member's entry of the set table.
 // The set index is block-uniform and read once into a scalar register; the entry's pointers are fetched where they are
 // used, by scalar loads through a constant-address-space pointer -- as the default kernels fetch theirs from the kernel
 // arguments -- so that none of the thirteen lives across the circulation sub-steps.  member_boundary makes the entry's
@@ -95,8 +95,8 @@ __device__ __forceinline__ BoundPtr member_boundary(const MemberArgs& a, int bse
 // One quad in three pieces -- load, compute, store -- so that a caller with several quads per thread can request the
 // next quad's operands BETWEEN the arithmetic of the current one and its stores (vector-memory operations retire in
 // order: loads issued behind a quad's stores wait for those stores as well).
-// EXP: the member's sensitivity-experiment switches `xsw` (member_switches) are honoured; false
-// compiles them out.
+// V: the variant (greb_kernels.h).  kVExp: the member's sensitivity-experiment switches `xsw` (member_switches) are
+// honoured; without it they are compiled out.
 struct PhysIn {
   f4 Ts, Ta, To, q, cap;                      // state
   f4 zt, gl, zo, ez;                          // static fields
@@ -112,12 +112,12 @@ struct PhysOut { // everything the stores need: the inputs are dead once this ex
   f4 s0, s1, s2, s3, s4; // the monthly sums including this step (:974)
 };
 
-template <bool FLUX, bool EXP, bool FORCE = false, bool BOUND = false>
+template <unsigned V>
 __device__ __forceinline__ PhysIn physics_load(const MemberArgs& a, int qd, const StepClock& ck, const float* __restrict__ state,
                                                const float* __restrict__ acc, const float* __restrict__ corr, unsigned xsw_member,
-                                               const MemberForce& F = MemberForce{}, BoundPtr B = BoundPtr{}) {
-  static_assert(!FORCE || (EXP && !FLUX), "forcing: scenario phase, switch-aware instantiations only");
-  static_assert(!BOUND || (EXP && (FLUX || FORCE)), "boundary sets: switch-aware, and in the scenario phase forcing-aware, instantiations only");
+                                               const MemberForce& F, BoundPtr B) {
+  constexpr bool FLUX = V & kVFlux, EXP = V & kVExp, FORCE = V & kVForce, BOUND = V & kVBound;
+  static_assert(variant_valid(V), "no such variant of the step kernels");
   const int nx = a.nx, ny = a.ny, np = a.np, p0 = 4 * qd;
   const size_t off = ck.off, offm = ck.offm;
   const unsigned xsw = EXP ? xsw_member : 0u;
@@ -153,7 +153,7 @@ __device__ __forceinline__ PhysIn physics_load(const MemberArgs& a, int qd, cons
   return i;
 }
 
-// Budget output (BUDGET instantiations, scenario phase only): where the thirteen flux terms of a step go.  Block-uniform:
+// Budget output (kVBudget variants, scenario phase only): where the thirteen flux terms of a step go.  Block-uniform:
 // the member's running sums [kNBudget][np], and -- on the last step of a month -- the month's record and its step count
 // (:974-984; step_clock is the one source of month ends for both record kinds).
 struct BudgetSink {
@@ -195,11 +195,12 @@ __device__ __forceinline__ void budget_add(const BudgetSink& b, int np, int term
 // budget sums (bs; p0: the quad's first point) -- under a member's switches they are what the update really used.
 // FORCE: CO2 is the member's scalar blended per point with its reference by the pattern's weight (forced_co2); the insolation
 // came forced from physics_load.
-template <bool STRICT, bool FLUX, bool EXP, bool BUDGET = false, bool FORCE = false>
+template <bool STRICT, unsigned V>
 __device__ __forceinline__ PhysOut physics_compute(const MemberArgs& a, const Phys& P, const PhysIn& in, float co2, const f4& xTa,
-                                                   const f4& xq, unsigned xsw_member, const BudgetSink& bs = BudgetSink{}, int p0 = 0,
-                                                   const MemberForce& F = MemberForce{}) {
-  static_assert(!(BUDGET && FLUX), "the flux-correction phase delivers no budget");
+                                                   const f4& xq, unsigned xsw_member, const BudgetSink& bs, int p0,
+                                                   const MemberForce& F) {
+  constexpr bool FLUX = V & kVFlux, EXP = V & kVExp, BUDGET = V & kVBudget, FORCE = V & kVForce;
+  static_assert(variant_valid(V), "no such variant of the step kernels");
   const unsigned xsw = EXP ? xsw_member : 0u;
   const int np = a.np;
   PhysOut o;
@@ -317,14 +318,14 @@ __device__ __forceinline__ void physics_store(const MemberArgs& a, int m, int qd
 }
 
 // the three pieces in a row (one quad per thread: the any-grid engine)
-template <bool STRICT, bool FLUX, bool EXP = false, bool BUDGET = false, bool FORCE = false, bool BOUND = false>
+template <bool STRICT, unsigned V>
 __device__ __forceinline__ void physics_quad(const MemberArgs& a, const Phys& P, int m, int qd, const StepClock& ck,
                                              float co2, float* __restrict__ state, float* __restrict__ acc,
                                              float* __restrict__ corr, const f4& xTa, const f4& xq, f4& oTa_out,
-                                             f4& oq_out, f4& tsmn_mean, unsigned xsw = 0u, const MemberForce& F = MemberForce{},
-                                             BoundPtr B = BoundPtr{}) {
-  const PhysIn in = physics_load<FLUX, EXP, FORCE, BOUND>(a, qd, ck, state, acc, corr, xsw, F, B);
-  const PhysOut o = physics_compute<STRICT, FLUX, EXP, BUDGET, FORCE>(a, P, in, co2, xTa, xq, xsw, budget_sink<BUDGET>(a, m, ck), 4 * qd, F);
+                                             f4& oq_out, f4& tsmn_mean, unsigned xsw, const MemberForce& F, BoundPtr B) {
+  constexpr bool FLUX = V & kVFlux, BUDGET = V & kVBudget;
+  const PhysIn in = physics_load<V>(a, qd, ck, state, acc, corr, xsw, F, B);
+  const PhysOut o = physics_compute<STRICT, V>(a, P, in, co2, xTa, xq, xsw, budget_sink<BUDGET>(a, m, ck), 4 * qd, F);
   physics_store<FLUX>(a, m, qd, ck, o, state, acc, corr, tsmn_mean);
   oTa_out = o.Ta; oq_out = o.q;
 }

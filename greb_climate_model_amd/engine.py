@@ -59,7 +59,7 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_engine_create_members", "greb_engine_set_member_experiments", "greb_diag_create", "greb_diag_destroy",
            "greb_diag_reduce_dev", "greb_engine_run_diag", "greb_engine_run_budget", "greb_budget_name",
            "greb_member_deal_cover", "greb_engine_set_forcing_tables", "greb_engine_set_member_forcing",
-           "greb_engine_add_boundary_set", "greb_engine_set_member_boundary"]
+           "greb_engine_add_boundary_set", "greb_engine_set_member_boundary", "greb_step_variant", "greb_step_variants"]
 
 
 def _check(rc: int, h=None):
@@ -444,6 +444,23 @@ def member_deal_cover(strict=False):
     out = np.zeros((48, 24), np.int32)
     _check(lib().greb_member_deal_cover(int(bool(strict)), out.ctypes.data_as(C.POINTER(C.c_int))))
     return out
+
+
+def step_variant(flux_phase=False, switches=False, budget=False, forced=False, on_sets=False):
+    """Host-only diagnostic: the variant mask of the step kernels a launch with these properties takes, or None where no
+    launch carries the combination (include/greb_engine.h: greb_step_variant)."""
+    v = C.c_uint(0xFFFFFFFF)
+    rc = lib().greb_step_variant(int(bool(flux_phase)), int(bool(switches)), int(bool(budget)), int(bool(forced)),
+                                 int(bool(on_sets)), C.byref(v))
+    return v.value if rc == 0 else None
+
+
+def step_variants():
+    """Host-only diagnostic: the variant masks that are built (include/greb_engine.h: greb_step_variants)."""
+    n = lib().greb_step_variants(None, 0)
+    out = (C.c_uint * n)()
+    assert lib().greb_step_variants(out, n) == n
+    return list(out)
 
 
 def circulation_launch_plan(params, nx, ny, n_members, kappa=None, slots=2048):

@@ -400,6 +400,20 @@ int greb_circulation_launch_plan(const greb_params* p, int nx, int ny, int n_mem
  * Returns 0, < 0 on a bad argument. */
 int greb_member_deal_cover(int strict, int* counts);
 
+/* Diagnostic, host only (no GPU call): the variant of the step kernels -- a mask of GREB_V_* -- that a launch takes in the
+ * flux-correction (flux_phase != 0) or scenario phase when the engine has experiment switches set (switches), the call is
+ * greb_engine_run_budget (budget), a member is forced (forced) or a member is on a boundary set (on_sets).  This is the
+ * selection the launches themselves go through.  Returns 0 and the mask in *variant; < 0, *variant untouched, for a
+ * combination no launch carries (the flux-correction phase with a budget, or forced without a boundary set). */
+#define GREB_V_FLUX 1u
+#define GREB_V_SWITCHES 2u
+#define GREB_V_BUDGET 4u
+#define GREB_V_FORCING 8u
+#define GREB_V_BOUNDARY 16u
+int greb_step_variant(int flux_phase, int switches, int budget, int forced, int on_sets, unsigned* variant);
+/* Every variant that is built: up to `capacity` masks into out; returns their number (call with capacity 0 to size). */
+int greb_step_variants(unsigned* out, int capacity);
+
 /* Point physics of one step for a batch of columns sets (tests): SWradiation :367-403,
  * LWradiation :407-434, hydro :438-469, deep_ocean :495-525, seaice :472-492 evaluated by the
  * same device functions the engine uses.  in  : Ts,Ta,To,q,cap_surf [5][ny][nx]

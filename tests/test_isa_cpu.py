@@ -124,6 +124,8 @@ def test_fast_kernels_at_a_register_cliff_stay_off_scratch(code_objects):
         notes.update(_kernel_notes(path))
     member = {k: v for k, v in notes.items() if "member_kernel" in k and "ILb0E" in k}  # member_kernel<false, ...>: FAST
     assert member, sorted(notes)[:5]
+    from greb_climate_model_amd import engine
+    assert len(member) == len(engine.step_variants()) == 11, sorted(member)  # one FAST member kernel per variant (greb_kernels.h: kVariants)
     for k, v in member.items():
         assert v["private_segment_fixed_size"] == 0 and v["vgpr_spill_count"] == 0 and v["vgpr_count"] <= 256, (k, v)
     rows = {k: v for k, v in notes.items() if "dif_rows_kernel" in k and "ILb0E" in k}

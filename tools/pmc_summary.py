@@ -34,7 +34,7 @@ def raw(files):
 
 
 def derive(sq, lds, stats):
-    key = "member_kernel<false, true, false,"  # flux-correction year of ONE member (shared physics): 8 waves on one CU
+    key = "member_kernel<false, 1u>"  # flux-correction year of ONE member (shared physics): 8 waves on one CU
     c = {}
     for f in (sq, lds):
         agg, ndisp = load(f)
