@@ -16,6 +16,7 @@ F_PERSISTENT = 16
 RUN_DEVICE_OUT = 1
 D_REGIONS, D_ZONAL, D_ANNUAL = 1, 2, 4  # reduced-output products, GREB_D_* of include/greb_engine.h
 D_MAX_REGIONS = 15
+C_MEAN, C_SEASONS, C_TREND, C_RESPONSE = 1, 2, 4, 8  # climatology products, GREB_C_* of include/greb_engine.h
 # budget output, GREB_NBUDGET / GREB_B_* of include/greb_engine.h: the flux terms of the update in its order, sign and unit
 BUDGET_NAMES = ("sw", "LW_surf", "LWair_down", "LW_abs", "Q_sens", "Q_lat", "Q_lat_air", "dq_eva", "dq_rain", "dT_ocean",
                 "dTo", "dTa_crcl", "dq_crcl")

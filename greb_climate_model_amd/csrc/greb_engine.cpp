@@ -24,6 +24,7 @@
 
 #include "greb_kernels.h"
 #include "greb_diag.h"
+#include "greb_clim.h"
 
 using namespace greb;
 
@@ -171,6 +172,7 @@ struct greb_engine {
   float* yearly_dev = nullptr; size_t yearly_cap = 0;
   float* diag_out = nullptr; size_t diag_out_cap = 0; // run_diag: zonal means and annual maps of two years (one per staging slot)
   float* diag_reg = nullptr; size_t diag_reg_cap = 0; // run_diag: the region series of the whole call
+  float* clim_out = nullptr; size_t clim_out_cap = 0; // run_clim: the products of two periods (one per output slot)
   // host copies needed later
   std::vector<RowTables> h_tabs;
   std::vector<int> h_tab_index;
@@ -824,7 +826,7 @@ int greb_engine_destroy(greb_engine* e) {
   void* ptrs[] = {e->z_topo, e->glacier, e->sw_solar, e->tclim, e->qclim, e->uclim, e->vclim, e->mldclim,
                   e->cldclim, e->swetclim, e->toclim, e->z_ocean, e->wz_air, e->wz_vapor, e->state, e->acc,
                   e->corr, e->corr_index, e->tab_index, e->tabs, e->phys, e->co2_dev, e->monthly_dev, e->yearly_dev,
-                  e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev, e->diag_out, e->diag_reg, e->bsum, e->budget_dev,
+                  e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev, e->diag_out, e->diag_reg, e->clim_out, e->bsum, e->budget_dev,
                   e->f_space, e->f_season, e->f_solar, e->force_dev, e->bsets_dev, e->bset_dev, e->neutral_force_dev};
   for (void* q : ptrs) if (q) (void)hipFree(q);
   for (size_t k = 1; k < e->bound.size(); ++k)
@@ -1121,6 +1123,277 @@ int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_d
   if (int rc = check_circulation(e)) return rc;
   e->it_scnr += (long long)years * kNT;
   if (do_r) HIP_TRY(e, hipMemcpy(regions, e->diag_reg, nm * years * reg_year * sizeof(float), hipMemcpyDeviceToHost));
+  if (yearly) HIP_TRY(e, hipMemcpy(yearly, e->yearly_dev, nm * years * 2 * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- climatology output (greb_clim.hip)
+// A plan is host data only: grid, member count, each member's control and the products.  The fp64 sums (and the control
+// map's device copy) are made per device the first time the plan adds a year there.  `added` counts the years since the
+// last finish: one period is summed at a time, on one device.
+struct greb_clim {
+  int nx = 0, ny = 0, nm = 0;
+  unsigned what = 0;
+  std::vector<int32_t> control; // [nm], or empty: no control map
+  int added = 0;                // years added since the last finish
+  int added_device = -1;        // ... on this device
+  struct Dev { int device; double* S; double* T; int* control; };
+  std::vector<Dev> devs;
+  size_t elems() const { return (size_t)nm * kClimMonths * kClimVars * nx * ny; }
+};
+
+namespace {
+int clim_on_device(greb_clim* c, int device, greb_clim::Dev** out) {
+  for (auto& x : c->devs) if (x.device == device) { *out = &x; return 0; }
+  greb_clim::Dev n{device, nullptr, nullptr, nullptr};
+  hipError_t err = dev_alloc(&n.S, c->elems());
+  if (err == hipSuccess && (c->what & GREB_C_TREND)) err = dev_alloc(&n.T, c->elems());
+  if (err == hipSuccess && !c->control.empty()) {
+    err = dev_alloc(&n.control, c->control.size());
+    if (err == hipSuccess) err = hipMemcpy(n.control, c->control.data(), c->control.size() * sizeof(int), hipMemcpyHostToDevice);
+  }
+  if (err != hipSuccess) {
+    if (n.S) (void)hipFree(n.S);
+    if (n.T) (void)hipFree(n.T);
+    if (n.control) (void)hipFree(n.control);
+    HIP_TRY(nullptr, err);
+  }
+  c->devs.push_back(n);
+  *out = &c->devs.back();
+  return 0;
+}
+
+// floats of one member's record of each product of one period: MEAN, SEASONS, TREND, the MEAN response, the SEASONS response
+void clim_sizes(const greb_clim* c, size_t out[5]) {
+  const size_t np = (size_t)c->nx * c->ny, mon = (size_t)kClimMonths * kClimVars * np, sea = (size_t)kClimSeasons * kClimVars * np;
+  const bool resp = (c->what & GREB_C_RESPONSE) != 0;
+  out[0] = (c->what & GREB_C_MEAN) ? mon : 0;
+  out[1] = (c->what & GREB_C_SEASONS) ? sea : 0;
+  out[2] = (c->what & GREB_C_TREND) ? mon : 0;
+  out[3] = resp && (c->what & GREB_C_MEAN) ? mon : 0;
+  out[4] = resp && (c->what & GREB_C_SEASONS) ? sea : 0;
+}
+
+ClimFinishArgs clim_finish_args(const greb_clim* c, const greb_clim::Dev* dv, int n_years, float* const out[5]) {
+  ClimFinishArgs a{};
+  a.S = dv->S; a.T = dv->T; a.control = dv->control;
+  a.np = (size_t)c->nx * c->ny; a.n_years = n_years;
+  a.mean = out[0]; a.seasons = out[1]; a.trend = out[2]; a.mean_resp = out[3]; a.seasons_resp = out[4];
+  return a;
+}
+
+const char* const kClimOutNames[5] = {"mean", "seasons", "trend", "mean_resp", "seasons_resp"};
+const char* const kClimFlagNames[5] = {"GREB_C_MEAN", "GREB_C_SEASONS", "GREB_C_TREND", "GREB_C_RESPONSE with GREB_C_MEAN",
+                                       "GREB_C_RESPONSE with GREB_C_SEASONS"};
+} // namespace
+
+extern "C" {
+
+int greb_clim_create(int nx, int ny, int n_members, const int32_t* control, unsigned what, greb_clim** out) {
+  if (!out) return fail(nullptr, GREB_E_INVALID, "clim_create: `out` is NULL");
+  *out = nullptr;
+  if (nx < 12 || (nx & 3) || ny < 5 || ny > kMaxNy)
+    return fail(nullptr, GREB_E_INVALID, "clim_create: grid " + std::to_string(nx) + " x " + std::to_string(ny) +
+                                             " (nx % 4 == 0, nx >= 12, 5 <= ny <= " + std::to_string(kMaxNy) + ")");
+  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "clim_create: n_members = " + std::to_string(n_members));
+  const unsigned all = GREB_C_MEAN | GREB_C_SEASONS | GREB_C_TREND | GREB_C_RESPONSE;
+  if (what == 0 || (what & ~all))
+    return fail(nullptr, GREB_E_INVALID, "clim_create: `what` = " + std::to_string(what) + " selects no product or an unknown one");
+  if ((what & GREB_C_RESPONSE) && !(what & (GREB_C_MEAN | GREB_C_SEASONS)))
+    return fail(nullptr, GREB_E_INVALID, "clim_create: GREB_C_RESPONSE needs GREB_C_MEAN or GREB_C_SEASONS (it is their difference to "
+                                         "the control)");
+  if ((what & GREB_C_RESPONSE) && !control)
+    return fail(nullptr, GREB_E_INVALID, "clim_create: GREB_C_RESPONSE selected but `control` is NULL");
+  if (control)
+    for (int m = 0; m < n_members; ++m)
+      if (control[m] < -1 || control[m] >= n_members)
+        return fail(nullptr, GREB_E_INVALID, "clim_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
+                                                 " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
+  greb_clim* c = new (std::nothrow) greb_clim();
+  if (!c) return fail(nullptr, GREB_E_INVALID, "out of host memory");
+  c->nx = nx; c->ny = ny; c->nm = n_members; c->what = what;
+  if (control) c->control.assign(control, control + n_members);
+  *out = c;
+  return 0;
+}
+
+int greb_clim_destroy(greb_clim* c) {
+  if (!c) return 0;
+  int prev = 0;
+  const bool have_prev = !c->devs.empty() && hipGetDevice(&prev) == hipSuccess;
+  for (auto& x : c->devs)
+    if (hipSetDevice(x.device) == hipSuccess) {
+      (void)hipDeviceSynchronize(); // a pass in flight may still use the sums
+      (void)hipFree(x.S);
+      if (x.T) (void)hipFree(x.T);
+      if (x.control) (void)hipFree(x.control);
+    }
+  if (have_prev) (void)hipSetDevice(prev);
+  delete c;
+  return 0;
+}
+
+int greb_clim_add_year_dev(greb_clim* c, int device, const float* monthly_year_dev, int k, void* stream) {
+  if (!c) return fail(nullptr, GREB_E_INVALID, "clim_add_year_dev: no plan (greb_clim is NULL)");
+  if (!monthly_year_dev) return fail(nullptr, GREB_E_INVALID, "clim_add_year_dev: monthly_year_dev is NULL");
+  if (reinterpret_cast<uintptr_t>(monthly_year_dev) & 15)
+    return fail(nullptr, GREB_E_INVALID, "clim_add_year_dev: monthly_year_dev is not 16-byte aligned");
+  if (k != c->added)
+    return fail(nullptr, GREB_E_INVALID, "clim_add_year_dev: k = " + std::to_string(k) + ", but " + std::to_string(c->added) +
+                                             " years were added since the last finish (years go in ascending order, k = 0 first)");
+  if (k > 0 && device != c->added_device)
+    return fail(nullptr, GREB_E_INVALID, "clim_add_year_dev: device " + std::to_string(device) + ", but this period's sums are on device " +
+                                             std::to_string(c->added_device));
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
+    return fail(nullptr, GREB_E_NOGPU, "clim_add_year_dev: no HIP device (no CPU path)");
+  HIP_TRY(nullptr, hipSetDevice(device));
+  greb_clim::Dev* dv = nullptr;
+  if (int rc = clim_on_device(c, device, &dv)) return rc;
+  HIP_TRY(nullptr, launch_clim_add_year(monthly_year_dev, dv->S, dv->T, c->elems(), k, (hipStream_t)stream));
+  c->added = k + 1; c->added_device = device;
+  return 0;
+}
+
+int greb_clim_finish_dev(greb_clim* c, int device, int n_years, float* mean_dev, float* seasons_dev, float* trend_dev,
+                         float* mean_resp_dev, float* seasons_resp_dev, void* stream) {
+  if (!c) return fail(nullptr, GREB_E_INVALID, "clim_finish_dev: no plan (greb_clim is NULL)");
+  size_t size[5];
+  clim_sizes(c, size);
+  float* out[5] = {mean_dev, seasons_dev, trend_dev, mean_resp_dev, seasons_resp_dev};
+  for (int i = 0; i < 5; ++i) {
+    if (!size[i]) { out[i] = nullptr; continue; } // (not selected: the pointer is ignored)
+    if (!out[i])
+      return fail(nullptr, GREB_E_INVALID, std::string("clim_finish_dev: ") + kClimFlagNames[i] + " selected but `" + kClimOutNames[i] +
+                                               "_dev` is NULL");
+    if (reinterpret_cast<uintptr_t>(out[i]) & 15)
+      return fail(nullptr, GREB_E_INVALID, std::string("clim_finish_dev: ") + kClimOutNames[i] + "_dev is not 16-byte aligned");
+  }
+  if (n_years != c->added || n_years < 1)
+    return fail(nullptr, GREB_E_INVALID, "clim_finish_dev: n_years = " + std::to_string(n_years) + ", but " + std::to_string(c->added) +
+                                             " years were added since the last finish");
+  if (device != c->added_device)
+    return fail(nullptr, GREB_E_INVALID, "clim_finish_dev: device " + std::to_string(device) + ", but this period's sums are on device " +
+                                             std::to_string(c->added_device));
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
+    return fail(nullptr, GREB_E_NOGPU, "clim_finish_dev: no HIP device (no CPU path)");
+  HIP_TRY(nullptr, hipSetDevice(device));
+  greb_clim::Dev* dv = nullptr;
+  if (int rc = clim_on_device(c, device, &dv)) return rc;
+  HIP_TRY(nullptr, launch_clim_finish(clim_finish_args(c, dv, n_years, out), c->nm, (hipStream_t)stream));
+  c->added = 0; c->added_device = -1;
+  return 0;
+}
+
+int greb_engine_run_clim(greb_engine* e, int years, const float* co2_ppm, greb_clim* c, int n_periods, const int32_t* first_year,
+                         const int32_t* n_years, float* mean, float* seasons, float* trend, float* mean_resp, float* seasons_resp,
+                         float* yearly) {
+  // argument errors first, before anything touches a device: the plan, the periods, the outputs, then the engine
+  if (!c) return fail(e, GREB_E_INVALID, "run_clim: no plan (greb_clim is NULL)");
+  if (years < 1) return fail(e, GREB_E_INVALID, "run_clim: years = " + std::to_string(years));
+  if (n_periods < 1 || !first_year || !n_years)
+    return fail(e, GREB_E_INVALID, "run_clim: n_periods = " + std::to_string(n_periods) + " with first_year / n_years " +
+                                       (first_year && n_years ? "given" : "NULL") + " (at least one period is needed)");
+  for (int p = 0; p < n_periods; ++p) {
+    const std::string who = "run_clim: period " + std::to_string(p) + " (first_year " + std::to_string(first_year[p]) + ", n_years " +
+                            std::to_string(n_years[p]) + ")";
+    if (n_years[p] < 1) return fail(e, GREB_E_INVALID, who + " has no years");
+    if (first_year[p] < 0 || (long long)first_year[p] + n_years[p] > years)
+      return fail(e, GREB_E_INVALID, who + " is not inside the run's years 0 ... " + std::to_string(years - 1));
+    if (p > 0 && first_year[p] < first_year[p - 1])
+      return fail(e, GREB_E_INVALID, who + " starts before period " + std::to_string(p - 1) + ": periods must be ascending");
+    if (p > 0 && first_year[p] < first_year[p - 1] + n_years[p - 1])
+      return fail(e, GREB_E_INVALID, who + " overlaps period " + std::to_string(p - 1) + ", which ends with year " +
+                                         std::to_string(first_year[p - 1] + n_years[p - 1] - 1));
+  }
+  size_t size[5];
+  clim_sizes(c, size);
+  float* host[5] = {mean, seasons, trend, mean_resp, seasons_resp};
+  for (int i = 0; i < 5; ++i)
+    if (size[i] && !host[i])
+      return fail(e, GREB_E_INVALID, std::string("run_clim: ") + kClimFlagNames[i] + " selected but `" + kClimOutNames[i] + "` is NULL");
+  if (c->added != 0)
+    return fail(e, GREB_E_INVALID, "run_clim: the plan holds " + std::to_string(c->added) + " years of an unfinished period");
+  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, "run_clim: bad argument (engine or co2_ppm)");
+  if (c->nx != e->nx || c->ny != e->ny)
+    return fail(e, GREB_E_INVALID, "run_clim: the plan's grid " + std::to_string(c->nx) + " x " + std::to_string(c->ny) +
+                                       " differs from the engine's " + std::to_string(e->nx) + " x " + std::to_string(e->ny));
+  if (c->nm != e->nm)
+    return fail(e, GREB_E_INVALID, "run_clim: the plan is for " + std::to_string(c->nm) + " members, the engine has " +
+                                       std::to_string(e->nm));
+  HIP_TRY(e, hipSetDevice(e->device));
+  const size_t nm = (size_t)e->nm;
+  const size_t slot = nm * 12 * 5 * (size_t)e->np; // one model year of records
+  size_t at[5], out_slot = 0; // where each product sits in an output slot: [member][its record], 16-byte aligned (np % 4 == 0)
+  for (int i = 0; i < 5; ++i) { at[i] = out_slot; out_slot += nm * size[i]; }
+  if (int rc = ensure(e, &e->co2_dev, &e->co2_cap, nm * years)) return rc;
+  HIP_TRY(e, hipMemcpyAsync(e->co2_dev, co2_ppm, nm * years * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  if (int rc = ensure(e, &e->yearly_dev, &e->yearly_cap, nm * years * 2)) return rc;
+  HIP_TRY(e, hipMemsetAsync(e->yearly_dev, 0, nm * years * 2 * sizeof(float), e->stream));
+  // On the device: the two one-year staging slots of greb_engine_run, the plan's sums, and two output slots of one
+  // period's products each.  Nothing of it grows with `years` or `n_periods` (besides the yearly scalars).
+  if (int rc = ensure(e, &e->monthly_dev, &e->monthly_cap, 2 * slot)) return rc;
+  if (int rc = ensure(e, &e->clim_out, &e->clim_out_cap, 2 * out_slot)) return rc;
+  greb_clim::Dev* dv = nullptr;
+  if (int rc = clim_on_device(c, e->device, &dv)) { e->last_error = g_last_error; return rc; }
+  if (!e->copy_stream) HIP_TRY(e, hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
+  for (int i = 0; i < 2; ++i) {
+    if (!e->ev_done[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_done[i], hipEventDisableTiming));
+    if (!e->ev_free[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_free[i], hipEventDisableTiming));
+  }
+  // period p's products leave from output slot p & 1 on the copy stream while the following years integrate (the event
+  // pairs of greb_engine_run, here per output slot); the host side is strided by the caller's [member][period] layout
+  auto deliver = [&](int p) -> int {
+    const int sl = p & 1;
+    HIP_TRY(e, hipStreamWaitEvent(e->copy_stream, e->ev_done[sl], 0));
+    for (int i = 0; i < 5; ++i)
+      if (size[i])
+        HIP_TRY(e, hipMemcpy2DAsync(host[i] + (size_t)p * size[i], (size_t)n_periods * size[i] * sizeof(float),
+                                    e->clim_out + (size_t)sl * out_slot + at[i], size[i] * sizeof(float), size[i] * sizeof(float), nm,
+                                    hipMemcpyDeviceToHost, e->copy_stream));
+    HIP_TRY(e, hipEventRecord(e->ev_free[sl], e->copy_stream));
+    return 0;
+  };
+  // as in greb_engine_run: no return while copies into the CALLER's buffers are in flight
+  const int rc_years = [&]() -> int {
+    int p = 0, finished = 0, delivered = 0; // the period year y is in or before; periods finished; periods delivered
+    for (int y = 0; y < years; ++y) {
+      const MemberArgs a = scenario_args(e, years, y, e->monthly_dev + (size_t)(y & 1) * slot, 1, 0);
+      if (int rc = run_year(e, a, e->nm)) return rc;
+      while (p < n_periods && y >= first_year[p] + n_years[p]) ++p;
+      if (p < n_periods && y >= first_year[p]) { // (a year outside every period is integrated, not summed)
+        const int k = y - first_year[p];
+        HIP_TRY(e, launch_clim_add_year(a.monthly, dv->S, dv->T, c->elems(), k, e->stream));
+        if (k == n_years[p] - 1) {
+          const int sl = p & 1;
+          if (p >= 2) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_free[sl], 0)); // the slot's products of period p - 2 have left
+          float* out[5];
+          for (int i = 0; i < 5; ++i) out[i] = size[i] ? e->clim_out + (size_t)sl * out_slot + at[i] : nullptr;
+          HIP_TRY(e, launch_clim_finish(clim_finish_args(c, dv, n_years[p], out), e->nm, e->stream));
+          HIP_TRY(e, hipEventRecord(e->ev_done[sl], e->stream));
+          finished = p + 1;
+        }
+      }
+      // a period that ended with an EARLIER year leaves now, with this year's kernels already enqueued (so that even a
+      // copy the runtime performs synchronously runs beside a kernel)
+      const int ready = (finished > 0 && first_year[finished - 1] + n_years[finished - 1] - 1 == y) ? finished - 1 : finished;
+      for (; delivered < ready; ++delivered) if (int rc = deliver(delivered)) return rc;
+    }
+    for (; delivered < finished; ++delivered) if (int rc = deliver(delivered)) return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->copy_stream));
+    return 0;
+  }();
+  if (rc_years) {
+    (void)hipStreamSynchronize(e->copy_stream);
+    (void)hipStreamSynchronize(e->stream);
+    return rc_years;
+  }
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  if (int rc = check_circulation(e)) return rc;
+  e->it_scnr += (long long)years * kNT;
   if (yearly) HIP_TRY(e, hipMemcpy(yearly, e->yearly_dev, nm * years * 2 * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }

@@ -59,7 +59,8 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_engine_create_members", "greb_engine_set_member_experiments", "greb_diag_create", "greb_diag_destroy",
            "greb_diag_reduce_dev", "greb_engine_run_diag", "greb_engine_run_budget", "greb_budget_name",
            "greb_member_deal_cover", "greb_engine_set_forcing_tables", "greb_engine_set_member_forcing",
-           "greb_engine_add_boundary_set", "greb_engine_set_member_boundary", "greb_step_variant", "greb_step_variants"]
+           "greb_engine_add_boundary_set", "greb_engine_set_member_boundary", "greb_step_variant", "greb_step_variants",
+           "greb_clim_create", "greb_clim_destroy", "greb_clim_add_year_dev", "greb_clim_finish_dev", "greb_engine_run_clim"]
 
 
 def _check(rc: int, h=None):
@@ -269,6 +270,22 @@ class Engine:
         _check(lib().greb_engine_run_diag(self.h, int(years), abi.fptr(co2), plan.h, C.c_uint(what), *ptr, abi.fptr(yearly)),
                self.h)
         return diag.Result(regions, zonal, annual, yearly, plan.names)
+
+    def run_clim(self, years: int, co2_ppm, plan, periods):
+        """The scenario run of run() that hands back only the climatology products of `plan` (clim.Plan) over `periods`, a
+        list of (first_year, n_years) inside this call's years -- ascending, not overlapping; years outside every period
+        are integrated but not summed (greb_engine_run_clim).  Returns a clim.Result of arrays [n_members][n_periods]...
+        (a product the plan does not select is None).  State, clock and yearly are those of run() over the same years."""
+        from . import clim
+        co2 = np.ascontiguousarray(np.broadcast_to(np.asarray(co2_ppm, np.float32), (self.nm, years)))
+        yearly = np.zeros((self.nm, years, 2), np.float32)
+        per = np.ascontiguousarray(periods, np.int32).reshape(-1, 2)
+        first, count = np.ascontiguousarray(per[:, 0]), np.ascontiguousarray(per[:, 1])
+        out = clim.empty_products(plan.what, (self.nm, len(per)), self.ny, self.nx)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        _check(lib().greb_engine_run_clim(self.h, int(years), abi.fptr(co2), plan.h, len(per), ip(first), ip(count),
+                                          *[None if a is None else abi.fptr(a) for a in out], abi.fptr(yearly)), self.h)
+        return clim.Result(*out, yearly)
 
     def state(self, member: int = 0) -> np.ndarray:
         s = np.empty((5, self.ny, self.nx), np.float32)

@@ -93,6 +93,44 @@ module greb_c_api
        real(c_float), intent(in) :: co2_ppm(*)
        real(c_float), intent(out) :: regions(*), zonal(*), annual(*), yearly(*)
      end function
+     ! climatology output (greb_clim.hip): a plan = grid, member count, control(n_members) with each member's control member
+     ! (0-based, -1 = none; c_null_ptr: no control map) and the products `what` (1 mean, 2 seasons, 4 trend, 8 response)
+     integer(c_int) function greb_clim_create(nx, ny, n_members, control, what, plan) bind(C, name="greb_clim_create")
+       import :: c_int, c_ptr
+       integer(c_int), value :: nx, ny, n_members, what
+       type(c_ptr), value :: control
+       type(c_ptr), intent(out) :: plan
+     end function
+     integer(c_int) function greb_clim_destroy(plan) bind(C, name="greb_clim_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan
+     end function
+     ! device pointers (c_ptr); year k (0-based) of the current period into the sums; launches on `stream`, no synchronisation
+     integer(c_int) function greb_clim_add_year_dev(plan, device, monthly_year_dev, k, stream) &
+          bind(C, name="greb_clim_add_year_dev")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan, monthly_year_dev, stream
+       integer(c_int), value :: device, k
+     end function
+     ! the products of the n_years years added since the last finish; a product the plan does not select may be c_null_ptr
+     integer(c_int) function greb_clim_finish_dev(plan, device, n_years, mean_dev, seasons_dev, trend_dev, mean_resp_dev, &
+          seasons_resp_dev, stream) bind(C, name="greb_clim_finish_dev")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan, mean_dev, seasons_dev, trend_dev, mean_resp_dev, seasons_resp_dev, stream
+       integer(c_int), value :: device, n_years
+     end function
+     ! greb_engine_run that delivers only the plan's products of n_periods averaging periods (0-based first_year, n_years):
+     ! mean, trend, mean_resp (nx,ny,5,12,n_periods,n_members); seasons, seasons_resp (nx,ny,5,5,n_periods,n_members);
+     ! a product the plan does not select may be c_null_ptr
+     integer(c_int) function greb_engine_run_clim(eng, years, co2_ppm, plan, n_periods, first_year, n_years, mean, seasons, &
+          trend, mean_resp, seasons_resp, yearly) bind(C, name="greb_engine_run_clim")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, plan, mean, seasons, trend, mean_resp, seasons_resp
+       integer(c_int), value :: years, n_periods
+       real(c_float), intent(in) :: co2_ppm(*)
+       integer(c_int), intent(in) :: first_year(*), n_years(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
      ! greb_engine_run that also delivers the monthly means of the 13 flux terms of the update (GREB_B_* of greb_engine.h):
      ! budget(nx,ny,13,12,years,n_members); monthly as in greb_engine_run, or c_null_ptr for a budget-only run
      integer(c_int) function greb_engine_run_budget(eng, years, co2_ppm, monthly, budget, yearly, run_flags) &

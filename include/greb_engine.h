@@ -230,6 +230,64 @@ int greb_diag_reduce_dev(greb_diag* d, int device, const float* monthly_year_dev
 int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_diag* d, unsigned what, float* regions,
                          float* zonal, float* annual, float* yearly);
 
+/* ---- climatology output: multi-year means, seasons, trends and responses made on the device -------
+ * What an ensemble with a control member beside its other members is run for: average each calendar month over a window
+ * of years, then subtract the control.  The reference leaves that to R scripts over the files of separate processes; here
+ * the reduction along the time axis -- the only axis whose output grows with the length of the run -- happens in the
+ * staging slot behind each model year (greb_clim.hip).  Per element the years of a period are summed in fp64 in
+ * ascending year order, S = sum x and (for the trend) T = sum k x with k = 0 ... n-1 the year inside the period; of those,
+ * all in fp64 and each rounded to fp32 exactly once:
+ *   mean64[mo]      = S[mo] / n
+ *   GREB_C_MEAN     [member][period][12][5][ny][nx]   mean64
+ *   GREB_C_SEASONS  [member][period][5][5][ny][nx]    DJF, MAM, JJA, SON, ANN:  acc = 0; acc = acc + jday_mon[mo] mean64[mo]
+ *                   over the season's months in calendar order (DJF = Dec, Jan, Feb of the SAME calendar years; ANN =
+ *                   Jan ... Dec); acc / the season's days (90, 92, 92, 91, 365; jday_mon: src/greb.f90:42)
+ *   GREB_C_TREND    [member][period][12][5][ny][nx]   per calendar month the least-squares slope per year,
+ *                   (T - kbar S) / Sxx with kbar = (n-1)/2, Sxx = n(n^2-1)/12; 0 for n = 1
+ *   GREB_C_RESPONSE the selected MEAN / SEASONS also as member minus its control, mean64[m] - mean64[control[m]] and the
+ *                   same of the seasonal means (the difference is formed in fp64, before anything is rounded).  A member
+ *                   with control[m] = -1 has a QUIET NaN in its response records -- zero would read as "no response";
+ *                   control[m] = m is legal and gives zeros.
+ * The order of these operations is the definition of the results (no fused multiply-add); every element has one owner
+ * (no atomics), so results are deterministic and a member's numbers do not depend on the batch it is in. */
+#define GREB_C_MEAN     1u
+#define GREB_C_SEASONS  2u
+#define GREB_C_TREND    4u
+#define GREB_C_RESPONSE 8u
+typedef struct greb_clim greb_clim;
+/* A plan: grid, member count, each member's control (control[m] in -1 ... n_members-1, or NULL: no control map) and the
+ * products.  Host data only, validated without touching a device: a grid greb_diag_create does not take, n_members < 1,
+ * a control index out of range, `what` zero or with unknown bits, GREB_C_RESPONSE without GREB_C_MEAN or GREB_C_SEASONS
+ * or without `control` are GREB_E_INVALID with a message that names the offender (greb_engine_last_error(NULL)).  The
+ * fp64 sums (8 bytes per element of a model year, 16 with the trend) live per device and are allocated on first use.  A
+ * plan sums one period at a time and serves any number of periods, calls and engines one after the other. */
+int greb_clim_create(int nx, int ny, int n_members, const int32_t* control, unsigned what, greb_clim** out);
+int greb_clim_destroy(greb_clim* c); /* waits for the device before it frees the sums */
+/* Year k (0-based) of the current period, one model year [n_members][12][5][ny][nx] on HIP device `device` (16-byte
+ * aligned), into the sums.  k must be the number of years added since the last finish: k = 0 stores, it does not add, so
+ * no clearing is needed.  Launches on `stream` (a hipStream_t, may be NULL) and does not synchronise; the calls of one
+ * period must be ordered among themselves (one stream, or the caller's events). */
+int greb_clim_add_year_dev(greb_clim* c, int device, const float* monthly_year_dev, int k, void* stream);
+/* The products of the n_years years added since the last finish (n_years must be that number) to device memory, laid out
+ * [n_members] + the shapes above without [period], 16-byte aligned.  A pointer whose product the plan does not select
+ * is ignored and may be NULL; a selected product with a NULL pointer is GREB_E_INVALID.  Both _dev calls check their
+ * arguments before any device query; without a device they are GREB_E_NOGPU (no CPU path). */
+int greb_clim_finish_dev(greb_clim* c, int device, int n_years, float* mean_dev, float* seasons_dev, float* trend_dev,
+                         float* mean_resp_dev, float* seasons_resp_dev, void* stream);
+/* greb_engine_run that delivers ONLY the plan's products of n_periods averaging periods, to host memory in the shapes
+ * above.  Period p covers the years first_year[p] ... first_year[p] + n_years[p] - 1 of this call (0-based); periods are
+ * ascending, do not overlap and lie inside 0 ... years-1 (GREB_E_INVALID otherwise, as for a plan made for another grid
+ * or member count or a selected product with a NULL pointer; the message names the period at fault; all of it is decided
+ * before any device work).  Years outside every period are integrated but not summed.  Each year is integrated into
+ * one of the engine's two one-year staging slots and added to the sums there; at a period's last year its products are
+ * written to one of two device output slots and leave on the copy stream while the following years integrate.  Device
+ * memory grows neither with `years` nor with n_periods (the yearly scalars aside).  co2_ppm, yearly, the model clock, the
+ * state the engine is left in and the kernels that integrate are those of greb_engine_run over the same years, bit for
+ * bit: switches, member forcing and boundary sets act as they do there. */
+int greb_engine_run_clim(greb_engine* e, int years, const float* co2_ppm, greb_clim* c, int n_periods, const int32_t* first_year,
+                         const int32_t* n_years, float* mean, float* seasons, float* trend, float* mean_resp, float* seasons_resp,
+                         float* yearly);
+
 /* ---- per-member forcing: regional and seasonal CO2, insolation tables and scale --------------------
  * Members of one engine may differ in the forcing itself, not only in the CO2 level: CO2 raised in one hemisphere, over
  * land or ocean only or in one half of the year, a changed solar constant, a changed latitudinal or seasonal distribution

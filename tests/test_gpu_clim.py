@@ -1,0 +1,281 @@
+"""GPU: the climatology output (csrc/greb_clim.hip) against clim.reference, the numpy fp64 statement of its products.
+
+Every comparison with the mirror is for EQUAL BITS: device and mirror perform the same IEEE fp64 operations (add,
+multiply, divide, one conversion to fp32) in the same order on the same fp32 data -- the kernels are built without
+contraction of a multiply into the add behind it -- so there is nothing for a tolerance to cover."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from greb_climate_model_amd import abi, clim, engine, workload
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LO = np.array([220.0, 220.0, 271.0, 1e-3, 0.05], np.float32)  # Tsurf, Tair, Tocean [K], q [kg/kg], albedo
+HI = np.array([310.0, 300.0, 303.0, 2e-2, 0.80], np.float32)
+CONTROL = [-1, 0, 0, 1, -1, 4, 6]
+NAMES = clim.PRODUCTS
+
+
+def synth(years, n, ny, nx, seed):
+    """Strictly positive fp32 records of physical magnitude, [years][n][12][5][ny][nx]."""
+    rng = np.random.default_rng(seed)
+    x = rng.random((years, n, 12, 5, ny, nx), dtype=np.float32)
+    x *= (HI - LO)[:, None, None]
+    x += LO[:, None, None]
+    assert x.dtype == np.float32 and x.min() > 0
+    return x
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def same_bits(got, ref, label):
+    """Every product of two Results: both None, or equal shape and equal bits (NaNs included)."""
+    for name in NAMES:
+        g, r = getattr(got, name), getattr(ref, name)
+        assert (g is None) == (r is None), (label, name)
+        if g is None:
+            continue
+        g, r = np.asarray(g), np.asarray(r)
+        assert g.dtype == np.float32 and g.shape == r.shape, (label, name, g.dtype, g.shape, r.shape)
+        bad = bits(g) != bits(r)
+        print(f"{label} {name}: {int(bad.sum())} of {bad.size} values differ from the mirror")
+        assert not bad.any(), (label, name, int(bad.sum()), g[bad][:4], r[bad][:4])
+
+
+def to_host(res):
+    import torch
+    torch.cuda.synchronize()
+    return clim.Result(*[None if getattr(res, n) is None else getattr(res, n).cpu().numpy() for n in NAMES])
+
+
+def reduce_dev(plan, xd, n_years=None):
+    """The years xd[0 ... n_years) through add_year_dev / finish_dev."""
+    n_years = len(xd) if n_years is None else n_years
+    for k in range(n_years):
+        clim.add_year_dev(plan, xd[k], k)
+    return to_host(clim.finish_dev(plan, n_years))
+
+
+@pytest.mark.parametrize("years", [1, 2, 5])
+@pytest.mark.parametrize("nx,ny,n", [(96, 48, 1), (96, 48, 3), (96, 48, 7), (100, 37, 1), (100, 37, 3), (100, 37, 7), (384, 192, 2)])
+def test_products_against_the_mirror(nx, ny, n, years):
+    """100 x 37: 3 700 points per record, 925 groups of four -- no multiple of a lane's or a block's share."""
+    import torch
+    control = CONTROL[:n]
+    x = synth(years, n, ny, nx, seed=1000 + nx + 10 * n + years)
+    plan = clim.Plan(nx, ny, n, control=control)
+    got = reduce_dev(plan, torch.from_numpy(x).cuda())
+    same_bits(got, clim.reference(x, control), f"{nx}x{ny} n={n} years={years}")
+    for name in ("mean_resp", "seasons_resp"):  # a member without a control: NaN; every other value is a number
+        r = getattr(got, name)
+        for m, c in enumerate(control):
+            assert np.isnan(r[m]).all() if c < 0 else np.isfinite(r[m]).all(), (name, m)
+    plan.close()
+
+
+@pytest.mark.parametrize("nx,ny", [(96, 48), (100, 37)])
+def test_deterministic_and_independent_of_the_batch(nx, ny):
+    import torch
+    x = synth(3, 7, ny, nx, seed=77)
+    xd = torch.from_numpy(x).cuda()
+    plan = clim.Plan(nx, ny, 7, control=CONTROL)
+    a, b = reduce_dev(plan, xd), reduce_dev(plan, xd)
+    same_bits(a, b, "second call")
+    plan.close()
+    for m in (3, 5, 6):  # the member alone with its control: control 1 -> {1, 3}, 4 -> {4, 5}, 6 -> {6}
+        c = CONTROL[m]
+        members, ctl = ([m], [0]) if c == m else ([c, m], [-1, 0])
+        small = clim.Plan(nx, ny, len(members), control=ctl)
+        one = reduce_dev(small, xd[:, members].contiguous())
+        for name in NAMES:
+            assert np.array_equal(bits(getattr(one, name)[-1]), bits(getattr(a, name)[m])), (name, m)
+        small.close()
+
+
+@pytest.mark.parametrize("nx,ny", [(96, 48), (100, 37)])
+def test_each_single_flag_gives_the_numbers_of_the_full_call(nx, ny):
+    import torch
+    control = CONTROL[:5]
+    xd = torch.from_numpy(synth(3, 5, ny, nx, seed=9)).cuda()
+    full_plan = clim.Plan(nx, ny, 5, control=control)
+    assert full_plan.what == clim.ALL
+    full = reduce_dev(full_plan, xd)
+    full_plan.close()
+    cases = ((abi.C_MEAN, ("mean",)), (abi.C_SEASONS, ("seasons",)), (abi.C_TREND, ("trend",)),
+             (abi.C_MEAN | abi.C_RESPONSE, ("mean", "mean_resp")), (abi.C_SEASONS | abi.C_RESPONSE, ("seasons", "seasons_resp")))
+    for what, names in cases:
+        plan = clim.Plan(nx, ny, 5, control=control, what=what)
+        one = reduce_dev(plan, xd)
+        for name in NAMES:
+            if name in names:
+                assert np.array_equal(bits(getattr(one, name)), bits(getattr(full, name))), (what, name)
+            else:
+                assert getattr(one, name) is None, (what, name)
+        plan.close()
+
+
+def test_a_plan_is_reused_without_clearing():
+    """Five years, then two: the second result is a fresh plan's (year 0 stores, it does not add)."""
+    import torch
+    nx, ny, n = 100, 37, 3
+    x = synth(7, n, ny, nx, seed=31)
+    xd = torch.from_numpy(x).cuda()
+    used, fresh = clim.Plan(nx, ny, n, control=CONTROL[:n]), clim.Plan(nx, ny, n, control=CONTROL[:n])
+    first = reduce_dev(used, xd[:5])
+    second = reduce_dev(used, xd[5:])
+    same_bits(second, reduce_dev(fresh, xd[5:]), "reused plan")
+    same_bits(second, clim.reference(x[5:], CONTROL[:n]), "reused plan against the mirror")
+    same_bits(first, clim.reference(x[:5], CONTROL[:n]), "first period against the mirror")
+    with pytest.raises(engine.GrebError) as ei:  # the year count is the plan's: a wrong k is refused, the sums stay
+        clim.add_year_dev(used, xd[0], 1)
+    assert ei.value.code == -1 and "k = 1, but 0 years" in str(ei.value)
+    used.close(); fresh.close()
+
+
+def _same_engine_state(a, b, yr_a, yr_b):
+    assert np.array_equal(yr_a, yr_b), "yearly differs"
+    for m in range(a.nm):
+        assert np.array_equal(a.state(m), b.state(m)), f"state of member {m} differs"
+
+
+def _period(res, p):
+    return clim.Result(*[None if getattr(res, n) is None else getattr(res, n)[:, p] for n in NAMES])
+
+
+def test_run_clim_against_run(inputs, params):
+    """Twin engines, flux correction, then four scenario years through run() and run_clim() with the periods (0, 1) and
+    (2, 2): year 1 is integrated but not summed."""
+    co2 = np.array([[340.0] * 4, [680.0] * 4, [1020.0] * 4], np.float32)
+    control = [-1, 0, 0]
+    plan = clim.Plan(inputs.nx, inputs.ny, 3, control=control)
+    ea, eb, ec = (engine.Engine(inputs, params, n_members=3) for _ in range(3))
+    for e in (ea, eb, ec):
+        e.flux_correction(1)
+    mon, yr_a = ea.run(4, co2)
+    res = eb.run_clim(4, co2, plan, [(0, 1), (2, 2)])
+    assert res.mean.shape == res.trend.shape == res.mean_resp.shape == (3, 2, 12, 5, 48, 96)
+    assert res.seasons.shape == res.seasons_resp.shape == (3, 2, 5, 5, 48, 96)
+    years = np.moveaxis(mon, 1, 0)  # [year][member]...
+    same_bits(_period(res, 0), clim.reference(years[0:1], control), "run_clim period (0, 1)")
+    same_bits(_period(res, 1), clim.reference(years[2:4], control), "run_clim period (2, 2)")
+    _same_engine_state(ea, eb, yr_a, res.yearly)
+    # the same periods over two calls of two years each
+    r1 = ec.run_clim(2, co2[:, :2], plan, [(0, 1)])
+    r2 = ec.run_clim(2, co2[:, 2:], plan, [(0, 2)])
+    same_bits(_period(r1, 0), _period(res, 0), "two calls, first")
+    same_bits(_period(r2, 0), _period(res, 1), "two calls, second")
+    assert np.array_equal(np.concatenate([r1.yearly, r2.yearly], axis=1), res.yearly)
+    _same_engine_state(eb, ec, res.yearly[:, 2:], r2.yearly)
+    # and run() continues from a run_clim() as from a run()
+    mon_a, yr2_a = ea.run(1, 500.0)
+    mon_b, yr2_b = eb.run(1, 500.0)
+    assert np.array_equal(mon_a, mon_b) and np.array_equal(yr2_a, yr2_b)
+    for e in (ea, eb, ec):
+        e.close()
+    plan.close()
+
+
+def test_run_clim_against_run_any_grid(params):
+    inp = workload.make_inputs(192, 96)
+    plan = clim.Plan(192, 96, 1, what=abi.C_MEAN | abi.C_SEASONS)
+    ea, eb = engine.Engine(inp, params), engine.Engine(inp, params)
+    for e in (ea, eb):
+        e.flux_correction(1)
+    mon, yr_a = ea.run(1, 680.0)
+    res = eb.run_clim(1, 680.0, plan, [(0, 1)])
+    assert res.trend is None and res.mean_resp is None and res.seasons_resp is None
+    assert np.array_equal(bits(res.mean[:, 0]), bits(mon[:, 0])), "S / 1 = x: the mean of one year is run()'s record"
+    ref = clim.reference(np.moveaxis(mon, 1, 0), what=abi.C_MEAN | abi.C_SEASONS)
+    assert np.array_equal(bits(res.seasons[:, 0]), bits(ref.seasons))
+    _same_engine_state(ea, eb, yr_a, res.yearly)
+    ea.close(); eb.close(); plan.close()
+
+
+def test_run_clim_with_a_switch_member(inputs, params):
+    plan = clim.Plan(inputs.nx, inputs.ny, 2, what=abi.C_MEAN)
+    ea, eb = (engine.Engine(inputs, params, n_members=2) for _ in range(2))
+    for e in (ea, eb):
+        e.flux_correction(1)
+        e.set_member_experiments([0, abi.X_NO_ICE])
+    family = eb.describe()["kernel_family"]
+    mon, yr_a = ea.run(1, 680.0)
+    res = eb.run_clim(1, 680.0, plan, [(0, 1)])
+    assert np.array_equal(bits(res.mean[:, 0]), bits(mon[:, 0]))
+    assert not np.array_equal(mon[0, 0], mon[1, 0]), "the switch acts"
+    assert eb.describe()["kernel_family"] == family == ea.describe()["kernel_family"]
+    _same_engine_state(ea, eb, yr_a, res.yearly)
+    ea.close(); eb.close(); plan.close()
+
+
+def test_products_pinned_to_the_reference(inputs, params):
+    """tests/golden/run_short_g96.npz holds the reference's own 24 monthly records of this configuration.  A mean with
+    non-negative normalised weights cannot move further than its fields did, so MEAN and SEASONS over the two scenario
+    years lie within the year-and-day-weighted mean of max |engine field - reference field| of the mirror applied to the
+    REFERENCE's records (+ 1 ulp for the product's own rounding); the field difference is measured here from run() of a
+    twin engine -- no new tolerance."""
+    from conftest import load_golden
+    g = load_golden("run_short_g96.npz")["monthly"].reshape(2, 1, 12, 5, 48, 96)  # [year][member]...
+    plan = clim.Plan(96, 48, 1, what=abi.C_MEAN | abi.C_SEASONS)
+    ea, eb = engine.Engine(inputs, params), engine.Engine(inputs, params)
+    for e in (ea, eb):
+        e.flux_correction(1)
+    mon, _ = ea.run(2, 680.0)
+    res = eb.run_clim(2, 680.0, plan, [(0, 2)])
+    moved = np.abs(mon[0].astype(np.float64) - g[:, 0].astype(np.float64)).max(axis=(-2, -1))  # [year][month][var]
+    moved_mean = moved.mean(axis=0)  # [month][var]: the two years weigh alike
+    days = np.asarray(abi.JDAY_MON, np.float64)
+    ref = clim.reference(g, what=abi.C_MEAN | abi.C_SEASONS)
+    ulp = lambda r: np.spacing(np.abs(r)).astype(np.float64)
+    d_mean = np.abs(res.mean[0, 0].astype(np.float64) - ref.mean[0].astype(np.float64))
+    print(f"fields moved <= {moved.max(axis=(0, 1))}; mean {d_mean.max(axis=(0, 2, 3))} (per variable)")
+    assert (d_mean <= moved_mean[:, :, None, None] + ulp(ref.mean[0])).all()
+    for s, months in enumerate(clim.SEASON_MONTHS):
+        w = days[list(months)]
+        moved_season = (moved_mean[list(months)] * w[:, None]).sum(axis=0) / w.sum()  # [var]
+        d = np.abs(res.seasons[0, 0, s].astype(np.float64) - ref.seasons[0, s].astype(np.float64))
+        print(f"{clim.SEASONS[s]}: moved <= {moved_season}; seasons {d.max(axis=(1, 2))}")
+        assert (d <= moved_season[:, None, None] + ulp(ref.seasons[0, s])).all(), clim.SEASONS[s]
+    ea.close(); eb.close(); plan.close()
+
+
+def test_refused_calls_leave_the_engine_alone(inputs, params):
+    co2 = [[400.0] * 2, [800.0] * 2]
+    ea, eb = (engine.Engine(inputs, params, n_members=2) for _ in range(2))
+    other_grid, other_members, plan = clim.Plan(100, 37, 2), clim.Plan(96, 48, 3), clim.Plan(96, 48, 2)
+    for bad, periods, words in ((other_grid, [(0, 1)], ("100 x 37", "96 x 48")), (other_members, [(0, 1)], ("3 members", "has 2")),
+                                (plan, [(0, 2), (1, 1)], ("period 1", "overlaps period 0"))):
+        with pytest.raises(engine.GrebError) as ei:
+            ea.run_clim(2, co2, bad, periods)
+        assert ei.value.code == -1 and all(w in str(ei.value) for w in words), ei.value
+    for m in range(2):
+        assert np.array_equal(ea.state(m), eb.state(m))
+    ra, rb = ea.run_clim(2, co2, plan, [(0, 2)]), eb.run_clim(2, co2, plan, [(0, 2)])  # ... bit-identical to an untouched twin
+    same_bits(ra, rb, "after the refusals")
+    _same_engine_state(ea, eb, ra.yearly, rb.yearly)
+    for x in (ea, eb, other_grid, other_members, plan):
+        x.close()
+
+
+def test_tool_prints_one_json_line():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "run_clim.py"), "4", "2", "--compare", "--passes", "1"],
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = out.stdout.strip().splitlines()
+    res = json.loads(lines[-1])
+    assert len(lines) == 1 and res["members"] == 4 and res["years"] == 2 and res["finite"] is True
+    resp = res["global_mean_annual_tsurf_response_K"]
+    assert len(resp) == 4 and resp[0] is None and 0 < resp[1] < resp[2] < resp[3], "more CO2 than the control warms more"
+    assert res["run_clim"]["ensemble_years_per_s"] > 0 and res["run_diag_annual"]["ensemble_years_per_s"] > 0
+    assert res["bytes_delivered"] == 4 * (3 * 60 + 2 * 25) * 48 * 96 * 4  # five products of one period, whatever the years
+    # The host's version of the same product from run_diag's annual maps: those are rounded to fp32 before the control is
+    # subtracted, half an ulp of a value in [256, 512) K each (1.53e-5), so the two differ by at most 3.05e-5 + half an
+    # ulp of the response itself (2.4e-7 below 8 K) per point, and an area mean cannot differ by more than its points do.
+    assert res["max_abs_difference_to_host_average_K"] <= 3.08e-5
