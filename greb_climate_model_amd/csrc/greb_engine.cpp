@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <new>
@@ -132,9 +133,9 @@ struct greb_engine {
   bool fused = true;       // every member has the 96x48 default sub-cycling layout -> fused member kernel
   float *Xa = nullptr, *Xb = nullptr, *red = nullptr, *W2 = nullptr; // any-grid (multi-launch) engine work arrays
   hipStream_t stream = nullptr;
-  hipStream_t copy_stream = nullptr;               // device -> host delivery of the monthly means
-  hipEvent_t ev_done[2] = {nullptr, nullptr};      // year written into staging slot i
-  hipEvent_t ev_free[2] = {nullptr, nullptr};      // staging slot i copied out
+  hipStream_t copy_stream = nullptr;               // device -> host delivery of a scenario run's output units (run_years)
+  hipEvent_t ev_done[2] = {nullptr, nullptr};      // a unit is complete in output slot i (compute stream)
+  hipEvent_t ev_free[2] = {nullptr, nullptr};      // output slot i is copied out (copy stream)
   // device
   float *z_topo = nullptr, *glacier = nullptr, *sw_solar = nullptr;
   float *tclim = nullptr, *qclim = nullptr, *uclim = nullptr, *vclim = nullptr, *mldclim = nullptr,
@@ -240,17 +241,22 @@ void apply_forcing(const greb_engine* e, MemberArgs& a) {
   a.f_space = e->f_space; a.f_season = e->f_season; a.f_solar = e->f_solar;
 }
 
-// Scenario year y of a run of `years` (greb_engine_run, _run_budget, _run_diag): its five records go to year mon_y of
-// mon_years in `mon` and, where the run has a budget, its budget records to year bud_y of bud_years in `bud`.
-MemberArgs scenario_args(greb_engine* e, int years, int y, float* mon, int mon_years, int mon_y, float* bud = nullptr,
-                         int bud_years = 0, int bud_y = 0) {
+// Where a scenario year's records go: year mon_y of mon_years in `mon` and, where the run has a budget, its budget
+// records to year bud_y of bud_years in `bud`.
+struct YearOut {
+  float* mon; int mon_years, mon_y;
+  float* bud = nullptr; int bud_years = 0, bud_y = 0;
+};
+
+// Scenario year y of a run of `years` (run_years), its records going to `o`.
+MemberArgs scenario_args(greb_engine* e, int years, int y, const YearOut& o) {
   MemberArgs a = base_args(e);
   a.flux_phase = 0;
   a.it0 = e->it_scnr + 1 + (long long)y * kNT; a.nsteps = kNT;
   a.co2 = e->co2_dev; a.co2_stride = years; a.co2_year0 = y;
-  a.monthly = mon; a.monthly_years = mon_years; a.year_out0 = mon_y;
+  a.monthly = o.mon; a.monthly_years = o.mon_years; a.year_out0 = o.mon_y;
   a.yearly = e->yearly_dev; a.yearly_years = years; a.yearly_year0 = y;
-  if (bud) { a.bsum = e->bsum; a.brec = bud; a.brec_years = bud_years; a.brec_year0 = bud_y; }
+  if (o.bud) { a.bsum = e->bsum; a.brec = o.bud; a.brec_years = o.bud_years; a.brec_year0 = o.bud_y; }
   apply_forcing(e, a);
   return a;
 }
@@ -715,83 +721,157 @@ int create_engine(const char* who, const greb_params* p, int nx, int ny, const g
   return 0;
 }
 
-// greb_engine_run (budget == nullptr) and greb_engine_run_budget (budget != nullptr, monthly may be nullptr): `years`
-// scenario years, each year's records delivered to the caller.  With a budget the launches take the BUDGET instantiations
-// (MemberArgs::bsum set); what they leave in state, clock, monthly and yearly is what the default ones leave.
-int run_scenario(greb_engine* e, int years, const float* co2_ppm, float* monthly, float* budget, float* yearly,
-                 unsigned run_flags) {
+// ---------------------------------------------------------------- scenario runs: one driver, one sink per output kind
+// What the driver shares with greb_engine_flux_correction.  Before the first year of a call: the yearly scalars
+// [member][years][2], cleared on the compute stream.
+int clear_yearly(greb_engine* e, int years) {
+  const size_t n = (size_t)e->nm * years * 2;
+  if (int rc = ensure(e, &e->yearly_dev, &e->yearly_cap, n)) return rc;
+  HIP_TRY(e, hipMemsetAsync(e->yearly_dev, 0, n * sizeof(float), e->stream));
+  return 0;
+}
+// after the last year of a call is enqueued: wait for it, then ask the one-launch circulation calls whether one gave up
+int finish_years(greb_engine* e) {
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  return check_circulation(e);
+}
+int yearly_to_host(greb_engine* e, int years, float* yearly) {
+  if (yearly) HIP_TRY(e, hipMemcpy(yearly, e->yearly_dev, (size_t)e->nm * years * 2 * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// staging slot y & 1 of e->monthly_dev: one model year of every member's records, [member][12][5][np]
+size_t year_records(const greb_engine* e) { return (size_t)e->nm * 12 * 5 * (size_t)e->np; }
+float* staging_slot(const greb_engine* e, int y) { return e->monthly_dev + (size_t)(y & 1) * year_records(e); }
+
+// every member's record (`rec` floats) of unit u, from `dev` to its place in the caller's [member][n][rec] array
+hipError_t unit_to_host(greb_engine* e, float* host, int n, int u, const float* dev, size_t rec) {
+  return hipMemcpy2DAsync(host + (size_t)u * rec, (size_t)n * rec * sizeof(float), dev, rec * sizeof(float), rec * sizeof(float),
+                          (size_t)e->nm, hipMemcpyDeviceToHost, e->copy_stream);
+}
+
+// What run_years offers a sink's year().  A UNIT is what leaves for the host in one piece (a year's records, a period's
+// climatology): units complete in ascending order from 0, and unit u is made in output slot u & 1.
+struct YearCalls {
+  std::function<int(int y, const YearOut& o)> integrate; // enqueue scenario year y of every member, its records going to `o`
+  // for a sink that delivers:
+  std::function<int(int u)> writing;  // what the sink enqueues next writes output slot u & 1, for unit u
+  std::function<int(int u)> complete; // everything that makes unit u is enqueued: it may leave
+};
+
+// One output kind.  The driver knows nothing about what is delivered, a sink nothing about streams and events.
+struct RunSink {
+  std::function<int()> prepare;                     // ensure the sink's own device buffers, bring its plan onto the device
+  std::function<int(const YearCalls&, int y)> year; // enqueue year y and whatever consumes it
+  std::function<int(int u, int slot)> deliver;      // enqueue unit u's copies on e->copy_stream (unit_to_host); empty: nothing
+                                                    // leaves for the host, and the run makes no copy stream and no events
+  std::function<int()> finish;                      // optional: what is copied after the final sync
+};
+
+// `years` scenario years of every member; `s` says what is made of each year and where it goes.  Host delivery: a unit
+// leaves over PCIe on the copy stream while the following year integrates on the compute stream (two output slots, one
+// event pair each).  A pinned destination makes the copies true DMA; a pageable one is staged by the runtime and still
+// overlaps the kernels.
+int run_years(greb_engine* e, int years, const float* co2_ppm, float* yearly, const RunSink& s) {
   HIP_TRY(e, hipSetDevice(e->device));
+  const size_t nm = (size_t)e->nm;
+  if (int rc = ensure(e, &e->co2_dev, &e->co2_cap, nm * years)) return rc;
+  HIP_TRY(e, hipMemcpyAsync(e->co2_dev, co2_ppm, nm * years * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  if (int rc = clear_yearly(e, years)) return rc;
+  const bool delivers = (bool)s.deliver;
+  if (delivers) if (int rc = ensure(e, &e->monthly_dev, &e->monthly_cap, 2 * year_records(e))) return rc; // the staging slots
+  if (int rc = s.prepare()) { e->last_error = g_last_error; return rc; } // (a plan reports its failure without an engine)
+  if (delivers && !e->copy_stream) HIP_TRY(e, hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
+  for (int i = 0; delivers && i < 2; ++i) {
+    if (!e->ev_done[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_done[i], hipEventDisableTiming));
+    if (!e->ev_free[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_free[i], hipEventDisableTiming));
+  }
+  int completed = 0, delivered = 0; // units
+  YearCalls calls;
+  calls.integrate = [&](int y, const YearOut& o) -> int { return run_year(e, scenario_args(e, years, y, o), e->nm); };
+  // called where the SINK's first write to the slot is enqueued, so that nothing before it waits: a year whose records
+  // are reduced on the device does not stall its integration on the copy of unit u - 2's small products
+  calls.writing = [&](int u) -> int {
+    if (u >= 2) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_free[u & 1], 0)); // the slot's unit u - 2 has left
+    return 0;
+  };
+  calls.complete = [&](int u) -> int {
+    HIP_TRY(e, hipEventRecord(e->ev_done[u & 1], e->stream));
+    completed = u + 1;
+    return 0;
+  };
+  auto deliver = [&](int u) -> int {
+    HIP_TRY(e, hipStreamWaitEvent(e->copy_stream, e->ev_done[u & 1], 0));
+    if (int rc = s.deliver(u, u & 1)) return rc;
+    HIP_TRY(e, hipEventRecord(e->ev_free[u & 1], e->copy_stream));
+    return 0;
+  };
+  // an error anywhere below must not return while copies into the CALLER's buffers are still in flight (the caller
+  // may free them as soon as it sees the error): the body runs in a lambda and both streams are drained on failure
+  const int rc_years = [&]() -> int {
+    for (int y = 0; y < years; ++y) {
+      // what EARLIER years completed leaves AFTER this year's kernels are enqueued, so that even a copy the runtime
+      // performs synchronously (pageable destination) runs beside a kernel
+      const int before = completed;
+      if (int rc = s.year(calls, y)) return rc;
+      for (; delivered < before; ++delivered) if (int rc = deliver(delivered)) return rc;
+    }
+    for (; delivered < completed; ++delivered) if (int rc = deliver(delivered)) return rc;
+    if (delivers) HIP_TRY(e, hipStreamSynchronize(e->copy_stream));
+    return 0;
+  }();
+  if (rc_years && delivers) {
+    (void)hipStreamSynchronize(e->copy_stream);
+    (void)hipStreamSynchronize(e->stream);
+  }
+  if (rc_years) return rc_years;
+  if (int rc = finish_years(e)) return rc;
+  e->it_scnr += (long long)years * kNT;
+  if (s.finish) if (int rc = s.finish()) return rc;
+  return yearly_to_host(e, years, yearly);
+}
+
+// The records sink: greb_engine_run (budget == nullptr) and greb_engine_run_budget (budget != nullptr, monthly may be
+// nullptr).  A unit is a year: its five records and, with a budget, its budget records.  With a budget the launches take
+// the BUDGET instantiations (MemberArgs::bsum set); what they leave in state, clock, monthly and yearly is what the
+// default ones leave.
+int run_records(greb_engine* e, int years, const float* co2_ppm, float* monthly, float* budget, float* yearly,
+                unsigned run_flags) {
   const size_t np = (size_t)e->np, nm = (size_t)e->nm;
   const size_t rec_year = 12 * 5 * np, bud_year = (size_t)12 * GREB_NBUDGET * np; // floats per member-year
   const bool dev_out = (run_flags & GREB_RUN_DEVICE_OUT) != 0;
-  if (int rc = ensure(e, &e->co2_dev, &e->co2_cap, nm * years)) return rc;
-  HIP_TRY(e, hipMemcpyAsync(e->co2_dev, co2_ppm, nm * years * sizeof(float), hipMemcpyHostToDevice, e->stream));
-  if (int rc = ensure(e, &e->yearly_dev, &e->yearly_cap, nm * years * 2)) return rc;
-  HIP_TRY(e, hipMemsetAsync(e->yearly_dev, 0, nm * years * 2 * sizeof(float), e->stream));
-  const size_t slot = nm * rec_year, bslot = nm * bud_year;
-  if (dev_out) {
+  auto budget_slot = [&](int y) { return e->budget_dev + (size_t)(y & 1) * nm * bud_year; }; // as staging_slot
+  RunSink s;
+  s.prepare = [&]() -> int {
+    if (!budget) return 0;
+    if (!e->bsum) { // zero from here on: every December ends with the sums cleared
+      HIP_TRY(e, dev_alloc(&e->bsum, nm * GREB_NBUDGET * np));
+      HIP_TRY(e, hipMemsetAsync(e->bsum, 0, nm * GREB_NBUDGET * np * sizeof(float), e->stream));
+    }
+    ++e->budget_runs;
+    if (!dev_out) return ensure(e, &e->budget_dev, &e->budget_cap, 2 * nm * bud_year);
     // (a budget-only run: the kernels write their five records regardless -- into one staging slot nobody reads)
-    if (!monthly) if (int rc = ensure(e, &e->monthly_dev, &e->monthly_cap, slot)) return rc;
-    for (int y = 0; y < years; ++y) {
-      const MemberArgs a = monthly ? scenario_args(e, years, y, monthly, years, y, budget, years, y)
-                                   : scenario_args(e, years, y, e->monthly_dev, 1, 0, budget, years, y);
-      if (int rc = run_year(e, a, e->nm)) return rc;
-    }
-  } else {
-    // Host delivery: year y's records leave over PCIe on the copy stream while year y+1 integrates on the compute
-    // stream (two staging slots of one model year each, [member][12][5][np], and the same of budget records); the host
-    // side is strided by the caller's [member][years] layout.  A pinned destination makes the copies true DMA; a
-    // pageable one is staged by the runtime and still overlaps the kernels.
-    if (int rc = ensure(e, &e->monthly_dev, &e->monthly_cap, 2 * slot)) return rc;
-    if (budget) if (int rc = ensure(e, &e->budget_dev, &e->budget_cap, 2 * bslot)) return rc;
-    if (!e->copy_stream) HIP_TRY(e, hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-      if (!e->ev_done[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_done[i], hipEventDisableTiming));
-      if (!e->ev_free[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_free[i], hipEventDisableTiming));
-    }
-    // copy of year y: issued AFTER year y+1's kernels are enqueued, so that even a copy the runtime performs
-    // synchronously (pageable destination) runs beside a kernel
-    auto deliver = [&](int y) -> int {
-      const int sl = y & 1;
-      HIP_TRY(e, hipStreamWaitEvent(e->copy_stream, e->ev_done[sl], 0));
-      if (monthly)
-        HIP_TRY(e, hipMemcpy2DAsync(monthly + (size_t)y * rec_year, (size_t)years * rec_year * sizeof(float),
-                                    e->monthly_dev + (size_t)sl * slot, rec_year * sizeof(float), rec_year * sizeof(float),
-                                    nm, hipMemcpyDeviceToHost, e->copy_stream));
-      if (budget)
-        HIP_TRY(e, hipMemcpy2DAsync(budget + (size_t)y * bud_year, (size_t)years * bud_year * sizeof(float),
-                                    e->budget_dev + (size_t)sl * bslot, bud_year * sizeof(float), bud_year * sizeof(float),
-                                    nm, hipMemcpyDeviceToHost, e->copy_stream));
-      HIP_TRY(e, hipEventRecord(e->ev_free[sl], e->copy_stream));
-      return 0;
+    return monthly ? 0 : ensure(e, &e->monthly_dev, &e->monthly_cap, year_records(e));
+  };
+  if (dev_out) { // the kernels write the caller's device arrays, [member][years]
+    s.year = [&](const YearCalls& run, int y) -> int {
+      return run.integrate(y, monthly ? YearOut{monthly, years, y, budget, years, y} : YearOut{e->monthly_dev, 1, 0, budget, years, y});
     };
-    // an error anywhere below must not return while copies into the CALLER's buffer are still in flight (the caller
-    // may free it as soon as it sees the error): the body runs in a lambda and both streams are drained on failure
-    const int rc_years = [&]() -> int {
-    for (int y = 0; y < years; ++y) {
-      const int sl = y & 1;
-      if (y >= 2) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_free[sl], 0)); // slot's previous year has left
-      const MemberArgs a = scenario_args(e, years, y, e->monthly_dev + (size_t)sl * slot, 1, 0,
-                                         budget ? e->budget_dev + (size_t)sl * bslot : nullptr, 1, 0);
-      if (int rc = run_year(e, a, e->nm)) return rc;
-      HIP_TRY(e, hipEventRecord(e->ev_done[sl], e->stream));
-      if (y > 0) if (int rc = deliver(y - 1)) return rc;
-    }
-    if (int rc = deliver(years - 1)) return rc;
-    HIP_TRY(e, hipStreamSynchronize(e->copy_stream));
-    return 0;
-    }();
-    if (rc_years) {
-      (void)hipStreamSynchronize(e->copy_stream);
-      (void)hipStreamSynchronize(e->stream);
-      return rc_years;
-    }
+    return run_years(e, years, co2_ppm, yearly, s);
   }
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  if (int rc = check_circulation(e)) return rc;
-  e->it_scnr += (long long)years * kNT;
-  if (yearly) HIP_TRY(e, hipMemcpy(yearly, e->yearly_dev, nm * years * 2 * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
+  // the staging slot IS the output slot: the year's own kernels write it, so here -- and only here -- the year itself
+  // waits until the slot's year y - 2 has left
+  s.year = [&](const YearCalls& run, int y) -> int {
+    if (int rc = run.writing(y)) return rc;
+    if (int rc = run.integrate(y, {staging_slot(e, y), 1, 0, budget ? budget_slot(y) : nullptr, 1, 0})) return rc;
+    return run.complete(y);
+  };
+  s.deliver = [&](int y, int sl) -> int {
+    if (monthly) HIP_TRY(e, unit_to_host(e, monthly, years, y, staging_slot(e, sl), rec_year));
+    if (budget) HIP_TRY(e, unit_to_host(e, budget, years, y, budget_slot(sl), bud_year));
+    return 0;
+  };
+  return run_years(e, years, co2_ppm, yearly, s);
 }
 } // namespace
 
@@ -849,8 +929,7 @@ int greb_engine_flux_correction(greb_engine* e, int years, float* yearly) {
   HIP_TRY(e, hipSetDevice(e->device));
   const size_t np = (size_t)e->np;
   const int nrun = e->shared_corr ? 1 : e->nm; // identical members: integrate one, broadcast
-  if (int rc = ensure(e, &e->yearly_dev, &e->yearly_cap, (size_t)e->nm * years * 2)) return rc;
-  HIP_TRY(e, hipMemsetAsync(e->yearly_dev, 0, (size_t)e->nm * years * 2 * sizeof(float), e->stream));
+  if (int rc = clear_yearly(e, years)) return rc;
   for (int y = 0; y < years; ++y) {
     MemberArgs a = base_args(e);
     a.flux_phase = 1;
@@ -864,35 +943,25 @@ int greb_engine_flux_correction(greb_engine* e, int years, float* yearly) {
       HIP_TRY(e, hipMemcpyAsync(e->state + (size_t)m * 5 * np, e->state, 5 * np * sizeof(float),
                                 hipMemcpyDeviceToDevice, e->stream));
   }
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  if (int rc = check_circulation(e)) return rc;
+  if (int rc = finish_years(e)) return rc;
   e->it_flux += (long long)years * kNT;
-  if (yearly) {
-    HIP_TRY(e, hipMemcpy(yearly, e->yearly_dev, (size_t)e->nm * years * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    if (e->shared_corr)
-      for (int m = 1; m < e->nm; ++m) std::memcpy(yearly + (size_t)m * years * 2, yearly, (size_t)years * 2 * sizeof(float));
-  }
+  if (int rc = yearly_to_host(e, years, yearly)) return rc;
+  if (yearly && e->shared_corr)
+    for (int m = 1; m < e->nm; ++m) std::memcpy(yearly + (size_t)m * years * 2, yearly, (size_t)years * 2 * sizeof(float));
   return 0;
 }
 
 int greb_engine_run(greb_engine* e, int years, const float* co2_ppm, float* monthly, float* yearly,
                     unsigned run_flags) {
   if (!e || years < 1 || !co2_ppm || !monthly) return fail(e, GREB_E_INVALID, "run: bad argument");
-  return run_scenario(e, years, co2_ppm, monthly, nullptr, yearly, run_flags);
+  return run_records(e, years, co2_ppm, monthly, nullptr, yearly, run_flags);
 }
 
 int greb_engine_run_budget(greb_engine* e, int years, const float* co2_ppm, float* monthly, float* budget, float* yearly,
                            unsigned run_flags) {
   if (!e || years < 1 || !co2_ppm) return fail(e, GREB_E_INVALID, "run_budget: bad argument (engine, years or co2_ppm)");
   if (!budget) return fail(e, GREB_E_INVALID, "run_budget: `budget` is NULL (greb_engine_run is the run without budget output)");
-  HIP_TRY(e, hipSetDevice(e->device));
-  if (!e->bsum) { // zero from here on: every December ends with the sums cleared
-    const size_t n = (size_t)e->nm * GREB_NBUDGET * e->np;
-    HIP_TRY(e, dev_alloc(&e->bsum, n));
-    HIP_TRY(e, hipMemsetAsync(e->bsum, 0, n * sizeof(float), e->stream));
-  }
-  ++e->budget_runs;
-  return run_scenario(e, years, co2_ppm, monthly, budget, yearly, run_flags);
+  return run_records(e, years, co2_ppm, monthly, budget, yearly, run_flags);
 }
 
 const char* greb_budget_name(int i) {
@@ -1058,73 +1127,40 @@ int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_d
   if (d->nx != e->nx || d->ny != e->ny)
     return fail(e, GREB_E_INVALID, "run_diag: the plan's grid " + std::to_string(d->nx) + " x " + std::to_string(d->ny) +
                                        " differs from the engine's " + std::to_string(e->nx) + " x " + std::to_string(e->ny));
-  HIP_TRY(e, hipSetDevice(e->device));
   const size_t np = (size_t)e->np, nm = (size_t)e->nm;
-  const size_t rec_year = 12 * 5 * np; // floats per member-year
-  const size_t slot = nm * rec_year;
   const bool do_r = (what & GREB_D_REGIONS) != 0, do_z = (what & GREB_D_ZONAL) != 0, do_a = (what & GREB_D_ANNUAL) != 0;
   const size_t reg_year = (size_t)12 * 5 * d->nr, zon_year = (size_t)12 * 5 * e->ny, ann_year = 5 * np; // floats per member-year
   const size_t zon_slot = do_z ? nm * zon_year : 0, ann_slot = do_a ? nm * ann_year : 0, out_slot = zon_slot + ann_slot;
-  if (int rc = ensure(e, &e->co2_dev, &e->co2_cap, nm * years)) return rc;
-  HIP_TRY(e, hipMemcpyAsync(e->co2_dev, co2_ppm, nm * years * sizeof(float), hipMemcpyHostToDevice, e->stream));
-  if (int rc = ensure(e, &e->yearly_dev, &e->yearly_cap, nm * years * 2)) return rc;
-  HIP_TRY(e, hipMemsetAsync(e->yearly_dev, 0, nm * years * 2 * sizeof(float), e->stream));
-  // On the device: the two one-year staging slots of greb_engine_run, the zonal means and annual maps of two years, and
-  // -- the only thing that grows with `years` besides the yearly scalars -- the region series.
-  if (int rc = ensure(e, &e->monthly_dev, &e->monthly_cap, 2 * slot)) return rc;
-  if (out_slot) if (int rc = ensure(e, &e->diag_out, &e->diag_out_cap, 2 * out_slot)) return rc;
-  if (do_r) if (int rc = ensure(e, &e->diag_reg, &e->diag_reg_cap, nm * years * reg_year)) return rc;
   greb_diag::Dev* dv = nullptr;
-  if (int rc = diag_on_device(d, e->device, e->nm, do_r, &dv)) { e->last_error = g_last_error; return rc; }
-  if (!e->copy_stream) HIP_TRY(e, hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-  for (int i = 0; i < 2; ++i) {
-    if (!e->ev_done[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_done[i], hipEventDisableTiming));
-    if (!e->ev_free[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_free[i], hipEventDisableTiming));
-  }
-  // year y's zonal means and annual maps leave on the copy stream while year y + 1 integrates, as the monthly records do
-  // in greb_engine_run; the host side is strided by the caller's [member][years] layout
-  auto deliver = [&](int y) -> int {
-    const int sl = y & 1;
+  // A unit is a year's zonal means and annual maps, made in output slot y & 1 of e->diag_out.  The region series -- the
+  // only thing on the device that grows with `years` besides the yearly scalars -- stays there for the whole call.
+  RunSink s;
+  s.prepare = [&]() -> int {
+    if (out_slot) if (int rc = ensure(e, &e->diag_out, &e->diag_out_cap, 2 * out_slot)) return rc;
+    if (do_r) if (int rc = ensure(e, &e->diag_reg, &e->diag_reg_cap, nm * years * reg_year)) return rc;
+    return diag_on_device(d, e->device, e->nm, do_r, &dv);
+  };
+  s.year = [&](const YearCalls& run, int y) -> int {
+    float* mon = staging_slot(e, y);
+    if (int rc = run.integrate(y, {mon, 1, 0})) return rc;
+    if (int rc = run.writing(y)) return rc; // (here, not before the year: only the reduction writes the slot)
+    float* out = out_slot ? e->diag_out + (size_t)(y & 1) * out_slot : nullptr;
+    const DiagArgs g = diag_args(d, dv, mon, do_r ? e->diag_reg + (size_t)y * reg_year : nullptr, (size_t)years * reg_year,
+                                 do_z ? out : nullptr, do_a ? out + zon_slot : nullptr);
+    HIP_TRY(e, launch_diag_year(g, e->nm, e->stream));
+    return run.complete(y);
+  };
+  s.deliver = [&](int y, int sl) -> int {
     float* out = e->diag_out + (size_t)sl * out_slot;
-    HIP_TRY(e, hipStreamWaitEvent(e->copy_stream, e->ev_done[sl], 0));
-    if (do_z)
-      HIP_TRY(e, hipMemcpy2DAsync(zonal + (size_t)y * zon_year, (size_t)years * zon_year * sizeof(float), out,
-                                  zon_year * sizeof(float), zon_year * sizeof(float), nm, hipMemcpyDeviceToHost, e->copy_stream));
-    if (do_a)
-      HIP_TRY(e, hipMemcpy2DAsync(annual + (size_t)y * ann_year, (size_t)years * ann_year * sizeof(float), out + zon_slot,
-                                  ann_year * sizeof(float), ann_year * sizeof(float), nm, hipMemcpyDeviceToHost, e->copy_stream));
-    HIP_TRY(e, hipEventRecord(e->ev_free[sl], e->copy_stream));
+    if (do_z) HIP_TRY(e, unit_to_host(e, zonal, years, y, out, zon_year));
+    if (do_a) HIP_TRY(e, unit_to_host(e, annual, years, y, out + zon_slot, ann_year));
     return 0;
   };
-  // as in greb_engine_run: no return while copies into the CALLER's buffers are in flight
-  const int rc_years = [&]() -> int {
-    for (int y = 0; y < years; ++y) {
-      const int sl = y & 1;
-      const MemberArgs a = scenario_args(e, years, y, e->monthly_dev + (size_t)sl * slot, 1, 0);
-      if (int rc = run_year(e, a, e->nm)) return rc;
-      if (y >= 2) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_free[sl], 0)); // the slot's products of year y - 2 have left
-      float* out = out_slot ? e->diag_out + (size_t)sl * out_slot : nullptr;
-      const DiagArgs g = diag_args(d, dv, a.monthly, do_r ? e->diag_reg + (size_t)y * reg_year : nullptr, (size_t)years * reg_year,
-                                   do_z ? out : nullptr, do_a ? out + zon_slot : nullptr);
-      HIP_TRY(e, launch_diag_year(g, e->nm, e->stream));
-      HIP_TRY(e, hipEventRecord(e->ev_done[sl], e->stream));
-      if (y > 0) if (int rc = deliver(y - 1)) return rc;
-    }
-    if (int rc = deliver(years - 1)) return rc;
-    HIP_TRY(e, hipStreamSynchronize(e->copy_stream));
+  s.finish = [&]() -> int {
+    if (do_r) HIP_TRY(e, hipMemcpy(regions, e->diag_reg, nm * years * reg_year * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
-  }();
-  if (rc_years) {
-    (void)hipStreamSynchronize(e->copy_stream);
-    (void)hipStreamSynchronize(e->stream);
-    return rc_years;
-  }
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  if (int rc = check_circulation(e)) return rc;
-  e->it_scnr += (long long)years * kNT;
-  if (do_r) HIP_TRY(e, hipMemcpy(regions, e->diag_reg, nm * years * reg_year * sizeof(float), hipMemcpyDeviceToHost));
-  if (yearly) HIP_TRY(e, hipMemcpy(yearly, e->yearly_dev, nm * years * 2 * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
+  };
+  return run_years(e, years, co2_ppm, yearly, s);
 }
 
 } // extern "C"
@@ -1324,78 +1360,38 @@ int greb_engine_run_clim(greb_engine* e, int years, const float* co2_ppm, greb_c
   if (c->nm != e->nm)
     return fail(e, GREB_E_INVALID, "run_clim: the plan is for " + std::to_string(c->nm) + " members, the engine has " +
                                        std::to_string(e->nm));
-  HIP_TRY(e, hipSetDevice(e->device));
   const size_t nm = (size_t)e->nm;
-  const size_t slot = nm * 12 * 5 * (size_t)e->np; // one model year of records
   size_t at[5], out_slot = 0; // where each product sits in an output slot: [member][its record], 16-byte aligned (np % 4 == 0)
   for (int i = 0; i < 5; ++i) { at[i] = out_slot; out_slot += nm * size[i]; }
-  if (int rc = ensure(e, &e->co2_dev, &e->co2_cap, nm * years)) return rc;
-  HIP_TRY(e, hipMemcpyAsync(e->co2_dev, co2_ppm, nm * years * sizeof(float), hipMemcpyHostToDevice, e->stream));
-  if (int rc = ensure(e, &e->yearly_dev, &e->yearly_cap, nm * years * 2)) return rc;
-  HIP_TRY(e, hipMemsetAsync(e->yearly_dev, 0, nm * years * 2 * sizeof(float), e->stream));
-  // On the device: the two one-year staging slots of greb_engine_run, the plan's sums, and two output slots of one
-  // period's products each.  Nothing of it grows with `years` or `n_periods` (besides the yearly scalars).
-  if (int rc = ensure(e, &e->monthly_dev, &e->monthly_cap, 2 * slot)) return rc;
-  if (int rc = ensure(e, &e->clim_out, &e->clim_out_cap, 2 * out_slot)) return rc;
   greb_clim::Dev* dv = nullptr;
-  if (int rc = clim_on_device(c, e->device, &dv)) { e->last_error = g_last_error; return rc; }
-  if (!e->copy_stream) HIP_TRY(e, hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-  for (int i = 0; i < 2; ++i) {
-    if (!e->ev_done[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_done[i], hipEventDisableTiming));
-    if (!e->ev_free[i]) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_free[i], hipEventDisableTiming));
-  }
-  // period p's products leave from output slot p & 1 on the copy stream while the following years integrate (the event
-  // pairs of greb_engine_run, here per output slot); the host side is strided by the caller's [member][period] layout
-  auto deliver = [&](int p) -> int {
-    const int sl = p & 1;
-    HIP_TRY(e, hipStreamWaitEvent(e->copy_stream, e->ev_done[sl], 0));
+  int p = 0; // the period the current year is in or before
+  // A unit is a period's products, made in output slot p & 1 of e->clim_out.  Nothing on the device grows with `years`
+  // or `n_periods` (besides the yearly scalars).
+  RunSink s;
+  s.prepare = [&]() -> int {
+    if (int rc = ensure(e, &e->clim_out, &e->clim_out_cap, 2 * out_slot)) return rc;
+    return clim_on_device(c, e->device, &dv);
+  };
+  s.year = [&](const YearCalls& run, int y) -> int {
+    float* mon = staging_slot(e, y);
+    if (int rc = run.integrate(y, {mon, 1, 0})) return rc;
+    while (p < n_periods && y >= first_year[p] + n_years[p]) ++p;
+    if (p >= n_periods || y < first_year[p]) return 0; // (a year outside every period is integrated, not summed)
+    const int k = y - first_year[p];
+    HIP_TRY(e, launch_clim_add_year(mon, dv->S, dv->T, c->elems(), k, e->stream));
+    if (k < n_years[p] - 1) return 0;
+    if (int rc = run.writing(p)) return rc; // (here, not before the year: only the finish pass writes the slot)
+    float* out[5];
+    for (int i = 0; i < 5; ++i) out[i] = size[i] ? e->clim_out + (size_t)(p & 1) * out_slot + at[i] : nullptr;
+    HIP_TRY(e, launch_clim_finish(clim_finish_args(c, dv, n_years[p], out), e->nm, e->stream));
+    return run.complete(p);
+  };
+  s.deliver = [&](int u, int sl) -> int {
     for (int i = 0; i < 5; ++i)
-      if (size[i])
-        HIP_TRY(e, hipMemcpy2DAsync(host[i] + (size_t)p * size[i], (size_t)n_periods * size[i] * sizeof(float),
-                                    e->clim_out + (size_t)sl * out_slot + at[i], size[i] * sizeof(float), size[i] * sizeof(float), nm,
-                                    hipMemcpyDeviceToHost, e->copy_stream));
-    HIP_TRY(e, hipEventRecord(e->ev_free[sl], e->copy_stream));
+      if (size[i]) HIP_TRY(e, unit_to_host(e, host[i], n_periods, u, e->clim_out + (size_t)sl * out_slot + at[i], size[i]));
     return 0;
   };
-  // as in greb_engine_run: no return while copies into the CALLER's buffers are in flight
-  const int rc_years = [&]() -> int {
-    int p = 0, finished = 0, delivered = 0; // the period year y is in or before; periods finished; periods delivered
-    for (int y = 0; y < years; ++y) {
-      const MemberArgs a = scenario_args(e, years, y, e->monthly_dev + (size_t)(y & 1) * slot, 1, 0);
-      if (int rc = run_year(e, a, e->nm)) return rc;
-      while (p < n_periods && y >= first_year[p] + n_years[p]) ++p;
-      if (p < n_periods && y >= first_year[p]) { // (a year outside every period is integrated, not summed)
-        const int k = y - first_year[p];
-        HIP_TRY(e, launch_clim_add_year(a.monthly, dv->S, dv->T, c->elems(), k, e->stream));
-        if (k == n_years[p] - 1) {
-          const int sl = p & 1;
-          if (p >= 2) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_free[sl], 0)); // the slot's products of period p - 2 have left
-          float* out[5];
-          for (int i = 0; i < 5; ++i) out[i] = size[i] ? e->clim_out + (size_t)sl * out_slot + at[i] : nullptr;
-          HIP_TRY(e, launch_clim_finish(clim_finish_args(c, dv, n_years[p], out), e->nm, e->stream));
-          HIP_TRY(e, hipEventRecord(e->ev_done[sl], e->stream));
-          finished = p + 1;
-        }
-      }
-      // a period that ended with an EARLIER year leaves now, with this year's kernels already enqueued (so that even a
-      // copy the runtime performs synchronously runs beside a kernel)
-      const int ready = (finished > 0 && first_year[finished - 1] + n_years[finished - 1] - 1 == y) ? finished - 1 : finished;
-      for (; delivered < ready; ++delivered) if (int rc = deliver(delivered)) return rc;
-    }
-    for (; delivered < finished; ++delivered) if (int rc = deliver(delivered)) return rc;
-    HIP_TRY(e, hipStreamSynchronize(e->copy_stream));
-    return 0;
-  }();
-  if (rc_years) {
-    (void)hipStreamSynchronize(e->copy_stream);
-    (void)hipStreamSynchronize(e->stream);
-    return rc_years;
-  }
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  if (int rc = check_circulation(e)) return rc;
-  e->it_scnr += (long long)years * kNT;
-  if (yearly) HIP_TRY(e, hipMemcpy(yearly, e->yearly_dev, nm * years * 2 * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
+  return run_years(e, years, co2_ppm, yearly, s);
 }
 
 const char* greb_engine_describe(greb_engine* e) {

@@ -211,13 +211,17 @@ class Engine:
         _check(lib().greb_engine_flux_correction(self.h, int(years), abi.fptr(yearly)), self.h)
         return yearly[:, :years]
 
+    def _run_arrays(self, years: int, co2_ppm):
+        """What every run* call hands the library: co2 [n_members][years] and the zeroed yearly [n_members][years][2]."""
+        co2 = np.ascontiguousarray(np.broadcast_to(np.asarray(co2_ppm, np.float32), (self.nm, years)))
+        return co2, np.zeros((self.nm, years, 2), np.float32)
+
     def run(self, years: int, co2_ppm, monthly_dev_ptr: int | None = None, out: np.ndarray | None = None):
         """co2_ppm: scalar, [years] or [n_members][years].  Returns (monthly, yearly); with
         monthly_dev_ptr (a device address) the monthly means stay on the GPU and monthly is None.
         out: caller-owned host buffer for the monthly means (float32, C-contiguous, n_members*years*12*5*np
         elements -- e.g. the numpy view of a pinned torch tensor, which makes the delivery a true DMA)."""
-        co2 = np.ascontiguousarray(np.broadcast_to(np.asarray(co2_ppm, np.float32), (self.nm, years)))
-        yearly = np.zeros((self.nm, years, 2), np.float32)
+        co2, yearly = self._run_arrays(years, co2_ppm)
         if monthly_dev_ptr is None:
             shape = (self.nm, years, 12, 5, self.ny, self.nx)
             if out is None:
@@ -239,8 +243,7 @@ class Engine:
         [n_members][years][12][13][ny][nx]; monthly is None with want_monthly=False (a budget-only run).  State, clock,
         monthly and yearly are those of run() over the same years.  With budget_dev_ptr (a device address) the records
         stay on the GPU (GREB_RUN_DEVICE_OUT: monthly then goes to monthly_dev_ptr, or nowhere) and both are None."""
-        co2 = np.ascontiguousarray(np.broadcast_to(np.asarray(co2_ppm, np.float32), (self.nm, years)))
-        yearly = np.zeros((self.nm, years, 2), np.float32)
+        co2, yearly = self._run_arrays(years, co2_ppm)
         f = lib().greb_engine_run_budget
         if budget_dev_ptr is not None:
             _check(f(self.h, int(years), abi.fptr(co2), None if monthly_dev_ptr is None else C.c_void_p(monthly_dev_ptr),
@@ -261,8 +264,7 @@ class Engine:
         not selected is None).  State, clock and yearly are those of run() over the same years."""
         from . import diag
         what = diag.ALL if what is None else int(what)
-        co2 = np.ascontiguousarray(np.broadcast_to(np.asarray(co2_ppm, np.float32), (self.nm, years)))
-        yearly = np.zeros((self.nm, years, 2), np.float32)
+        co2, yearly = self._run_arrays(years, co2_ppm)
         regions = np.empty((self.nm, years, 12, 5, plan.nr), np.float32) if what & abi.D_REGIONS else None
         zonal = np.empty((self.nm, years, 12, 5, self.ny), np.float32) if what & abi.D_ZONAL else None
         annual = np.empty((self.nm, years, 5, self.ny, self.nx), np.float32) if what & abi.D_ANNUAL else None
@@ -277,8 +279,7 @@ class Engine:
         are integrated but not summed (greb_engine_run_clim).  Returns a clim.Result of arrays [n_members][n_periods]...
         (a product the plan does not select is None).  State, clock and yearly are those of run() over the same years."""
         from . import clim
-        co2 = np.ascontiguousarray(np.broadcast_to(np.asarray(co2_ppm, np.float32), (self.nm, years)))
-        yearly = np.zeros((self.nm, years, 2), np.float32)
+        co2, yearly = self._run_arrays(years, co2_ppm)
         per = np.ascontiguousarray(periods, np.int32).reshape(-1, 2)
         first, count = np.ascontiguousarray(per[:, 0]), np.ascontiguousarray(per[:, 1])
         out = clim.empty_products(plan.what, (self.nm, len(per)), self.ny, self.nx)

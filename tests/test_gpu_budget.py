@@ -7,7 +7,7 @@
 4. A member's switches zero the terms of the processes they switch off; a member equals its one-member engine.
 5. Call patterns: split calls, run / run_budget alternating, budget-only, device-out.
 6. Errors.
-Every case: 1 flux-correction year + 1 or 2 scenario years on the synthetic workload."""
+Every case: 1 flux-correction year + 1 or 2 scenario years on the synthetic workload (5 where staging slots are to be reused)."""
 import numpy as np
 import pytest
 
@@ -283,6 +283,66 @@ def test_budget_only_and_device_out_equal_the_host_form(eng_mod, params, inputs,
         assert np.array_equal(dbud.cpu().numpy(), bud) and np.array_equal(yr_c, yr), with_monthly
         if with_monthly:
             assert np.array_equal(dmon.cpu().numpy(), mon)
+
+
+def _one_member(eng_mod, inputs, params):
+    e = eng_mod.Engine(inputs, params)
+    e.flux_correction(1)
+    return e
+
+
+RAMP = np.asarray([[340.0, 400.0, 480.0, 560.0, CO2]], np.float32)  # five years: every staging slot is written again, in both parities
+
+
+def test_five_budget_years_host_device_out_and_run(eng_mod, params, inputs):
+    """One member, five years whose CO2 differs: the host-delivered records (each year leaves from a staging slot that
+    year y + 2 writes again) are the ones the kernels write straight into device arrays, and run()'s."""
+    import torch
+    a = _one_member(eng_mod, inputs, params)
+    mon, bud, yr = a.run_budget(5, RAMP)
+    sa = states(a)
+    a.close()
+    assert not any(np.array_equal(bud[:, y], bud[:, y + 1]) for y in range(4))
+    c = _one_member(eng_mod, inputs, params)
+    dbud = torch.full(bud.shape, float("nan"), dtype=torch.float32, device="cuda")
+    dmon = torch.full(mon.shape, float("nan"), dtype=torch.float32, device="cuda")
+    _, _, yr_c = c.run_budget(5, RAMP, budget_dev_ptr=dbud.data_ptr(), monthly_dev_ptr=dmon.data_ptr())
+    torch.cuda.synchronize()
+    sc = states(c)
+    c.close()
+    assert np.array_equal(dbud.cpu().numpy(), bud) and np.array_equal(dmon.cpu().numpy(), mon)
+    assert np.array_equal(yr_c, yr) and np.array_equal(sc, sa)
+    d = _one_member(eng_mod, inputs, params)
+    mon_d, yr_d = d.run(5, RAMP)
+    sd = states(d)
+    d.close()
+    assert np.array_equal(mon_d, mon) and np.array_equal(yr_d, yr) and np.array_equal(sd, sa)
+    b = _one_member(eng_mod, inputs, params)
+    none, only, yr_b = b.run_budget(5, RAMP, want_monthly=False)
+    b.close()
+    assert none is None and np.array_equal(only, bud) and np.array_equal(yr_b, yr)
+
+
+def test_five_run_years_pinned_pageable_and_device_out(eng_mod, params, inputs):
+    """run() of one member over the same five years: delivered into a pinned buffer (true DMA), into a pageable one (staged
+    by the runtime) and written by the kernels into a device array -- identical records, yearly values and state."""
+    import torch
+    shape = (1, 5, 12, 5, inputs.ny, inputs.nx)
+    pinned = torch.full(shape, float("nan"), dtype=torch.float32).pin_memory()
+    assert pinned.is_pinned()
+    pageable = np.full(shape, np.nan, np.float32)
+    dev = torch.full(shape, float("nan"), dtype=torch.float32, device="cuda")
+    got = []
+    for kw in ({"out": pinned.numpy()}, {"out": pageable}, {"monthly_dev_ptr": dev.data_ptr()}):
+        e = _one_member(eng_mod, inputs, params)
+        _, yr = e.run(5, RAMP, **kw)
+        torch.cuda.synchronize()
+        got.append((yr, states(e)))
+        e.close()
+    assert np.isfinite(pageable).all() and not any(np.array_equal(pageable[:, y], pageable[:, y + 1]) for y in range(4))
+    assert np.array_equal(pinned.numpy(), pageable) and np.array_equal(dev.cpu().numpy(), pageable)
+    for yr, st in got[1:]:
+        assert np.array_equal(yr, got[0][0]) and np.array_equal(st, got[0][1])
 
 
 # ------------------------------------------------------------------------------------------------ 6. errors

@@ -183,6 +183,33 @@ def test_run_clim_against_run(inputs, params):
     plan.close()
 
 
+def test_run_clim_five_periods_reuse_both_output_slots(inputs, params):
+    """Seven years in one call with the periods (0, 1), (1, 1), (2, 2), (5, 1), (6, 1): adjacent one-year periods (one
+    finishes every year), five periods (both output slots are written again, twice), a year in no period (4), and a
+    period that ends with the last year right after another.  The CO2 differs from year to year, so a period delivered
+    from the wrong slot, or before its kernel, is not the mirror's."""
+    co2 = np.array([[340.0] * 7, [400.0, 480.0, 560.0, 680.0, 800.0, 900.0, 1020.0]], np.float32)
+    control = [-1, 0]
+    periods = [(0, 1), (1, 1), (2, 2), (5, 1), (6, 1)]
+    plan = clim.Plan(inputs.nx, inputs.ny, 2, control=control)
+    ea, eb = (engine.Engine(inputs, params, n_members=2) for _ in range(2))
+    for e in (ea, eb):
+        e.flux_correction(1)
+    mon, yr_a = ea.run(7, co2)
+    res = eb.run_clim(7, co2, plan, periods)
+    assert res.mean.shape == (2, 5, 12, 5, 48, 96) and res.seasons_resp.shape == (2, 5, 5, 5, 48, 96)
+    years = np.moveaxis(mon, 1, 0)  # [year][member]...
+    for p, (first, n) in enumerate(periods):
+        same_bits(_period(res, p), clim.reference(years[first:first + n], control), f"run_clim period {p} ({first}, {n})")
+    _same_engine_state(ea, eb, yr_a, res.yearly)
+    # the plan holds no unfinished period: the next call on it runs, and continues as run() does
+    mon_a, yr2_a = ea.run(1, 500.0)
+    again = eb.run_clim(1, 500.0, plan, [(0, 1)])
+    same_bits(_period(again, 0), clim.reference(np.moveaxis(mon_a, 1, 0), control), "the plan's next call")
+    _same_engine_state(ea, eb, yr2_a, again.yearly)
+    ea.close(); eb.close(); plan.close()
+
+
 def test_run_clim_against_run_any_grid(params):
     inp = workload.make_inputs(192, 96)
     plan = clim.Plan(192, 96, 1, what=abi.C_MEAN | abi.C_SEASONS)

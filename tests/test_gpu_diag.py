@@ -146,6 +146,31 @@ def test_run_diag_against_run(inputs, params):
     plan.close()
 
 
+def test_run_diag_five_years_reuse_both_output_slots(inputs, params):
+    """One call of five years: the products of years 2, 3 and 4 are made in an output slot that an earlier year's products
+    must have left first, in both parities.  The CO2 differs from year to year and between the members, so a product
+    delivered from the wrong slot, or before its kernel, is not the mirror's."""
+    co2 = np.array([[340.0, 400.0, 480.0, 560.0, 680.0], [1020.0, 900.0, 800.0, 700.0, 600.0]], np.float32)
+    plan = diag.Plan(inputs.nx, inputs.ny, regions_for(inputs.nx, inputs.ny))
+    ea, eb, ec = (engine.Engine(inputs, params, n_members=2) for _ in range(3))
+    for e in (ea, eb, ec):
+        e.flux_correction(1)
+    mon, yr_a = ea.run(5, co2)
+    res = eb.run_diag(5, co2, plan)
+    for y in range(5):
+        check_against_mirror(diag.Result(res.regions[:, y], res.zonal[:, y], res.annual[:, y], None, res.names), mon[:, y],
+                             plan.weights, f"run_diag year {y} of 5")
+    _same_engine_state(ea, eb, yr_a, res.yearly)
+    # one call of five years == five calls of one year, bit for bit
+    parts = [ec.run_diag(1, co2[:, y:y + 1], plan) for y in range(5)]
+    for name in ("regions", "zonal", "annual", "yearly"):
+        assert np.array_equal(np.concatenate([getattr(r, name) for r in parts], axis=1), getattr(res, name)), name
+    _same_engine_state(eb, ec, res.yearly[:, 4:], parts[-1].yearly)
+    for e in (ea, eb, ec):
+        e.close()
+    plan.close()
+
+
 def test_run_diag_against_run_any_grid(params):
     inp = workload.make_inputs(192, 96)
     plan = diag.Plan(192, 96, regions_for(192, 96))
