@@ -17,6 +17,8 @@ RUN_DEVICE_OUT = 1
 D_REGIONS, D_ZONAL, D_ANNUAL = 1, 2, 4  # reduced-output products, GREB_D_* of include/greb_engine.h
 D_MAX_REGIONS = 15
 C_MEAN, C_SEASONS, C_TREND, C_RESPONSE = 1, 2, 4, 8  # climatology products, GREB_C_* of include/greb_engine.h
+S_MEAN, S_VAR, S_RANGE, S_QUANTILES = 1, 2, 4, 8  # ensemble-output products, GREB_S_* of include/greb_engine.h
+ENS_MAX_GROUPS, ENS_MAX_PROBS, ENS_MAX_SORTED = 64, 16, 4096  # GREB_ENS_MAX_*
 # budget output, GREB_NBUDGET / GREB_B_* of include/greb_engine.h: the flux terms of the update in its order, sign and unit
 BUDGET_NAMES = ("sw", "LW_surf", "LWair_down", "LW_abs", "Q_sens", "Q_lat", "Q_lat_air", "dq_eva", "dq_rain", "dT_ocean",
                 "dTo", "dTa_crcl", "dq_crcl")
@@ -117,6 +119,18 @@ def make_fields(inp) -> tuple[GrebFields, list]:
         keep.append(a)
         setattr(f, name, fptr(a))
     return f, keep
+
+
+def ens_prototypes(lib) -> None:
+    """The argument types of greb_ens_* and greb_engine_run_ens (greb_ens_reduce_dev takes a size_t, which ctypes would
+    otherwise pass as an int)."""
+    i32p, vp = C.POINTER(C.c_int32), C.c_void_p
+    lib.greb_ens_create.argtypes = [C.c_int, C.c_int, C.c_int, i32p, C.c_int, i32p, c_float_p, C.c_int, C.c_uint, C.POINTER(vp)]
+    lib.greb_ens_destroy.argtypes = [vp]
+    lib.greb_ens_reduce_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+    lib.greb_engine_run_ens.argtypes = [vp, C.c_int, c_float_p, vp] + [c_float_p] * 6
+    for f in (lib.greb_ens_create, lib.greb_ens_destroy, lib.greb_ens_reduce_dev, lib.greb_engine_run_ens):
+        f.restype = C.c_int
 
 
 def nan_overrides(n: int):

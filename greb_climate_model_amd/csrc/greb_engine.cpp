@@ -26,6 +26,7 @@
 #include "greb_kernels.h"
 #include "greb_diag.h"
 #include "greb_clim.h"
+#include "greb_ens.h"
 
 using namespace greb;
 
@@ -174,6 +175,7 @@ struct greb_engine {
   float* diag_out = nullptr; size_t diag_out_cap = 0; // run_diag: zonal means and annual maps of two years (one per staging slot)
   float* diag_reg = nullptr; size_t diag_reg_cap = 0; // run_diag: the region series of the whole call
   float* clim_out = nullptr; size_t clim_out_cap = 0; // run_clim: the products of two periods (one per output slot)
+  float* ens_out = nullptr; size_t ens_out_cap = 0;   // run_ens: the group statistics of two years (one per output slot)
   // host copies needed later
   std::vector<RowTables> h_tabs;
   std::vector<int> h_tab_index;
@@ -906,7 +908,7 @@ int greb_engine_destroy(greb_engine* e) {
   void* ptrs[] = {e->z_topo, e->glacier, e->sw_solar, e->tclim, e->qclim, e->uclim, e->vclim, e->mldclim,
                   e->cldclim, e->swetclim, e->toclim, e->z_ocean, e->wz_air, e->wz_vapor, e->state, e->acc,
                   e->corr, e->corr_index, e->tab_index, e->tabs, e->phys, e->co2_dev, e->monthly_dev, e->yearly_dev,
-                  e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev, e->diag_out, e->diag_reg, e->clim_out, e->bsum, e->budget_dev,
+                  e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev, e->diag_out, e->diag_reg, e->clim_out, e->ens_out, e->bsum, e->budget_dev,
                   e->f_space, e->f_season, e->f_solar, e->force_dev, e->bsets_dev, e->bset_dev, e->neutral_force_dev};
   for (void* q : ptrs) if (q) (void)hipFree(q);
   for (size_t k = 1; k < e->bound.size(); ++k)
@@ -1392,6 +1394,231 @@ int greb_engine_run_clim(greb_engine* e, int years, const float* co2_ppm, greb_c
     return 0;
   };
   return run_years(e, years, co2_ppm, yearly, s);
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- ensemble output (greb_ens.hip)
+// A plan is host data only: grid, member count, the products, the probabilities and the member lists -- group g is
+// member[offs[g] ... offs[g + 1]) in ascending member index, control[k] the control of member[k].  The lists' device copy
+// (one allocation: offs, member, control) is made per device the first time the plan reduces there.
+struct greb_ens {
+  int nx = 0, ny = 0, nm = 0, ng = 0;
+  unsigned what = 0;
+  EnsProbs probs{};
+  bool has_control = false;
+  std::vector<int> offs, member, control;
+  struct Dev { int device; int* lists; };
+  std::vector<Dev> devs;
+};
+
+namespace {
+int ens_on_device(greb_ens* s, int device, EnsLists* out) {
+  const size_t listed = s->member.size(), n_offs = s->offs.size();
+  int* base = nullptr;
+  for (auto& x : s->devs) if (x.device == device) base = x.lists;
+  if (!base) {
+    std::vector<int> all(s->offs);
+    all.insert(all.end(), s->member.begin(), s->member.end());
+    all.insert(all.end(), s->control.begin(), s->control.end());
+    hipError_t err = dev_alloc(&base, all.size());
+    if (err == hipSuccess) err = hipMemcpy(base, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+      if (base) (void)hipFree(base);
+      HIP_TRY(nullptr, err);
+    }
+    s->devs.push_back({device, base});
+  }
+  out->offs = base; out->member = base + n_offs; out->control = s->has_control ? base + n_offs + listed : nullptr;
+  return 0;
+}
+
+// the five products: MEAN, VAR, the two of RANGE, QUANTILES
+const char* const kEnsOutNames[5] = {"mean", "var", "min", "max", "quant"};
+const char* const kEnsFlagNames[5] = {"GREB_S_MEAN", "GREB_S_VAR", "GREB_S_RANGE", "GREB_S_RANGE", "GREB_S_QUANTILES"};
+// floats of one group's record of each product, for rows of n elements (0: not selected)
+void ens_sizes(const greb_ens* s, size_t n, size_t out[5]) {
+  out[0] = (s->what & GREB_S_MEAN) ? n : 0;
+  out[1] = (s->what & GREB_S_VAR) ? n : 0;
+  out[2] = out[3] = (s->what & GREB_S_RANGE) ? n : 0;
+  out[4] = (s->what & GREB_S_QUANTILES) ? (size_t)s->probs.n * n : 0;
+}
+
+// the moments launch and one quantile launch per group, of x[nm][n] into out[5] (null where not selected)
+int ens_launch(greb_engine* e, const greb_ens* s, const EnsLists& l, const float* x, size_t n, float* const out[5],
+               hipStream_t stream) {
+  if (out[0] || out[1] || out[2]) {
+    EnsMomentArgs a{x, n, l, out[0], out[1], out[2], out[3]};
+    HIP_TRY(e, launch_ens_moments(a, s->ng, stream));
+  }
+  for (int g = 0; out[4] && g < s->ng; ++g) {
+    const int k0 = s->offs[(size_t)g];
+    HIP_TRY(e, launch_ens_quantiles(x, n, l.member + k0, l.control ? l.control + k0 : nullptr, s->offs[(size_t)g + 1] - k0, s->probs,
+                                    out[4] + (size_t)g * s->probs.n * n, stream));
+  }
+  return 0;
+}
+} // namespace
+
+extern "C" {
+
+int greb_ens_create(int nx, int ny, int n_members, const int32_t* group, int n_groups, const int32_t* control,
+                    const float* probs, int n_probs, unsigned what, greb_ens** out) {
+  if (!out) return fail(nullptr, GREB_E_INVALID, "ens_create: `out` is NULL");
+  *out = nullptr;
+  if (nx < 12 || (nx & 3) || ny < 5 || ny > kMaxNy)
+    return fail(nullptr, GREB_E_INVALID, "ens_create: grid " + std::to_string(nx) + " x " + std::to_string(ny) +
+                                             " (nx % 4 == 0, nx >= 12, 5 <= ny <= " + std::to_string(kMaxNy) + ")");
+  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "ens_create: n_members = " + std::to_string(n_members));
+  if (n_groups < 1 || n_groups > kEnsMaxGroups)
+    return fail(nullptr, GREB_E_INVALID, "ens_create: n_groups = " + std::to_string(n_groups) + " (1 ... " +
+                                             std::to_string(kEnsMaxGroups) + ")");
+  if (!group) return fail(nullptr, GREB_E_INVALID, "ens_create: `group` is NULL");
+  const unsigned all = GREB_S_MEAN | GREB_S_VAR | GREB_S_RANGE | GREB_S_QUANTILES;
+  if (what == 0 || (what & ~all))
+    return fail(nullptr, GREB_E_INVALID, "ens_create: `what` = " + std::to_string(what) + " selects no product or an unknown one");
+  std::vector<int> count((size_t)n_groups, 0);
+  for (int m = 0; m < n_members; ++m) {
+    if (group[m] < -1 || group[m] >= n_groups)
+      return fail(nullptr, GREB_E_INVALID, "ens_create: member " + std::to_string(m) + ": group = " + std::to_string(group[m]) +
+                                               " (-1 = none, or 0 ... " + std::to_string(n_groups - 1) + ")");
+    if (control && (control[m] < -1 || control[m] >= n_members))
+      return fail(nullptr, GREB_E_INVALID, "ens_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
+                                               " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
+    if (group[m] < 0) continue;
+    if (control && control[m] < 0)
+      return fail(nullptr, GREB_E_INVALID, "ens_create: member " + std::to_string(m) + " is in group " + std::to_string(group[m]) +
+                                               " but has no control (control = -1) while a control map is given");
+    ++count[(size_t)group[m]];
+  }
+  for (int g = 0; g < n_groups; ++g)
+    if (count[(size_t)g] == 0) return fail(nullptr, GREB_E_INVALID, "ens_create: group " + std::to_string(g) + " is empty");
+  EnsProbs pr{};
+  if (what & GREB_S_QUANTILES) {
+    if (n_probs < 1 || n_probs > kEnsMaxProbs || !probs)
+      return fail(nullptr, GREB_E_INVALID, "ens_create: GREB_S_QUANTILES with n_probs = " + std::to_string(n_probs) +
+                                               (probs ? "" : " and `probs` NULL") + " (1 ... " + std::to_string(kEnsMaxProbs) + ")");
+    pr.n = n_probs;
+    for (int i = 0; i < n_probs; ++i) {
+      if (!(probs[i] >= 0.f && probs[i] <= 1.f)) { // (a NaN fails both comparisons)
+        char buf[128];
+        std::snprintf(buf, sizeof(buf), "ens_create: probability %d = %g is not in [0, 1]", i, (double)probs[i]);
+        return fail(nullptr, GREB_E_INVALID, buf);
+      }
+      pr.p[i] = probs[i];
+    }
+    for (int g = 0; g < n_groups; ++g)
+      if (count[(size_t)g] > kEnsMaxSorted)
+        return fail(nullptr, GREB_E_UNSUPPORTED, "ens_create: GREB_S_QUANTILES with group " + std::to_string(g) + " of " +
+                                                     std::to_string(count[(size_t)g]) + " members (at most " +
+                                                     std::to_string(kEnsMaxSorted) + " are sorted in one compute unit's LDS)");
+  }
+  greb_ens* s = new (std::nothrow) greb_ens();
+  if (!s) return fail(nullptr, GREB_E_INVALID, "out of host memory");
+  s->nx = nx; s->ny = ny; s->nm = n_members; s->ng = n_groups; s->what = what; s->probs = pr; s->has_control = control != nullptr;
+  s->offs.assign((size_t)n_groups + 1, 0);
+  for (int g = 0; g < n_groups; ++g) s->offs[(size_t)g + 1] = s->offs[(size_t)g] + count[(size_t)g];
+  s->member.resize((size_t)s->offs[(size_t)n_groups]);
+  if (control) s->control.resize(s->member.size());
+  std::vector<int> at(s->offs.begin(), s->offs.end() - 1);
+  for (int m = 0; m < n_members; ++m) { // ascending member index inside every group
+    if (group[m] < 0) continue;
+    const size_t k = (size_t)at[(size_t)group[m]]++;
+    s->member[k] = m;
+    if (control) s->control[k] = control[m];
+  }
+  *out = s;
+  return 0;
+}
+
+int greb_ens_destroy(greb_ens* s) {
+  if (!s) return 0;
+  int prev = 0;
+  const bool have_prev = !s->devs.empty() && hipGetDevice(&prev) == hipSuccess;
+  for (auto& x : s->devs)
+    if (hipSetDevice(x.device) == hipSuccess) {
+      (void)hipDeviceSynchronize(); // a reduction in flight may still read the lists
+      (void)hipFree(x.lists);
+    }
+  if (have_prev) (void)hipSetDevice(prev);
+  delete s;
+  return 0;
+}
+
+int greb_ens_reduce_dev(greb_ens* s, int device, const float* x_dev, size_t n, float* mean_dev, float* var_dev, float* min_dev,
+                        float* max_dev, float* quant_dev, void* stream) {
+  if (!s) return fail(nullptr, GREB_E_INVALID, "ens_reduce_dev: no plan (greb_ens is NULL)");
+  if (!x_dev) return fail(nullptr, GREB_E_INVALID, "ens_reduce_dev: x_dev is NULL");
+  if (reinterpret_cast<uintptr_t>(x_dev) & 15) return fail(nullptr, GREB_E_INVALID, "ens_reduce_dev: x_dev is not 16-byte aligned");
+  if (n < 1) return fail(nullptr, GREB_E_INVALID, "ens_reduce_dev: n = 0");
+  size_t size[5];
+  ens_sizes(s, n, size);
+  float* out[5] = {mean_dev, var_dev, min_dev, max_dev, quant_dev};
+  for (int i = 0; i < 5; ++i) {
+    if (!size[i]) { out[i] = nullptr; continue; } // (not selected: the pointer is ignored)
+    if (!out[i])
+      return fail(nullptr, GREB_E_INVALID, std::string("ens_reduce_dev: ") + kEnsFlagNames[i] + " selected but `" + kEnsOutNames[i] +
+                                               "_dev` is NULL");
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
+    return fail(nullptr, GREB_E_NOGPU, "ens_reduce_dev: no HIP device (no CPU path)");
+  HIP_TRY(nullptr, hipSetDevice(device));
+  EnsLists l{};
+  if (int rc = ens_on_device(s, device, &l)) return rc;
+  return ens_launch(nullptr, s, l, x_dev, n, out, (hipStream_t)stream);
+}
+
+int greb_engine_run_ens(greb_engine* e, int years, const float* co2_ppm, greb_ens* s, float* mean, float* var, float* min,
+                        float* max, float* quant, float* yearly) {
+  // argument errors first, before anything touches a device: the plan, the outputs, then the engine
+  if (!s) return fail(e, GREB_E_INVALID, "run_ens: no plan (greb_ens is NULL)");
+  if (years < 1) return fail(e, GREB_E_INVALID, "run_ens: years = " + std::to_string(years));
+  const size_t n = (size_t)12 * 5 * s->nx * s->ny; // one member's model year
+  size_t size[5];
+  ens_sizes(s, n, size);
+  float* host[5] = {mean, var, min, max, quant};
+  for (int i = 0; i < 5; ++i)
+    if (size[i] && !host[i])
+      return fail(e, GREB_E_INVALID, std::string("run_ens: ") + kEnsFlagNames[i] + " selected but `" + kEnsOutNames[i] + "` is NULL");
+  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, "run_ens: bad argument (engine or co2_ppm)");
+  if (s->nx != e->nx || s->ny != e->ny)
+    return fail(e, GREB_E_INVALID, "run_ens: the plan's grid " + std::to_string(s->nx) + " x " + std::to_string(s->ny) +
+                                       " differs from the engine's " + std::to_string(e->nx) + " x " + std::to_string(e->ny));
+  if (s->nm != e->nm)
+    return fail(e, GREB_E_INVALID, "run_ens: the plan is for " + std::to_string(s->nm) + " members, the engine has " +
+                                       std::to_string(e->nm));
+  const size_t ng = (size_t)s->ng;
+  size_t at[5], out_slot = 0; // where each product sits in an output slot: [group][its record], 16-byte aligned (np % 4 == 0)
+  for (int i = 0; i < 5; ++i) { at[i] = out_slot; out_slot += ng * size[i]; }
+  EnsLists l{};
+  // A unit is a year's statistics, made in output slot y & 1 of e->ens_out.  Nothing on the device grows with `years`
+  // (besides the yearly scalars).
+  RunSink k;
+  k.prepare = [&]() -> int {
+    if (int rc = ensure(e, &e->ens_out, &e->ens_out_cap, 2 * out_slot)) return rc;
+    return ens_on_device(s, e->device, &l);
+  };
+  k.year = [&](const YearCalls& run, int y) -> int {
+    float* mon = staging_slot(e, y);
+    if (int rc = run.integrate(y, {mon, 1, 0})) return rc;
+    if (int rc = run.writing(y)) return rc; // (here, not before the year: only the reduction writes the slot)
+    float* out[5];
+    for (int i = 0; i < 5; ++i) out[i] = size[i] ? e->ens_out + (size_t)(y & 1) * out_slot + at[i] : nullptr;
+    if (int rc = ens_launch(e, s, l, mon, n, out, e->stream)) return rc;
+    return run.complete(y);
+  };
+  // every group's record of year y to its place in the caller's [group][years][record] array (as unit_to_host, whose rows
+  // are the members)
+  k.deliver = [&](int y, int sl) -> int {
+    for (int i = 0; i < 5; ++i)
+      if (size[i])
+        HIP_TRY(e, hipMemcpy2DAsync(host[i] + (size_t)y * size[i], (size_t)years * size[i] * sizeof(float),
+                                    e->ens_out + (size_t)sl * out_slot + at[i], size[i] * sizeof(float), size[i] * sizeof(float), ng,
+                                    hipMemcpyDeviceToHost, e->copy_stream));
+    return 0;
+  };
+  return run_years(e, years, co2_ppm, yearly, k);
 }
 
 const char* greb_engine_describe(greb_engine* e) {

@@ -45,6 +45,7 @@ def lib() -> C.CDLL:
         L.greb_engine_last_error.argtypes = [C.c_void_p]
         L.greb_device_info.restype = C.c_char_p
         L.greb_params_default.restype = None
+        abi.ens_prototypes(L)
         _lib = L
     return _lib
 
@@ -60,7 +61,8 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_diag_reduce_dev", "greb_engine_run_diag", "greb_engine_run_budget", "greb_budget_name",
            "greb_member_deal_cover", "greb_engine_set_forcing_tables", "greb_engine_set_member_forcing",
            "greb_engine_add_boundary_set", "greb_engine_set_member_boundary", "greb_step_variant", "greb_step_variants",
-           "greb_clim_create", "greb_clim_destroy", "greb_clim_add_year_dev", "greb_clim_finish_dev", "greb_engine_run_clim"]
+           "greb_clim_create", "greb_clim_destroy", "greb_clim_add_year_dev", "greb_clim_finish_dev", "greb_engine_run_clim",
+           "greb_ens_create", "greb_ens_destroy", "greb_ens_reduce_dev", "greb_engine_run_ens"]
 
 
 def _check(rc: int, h=None):
@@ -287,6 +289,19 @@ class Engine:
         _check(lib().greb_engine_run_clim(self.h, int(years), abi.fptr(co2), plan.h, len(per), ip(first), ip(count),
                                           *[None if a is None else abi.fptr(a) for a in out], abi.fptr(yearly)), self.h)
         return clim.Result(*out, yearly)
+
+    def run_ens(self, years: int, co2_ppm, plan):
+        """The scenario run of run() that hands back only the statistics across the members of each group of `plan`
+        (ens.Plan), of every monthly record of every year: made on the device year by year, of the records or of each
+        member's difference to its control member (greb_engine_run_ens).  Returns an ens.Result of arrays
+        [n_groups][years][12][5][ny][nx], quant [n_groups][years][n_probs][12][5][ny][nx] (a product the plan does not
+        select is None).  State, clock and yearly are those of run() over the same years."""
+        from . import ens
+        co2, yearly = self._run_arrays(years, co2_ppm)
+        out = ens.empty_products(plan, (years,), (12, 5, self.ny, self.nx))
+        _check(lib().greb_engine_run_ens(self.h, int(years), abi.fptr(co2), plan.h,
+                                         *[None if a is None else abi.fptr(a) for a in out], abi.fptr(yearly)), self.h)
+        return ens.Result(*out, yearly)
 
     def state(self, member: int = 0) -> np.ndarray:
         s = np.empty((5, self.ny, self.nx), np.float32)

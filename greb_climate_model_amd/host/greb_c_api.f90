@@ -131,6 +131,41 @@ module greb_c_api
        integer(c_int), intent(in) :: first_year(*), n_years(*)
        real(c_float), intent(out) :: yearly(*)
      end function
+     ! ensemble output (greb_ens.hip): a plan = grid, member count, group(n_members) (0-based, -1 = in no group),
+     ! control(n_members) (0-based, -1 = none; c_null_ptr: no control map), probs(n_probs) and the products `what`
+     ! (1 mean, 2 variance, 4 min and max, 8 quantiles)
+     integer(c_int) function greb_ens_create(nx, ny, n_members, group, n_groups, control, probs, n_probs, what, plan) &
+          bind(C, name="greb_ens_create")
+       import :: c_int, c_ptr
+       integer(c_int), value :: nx, ny, n_members, n_groups, n_probs, what
+       integer(c_int), intent(in) :: group(*)
+       type(c_ptr), value :: control, probs
+       type(c_ptr), intent(out) :: plan
+     end function
+     integer(c_int) function greb_ens_destroy(plan) bind(C, name="greb_ens_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan
+     end function
+     ! device pointers (c_ptr): x_dev(n,n_members) -> the statistics per group; a product the plan does not select may be
+     ! c_null_ptr; launches on `stream`, no synchronisation
+     integer(c_int) function greb_ens_reduce_dev(plan, device, x_dev, n, mean_dev, var_dev, min_dev, max_dev, quant_dev, &
+          stream) bind(C, name="greb_ens_reduce_dev")
+       import :: c_int, c_ptr, c_size_t
+       type(c_ptr), value :: plan, x_dev, mean_dev, var_dev, min_dev, max_dev, quant_dev, stream
+       integer(c_int), value :: device
+       integer(c_size_t), value :: n
+     end function
+     ! greb_engine_run that delivers only the plan's statistics of every year's monthly records:
+     ! mean, var, min, max (nx,ny,5,12,years,n_groups); quant (nx,ny,5,12,n_probs,years,n_groups);
+     ! a product the plan does not select may be c_null_ptr
+     integer(c_int) function greb_engine_run_ens(eng, years, co2_ppm, plan, mean, var, vmin, vmax, quant, yearly) &
+          bind(C, name="greb_engine_run_ens")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, plan, mean, var, vmin, vmax, quant
+       integer(c_int), value :: years
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
      ! greb_engine_run that also delivers the monthly means of the 13 flux terms of the update (GREB_B_* of greb_engine.h):
      ! budget(nx,ny,13,12,years,n_members); monthly as in greb_engine_run, or c_null_ptr for a budget-only run
      integer(c_int) function greb_engine_run_budget(eng, years, co2_ppm, monthly, budget, yearly, run_flags) &

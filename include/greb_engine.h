@@ -288,6 +288,61 @@ int greb_engine_run_clim(greb_engine* e, int years, const float* co2_ppm, greb_c
                          const int32_t* n_years, float* mean, float* seasons, float* trend, float* mean_resp, float* seasons_resp,
                          float* yearly);
 
+/* ---- ensemble output: statistics across the members of a group, made on the device -----------------
+ * The member axis is what makes a many-member run's output big.  A plan puts each member into a group (group[m] in
+ * -1 ... n_groups-1; -1: in no group, e.g. a pure control member) and optionally names its control member (control[m] in
+ * -1 ... n_members-1); per group and per element of x[n_members][n] the statistics are taken across the group's members,
+ * in ascending member index, of the samples
+ *   v = x[m][i]                          without a control map
+ *   v = x[m][i] - x[control[m]][i]       with one, as ONE fp32 subtraction (control[m] = m is legal and gives zeros)
+ * For a group of n_g members, all in fp64 unless said otherwise, each product rounded to fp32 exactly once:
+ *   GREB_S_MEAN       S = sum (double)v;  mean = S / n_g
+ *   GREB_S_VAR        K = (double)v of the group's first member, d = (double)v - K, S1 = sum d, S2 = sum d d;
+ *                     var = (S2 - S1 S1 / n_g) / (n_g - 1), set to 0 where that is negative and for n_g = 1: the sample
+ *                     variance in one pass.  No square root is taken on the device.
+ *   GREB_S_RANGE      min and max of v, in fp32
+ *   GREB_S_QUANTILES  the group's v sorted ascending; for probability p (fp32): h = (double)p (n_g - 1), lo = floor(h),
+ *                     t = h - lo, a = v[lo], b = v[min(lo + 1, n_g - 1)], q = a + t (b - a) as a multiply, then an add
+ *                     (numpy's "linear" rule with the arithmetic pinned)
+ * The order of these operations is the definition of the results (no fused multiply-add); every output element has one
+ * owner (no atomics), so results are deterministic, and a group's numbers depend neither on the other groups and members
+ * of the call nor on where its members sit. */
+#define GREB_S_MEAN      1u
+#define GREB_S_VAR       2u
+#define GREB_S_RANGE     4u
+#define GREB_S_QUANTILES 8u
+#define GREB_ENS_MAX_GROUPS 64
+#define GREB_ENS_MAX_PROBS  16
+#define GREB_ENS_MAX_SORTED 4096 /* members of one group under GREB_S_QUANTILES */
+typedef struct greb_ens greb_ens;
+/* A plan: grid, member count, group[n_members], control[n_members] or NULL, probs[n_probs] and the products `what`
+ * (GREB_S_*; probs is read only under GREB_S_QUANTILES).  Host work only, validated without touching a device.
+ * GREB_E_INVALID with a message that names the offender (greb_engine_last_error(NULL)): a grid greb_diag_create does not
+ * take, n_members < 1, n_groups outside 1 ... 64, a group or control index out of range, an empty group, a member of a
+ * group whose control is -1 while a control map is given, `what` zero or with unknown bits, GREB_S_QUANTILES with n_probs
+ * outside 1 ... 16 or a probability outside [0, 1] or not finite.  GREB_E_UNSUPPORTED: GREB_S_QUANTILES with a group of
+ * more than 4096 members (the sort's tile is one compute unit's LDS).  A plan serves any number of calls and engines. */
+int greb_ens_create(int nx, int ny, int n_members, const int32_t* group, int n_groups, const int32_t* control,
+                    const float* probs, int n_probs, unsigned what, greb_ens** out);
+int greb_ens_destroy(greb_ens* s); /* waits for the device before it frees the member lists */
+/* x_dev[n_members][n] on HIP device `device` (16-byte aligned; n is arbitrary, a model year's staging slot is
+ * n = 12 * 5 * ny * nx) -> mean_dev, var_dev, min_dev, max_dev [n_groups][n] and quant_dev [n_groups][n_probs][n].  A
+ * pointer whose product the plan does not select is ignored and may be NULL; a selected product with a NULL pointer is
+ * GREB_E_INVALID (GREB_S_RANGE needs both min_dev and max_dev).  Launches on `stream` (a hipStream_t, may be NULL) and
+ * does not synchronise.  Arguments are checked before any device query; without a device: GREB_E_NOGPU (no CPU path). */
+int greb_ens_reduce_dev(greb_ens* s, int device, const float* x_dev, size_t n, float* mean_dev, float* var_dev, float* min_dev,
+                        float* max_dev, float* quant_dev, void* stream);
+/* greb_engine_run that delivers ONLY the plan's statistics of each model year's monthly records, to host memory:
+ *   mean, var, min, max  [n_groups][years][12][5][ny][nx]      quant  [n_groups][years][n_probs][12][5][ny][nx]
+ * (unselected products as above; a plan made for another grid or member count is GREB_E_INVALID; all of it is decided
+ * before any device work).  Each year is integrated into one of the engine's two one-year staging slots and reduced
+ * there into one of two device output slots, which leaves on the copy stream while the following year integrates.
+ * Device memory does not grow with `years` (the yearly scalars aside).  co2_ppm, yearly, the model clock, the state the
+ * engine is left in and the kernels that integrate are those of greb_engine_run over the same years, bit for bit:
+ * switches, member forcing and boundary sets act as they do there. */
+int greb_engine_run_ens(greb_engine* e, int years, const float* co2_ppm, greb_ens* s, float* mean, float* var, float* min,
+                        float* max, float* quant, float* yearly);
+
 /* ---- per-member forcing: regional and seasonal CO2, insolation tables and scale --------------------
  * Members of one engine may differ in the forcing itself, not only in the CO2 level: CO2 raised in one hemisphere, over
  * land or ocean only or in one half of the year, a changed solar constant, a changed latitudinal or seasonal distribution
