@@ -30,9 +30,12 @@ class MirrorStart:
         oracle.field(4)[:] = self.state5[4]
 
 
-def run_year(oracle, start: MirrorStart, co2: float):
+def run_year(oracle, start: MirrorStart, co2: float, observer=None):
     """One scenario year (steps it = 1 ... 730 of a scenario that begins at the year's first step) from `start`.
-    Returns (monthly [12][5][ny][nx], budget [12][13][ny][nx], state5 at the end)."""
+    Returns (monthly [12][5][ny][nx], budget [12][13][ny][nx], state5 at the end).
+    observer: called once per step as observer(ityr, Ts, To, q, dq, Ts0) with the state the step starts from, the humidity
+    increment BEFORE the clamp of :265 and the new Tsurf (what seaice sees); it reports, it changes nothing
+    (tests/edge_workload.py: Census counts the points the clamp fires at and the smallest |dq + q| / q)."""
     p = oracle.params
     dt = f32(p.dt)
     cap_air = f32(p.cp_air) * f32(p.rho_air) * f32(p.d_air)  # :188
@@ -66,11 +69,14 @@ def run_year(oracle, start: MirrorStart, co2: float):
         Ta0 = (Ta + dTa_crcl) + (dt * ((((LWair_up + LWair_down) - LW_abs) + Q_lat_air) - Q_sens)) / cap_air
         To0 = (To + dTo) + ToF[ityr - 1]
         dq = ((dt * (dq_eva + dq_rain)) + dq_crcl) + qF[ityr - 1]
+        dq_raw = dq
         dq = np.where(dq <= -q, f32(-0.9) * q, dq).astype(f32)
         q0 = q + dq
         for a in (Ts0, Ta0, To0, q0):
             assert a.dtype == f32
         oracle.seaice(ityr, Ts0)          # :268
+        if observer is not None:
+            observer(ityr, Ts, To, q, dq_raw, Ts0)
         # output, :974-984, and the same rule for the thirteen terms
         for i, x in enumerate((Ts0, Ta0, To0, q0, albedo)):
             acc5[i] += x
