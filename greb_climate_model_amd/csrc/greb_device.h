@@ -438,21 +438,35 @@ __device__ __forceinline__ void lw_radiation(const Phys& P, float Ts, float Ta, 
 }
 
 // a6 hydro :452-467
+// the wind-speed term (:455-457): boundary data only.  The FAST fused member kernel reads it from the set's forcing record,
+// where the pack kernel put the value of this very function (greb_member.hip: pack_forcing_kernel).
 template <bool EXACT = true>
-__device__ __forceinline__ void hydro(const Phys& P, float Ts, float q, float u, float v, float z_topo,
-                                      float ez, float swet, float& Qlat, float& Qlat_air, float& dq_eva,
-                                      float& dq_rain, unsigned xsw = 0) {
+__device__ __forceinline__ float wind_speed(float u, float v, float z_topo) {
 #pragma clang fp contract(off)
-  if (xsw & kXNoHydro) { Qlat = Qlat_air = dq_eva = dq_rain = 0.f; return; } // greb.original.model.f90:452-453
   float abswind = fsqrt<EXACT>(u * u + v * v);
   if (z_topo > 0.f) abswind = fsqrt<EXACT>(abswind * abswind + 2.0f * 2.0f);
   if (z_topo < 0.f) abswind = fsqrt<EXACT>(abswind * abswind + 3.0f * 3.0f);
+  return abswind;
+}
+// hydro with the finished wind-speed term
+template <bool EXACT = true>
+__device__ __forceinline__ void hydro_wind(const Phys& P, float Ts, float q, float abswind, float ez, float swet, float& Qlat,
+                                           float& Qlat_air, float& dq_eva, float& dq_rain, unsigned xsw = 0) {
+#pragma clang fp contract(off)
+  if (xsw & kXNoHydro) { Qlat = Qlat_air = dq_eva = dq_rain = 0.f; return; } // greb.original.model.f90:452-453
   float qs = 3.75e-3f * fexp<EXACT>(fdiv<EXACT>(17.08085f * (Ts - 273.15f), Ts - 273.15f + 234.175f));
   qs = qs * ez;
   Qlat = (q - qs) * abswind * P.cq_latent * P.rho_air * P.ce * swet;
   dq_eva = fdiv<EXACT>(fdiv<EXACT>(-Qlat, P.cq_latent), P.r_qviwv);
   dq_rain = P.cq_rain * q;
   Qlat_air = -dq_rain * P.cq_latent * P.r_qviwv;
+}
+template <bool EXACT = true>
+__device__ __forceinline__ void hydro(const Phys& P, float Ts, float q, float u, float v, float z_topo,
+                                      float ez, float swet, float& Qlat, float& Qlat_air, float& dq_eva,
+                                      float& dq_rain, unsigned xsw = 0) {
+  if (xsw & kXNoHydro) { Qlat = Qlat_air = dq_eva = dq_rain = 0.f; return; } // greb.original.model.f90:452-453
+  hydro_wind<EXACT>(P, Ts, q, wind_speed<EXACT>(u, v, z_topo), ez, swet, Qlat, Qlat_air, dq_eva, dq_rain, xsw);
 }
 
 // a7 deep_ocean :505-523

@@ -162,13 +162,15 @@ struct greb_engine {
     float* dev[kBoundaryFields] = {};    // the set's thirteen device arrays in BoundarySet's order: its own or the engine's
     bool own[kBoundaryFields] = {};      // which of them this set allocated
     unsigned over = 0;                   // bit i: input field i (< kBoundaryInputs) is overridden
+    float* frec = nullptr;               // the set's forcing record (greb_kernels.h), kFrBytes; FAST fused engine only
     // what the initial state is made of (:190-197), np floats each: tclim[729], qclim[729], toclim, z_topo, mldclim[0]
     std::vector<float> t_last, q_last, toclim, z_topo, mld0;
   };
   std::vector<BoundSet> bound;                         // [1 + sets made]; [0]: the engine's own data
   std::vector<int> h_bset;                             // [nm] each member's set, or empty: every member 0
   int members_on_sets = 0;                             // members that name a set above 0
-  BoundarySet* bsets_dev = nullptr;                    // [1 + GREB_MAX_BOUNDARY_SETS], made with the first set
+  BoundarySet* bsets_dev = nullptr;                    // the set table (greb_kernels.h: kSetTableBytes), made with the engine where it
+                                                       // keeps forcing records, else with the first set
   int* bset_dev = nullptr;                             // [nm], current whenever members_on_sets > 0
   MemberForcing* neutral_force_dev = nullptr;          // [nm] {-1, ., -1, 1}: what a BOUND scenario launch takes when no member is forced
   float* yearly_dev = nullptr; size_t yearly_cap = 0;
@@ -231,6 +233,7 @@ MemberArgs base_args(greb_engine* e) {
   if (all) a.nsub = 0;
   // a member on a boundary set: the launch carries the set table and takes the boundary-aware kernels
   if (e->members_on_sets > 0) { a.bsets = e->bsets_dev; a.bset_m = e->bset_dev; }
+  else if (e->bound[0].frec) a.bsets = e->bsets_dev; // the FAST fused member kernel finds its forcing record behind the set table
   return a;
 }
 
@@ -546,6 +549,28 @@ const char* const kBoundaryNames[kBoundaryFields] = {"z_topo", "glacier", "tclim
 enum { kBfZtopo, kBfGlacier, kBfTclim, kBfQclim, kBfUclim, kBfVclim, kBfMld, kBfCld, kBfSwet, kBfToclim, kBfZocean, kBfWzAir, kBfWzVapor };
 size_t boundary_floats(int field, size_t np) { return (field >= kBfTclim && field <= kBfSwet) ? np * kNT : np; }
 
+BoundarySet set_entry(const greb_engine::BoundSet& x) {
+  return BoundarySet{x.dev[0], x.dev[1], x.dev[2], x.dev[3], x.dev[4], x.dev[5], x.dev[6], x.dev[7], x.dev[8], x.dev[9], x.dev[10],
+                     x.dev[11], x.dev[12]};
+}
+// The FAST fused member kernel reads boundary data from one packed record per set (greb_kernels.h: forcing record).
+bool uses_forcing_records(const greb_engine* e) { return e->fused && !e->strict; }
+// The record of set `b`, whose arrays are on the device: made there, on the engine's stream -- ahead of every launch that
+// reads it -- and entered into slot `id` of the record pointers behind the set table.  On failure nothing is left behind
+// and *what names the step.
+hipError_t make_forcing_record(greb_engine* e, const greb_engine::BoundSet& b, BoundarySet* table, size_t id, float** rec,
+                               const char** what) {
+  *rec = nullptr;
+  *what = "hipMalloc of the set's forcing record";
+  hipError_t err = dev_alloc(rec, kFrBytes / sizeof(float));
+  if (err != hipSuccess) { *rec = nullptr; return err; }
+  *what = "packing the set's forcing record";
+  err = launch_pack_forcing(set_entry(b), *rec, e->stream);
+  if (err == hipSuccess) { *what = "hipMemcpy"; err = hipMemcpy(set_table_records(table) + id, rec, sizeof(float*), hipMemcpyHostToDevice); }
+  if (err != hipSuccess) { (void)hipStreamSynchronize(e->stream); (void)hipFree(*rec); *rec = nullptr; }
+  return err;
+}
+
 // An engine whose members share one flux-correction set gives every member a copy of it -- on a NEW buffer: the engine is
 // untouched, and the caller frees the buffer if anything later fails.
 hipError_t copy_shared_corrections(greb_engine* e, float** corr, const char** what) {
@@ -638,6 +663,15 @@ int create_engine(const char* who, const greb_params* p, int nx, int ny, const g
     b0.t_last.assign(f->tclim + last, f->tclim + last + np); b0.q_last.assign(f->qclim + last, f->qclim + last + np);
     b0.toclim = toclim; b0.z_topo.assign(f->z_topo, f->z_topo + np); b0.mld0.assign(f->mldclim, f->mldclim + np);
     e->bound.push_back(std::move(b0));
+  }
+  if (uses_forcing_records(e)) { // the forcing record of the engine's own data; an allocation failure is an engine error
+    const BoundarySet own = set_entry(e->bound[0]);
+    HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&e->bsets_dev), kSetTableBytes));
+    HIP_TRY(e, hipMemset(e->bsets_dev, 0, kSetTableBytes));
+    HIP_TRY(e, hipMemcpy(e->bsets_dev, &own, sizeof(own), hipMemcpyHostToDevice));
+    const char* what = "";
+    const hipError_t err = make_forcing_record(e, e->bound[0], e->bsets_dev, 0, &e->bound[0].frec, &what);
+    if (err != hipSuccess) return fail(e, (int)err, std::string(who) + ": " + what + ": " + hipGetErrorString(err));
   }
 
   // per-member physics, grid tables (deduplicated by kappa), correction-set mapping
@@ -911,6 +945,7 @@ int greb_engine_destroy(greb_engine* e) {
                   e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev, e->diag_out, e->diag_reg, e->clim_out, e->ens_out, e->bsum, e->budget_dev,
                   e->f_space, e->f_season, e->f_solar, e->force_dev, e->bsets_dev, e->bset_dev, e->neutral_force_dev};
   for (void* q : ptrs) if (q) (void)hipFree(q);
+  for (const auto& b : e->bound) if (b.frec) (void)hipFree(b.frec);
   for (size_t k = 1; k < e->bound.size(); ++k)
     for (int i = 0; i < kBoundaryFields; ++i) if (e->bound[k].own[i]) (void)hipFree(e->bound[k].dev[i]);
   for (auto& kv : e->plans) free_plan(kv.second);
@@ -1647,6 +1682,12 @@ const char* greb_engine_describe(greb_engine* e) {
     s += "]";
   }
   s += "]}";
+  { // the packed forcing records of the FAST fused member kernel: one per set that has one
+    int n = 0;
+    for (const auto& b : e->bound) n += b.frec != nullptr;
+    std::snprintf(buf, sizeof(buf), ", \"forcing_records\": {\"sets\": %d, \"bytes\": %zu}", n, (size_t)n * kFrBytes);
+    s += buf;
+  }
   { // the kernel family the next launch of each phase takes (budget output is chosen per call, on top of it)
     unsigned v;
     auto family = [&v](const MemberArgs& a) { return select_variant(a, &v) == hipSuccess ? variant_family(v) : "none"; };
@@ -1916,8 +1957,10 @@ int greb_engine_add_boundary_set(greb_engine* e, const greb_fields* over, int* s
   greb_engine::BoundSet b = e->bound[0]; // everything inherited: aliases of the engine's arrays, its host slices
   for (bool& o : b.own) o = false;
   b.over = mask;
+  b.frec = nullptr;
   auto step = [&](hipError_t err, const char* what) -> int {
     if (err == hipSuccess) return 0;
+    if (b.frec) { (void)hipStreamSynchronize(e->stream); (void)hipFree(b.frec); } // (the pack kernel may still be writing it)
     for (int i = 0; i < kBoundaryFields; ++i) if (b.own[i]) (void)hipFree(b.dev[i]);
     return fail(e, (int)err, std::string(who) + what + ": " + hipGetErrorString(err));
   };
@@ -1943,19 +1986,20 @@ int greb_engine_add_boundary_set(greb_engine* e, const greb_fields* over, int* s
   if (over->qclim) b.q_last.assign(over->qclim + last, over->qclim + last + np);
   if (over->z_topo) b.z_topo.assign(over->z_topo, over->z_topo + np);
   if (over->mldclim) b.mld0.assign(over->mldclim, over->mldclim + np);
-  // the table: made with the first set (entry 0: the engine's own); a new set fills the next entry, which no launch in
-  // flight reads
-  auto entry = [](const greb_engine::BoundSet& x) {
-    return BoundarySet{x.dev[0], x.dev[1], x.dev[2], x.dev[3], x.dev[4], x.dev[5], x.dev[6], x.dev[7], x.dev[8], x.dev[9], x.dev[10],
-                       x.dev[11], x.dev[12]};
-  };
+  // the table: made with the engine or with the first set (entry 0: the engine's own); a new set fills the next entry,
+  // which no launch in flight reads -- and, where the engine keeps forcing records, the next record pointer behind it
   BoundarySet* table = e->bsets_dev;
   if (!table) {
-    if (int rc = step(dev_alloc(&table, (size_t)1 + GREB_MAX_BOUNDARY_SETS), "hipMalloc")) return rc;
-    const BoundarySet own = entry(e->bound[0]);
+    if (int rc = step(hipMalloc(reinterpret_cast<void**>(&table), kSetTableBytes), "hipMalloc")) return rc;
+    const BoundarySet own = set_entry(e->bound[0]);
     if (int rc = step(hipMemcpy(table, &own, sizeof(own), hipMemcpyHostToDevice), "hipMemcpy")) { (void)hipFree(table); return rc; }
   }
-  const BoundarySet mine = entry(b);
+  if (uses_forcing_records(e)) {
+    const char* what = "";
+    const hipError_t err = make_forcing_record(e, b, table, e->bound.size(), &b.frec, &what);
+    if (int rc = step(err, what)) return rc;
+  }
+  const BoundarySet mine = set_entry(b);
   if (int rc = step(hipMemcpy(table + e->bound.size(), &mine, sizeof(mine), hipMemcpyHostToDevice), "hipMemcpy")) {
     if (!e->bsets_dev) (void)hipFree(table);
     return rc;
@@ -2200,6 +2244,48 @@ int greb_step_variants(unsigned* out, int capacity) {
 int greb_member_deal_cover(int strict, int* counts) {
   if (!counts) return fail(nullptr, GREB_E_INVALID, "member_deal_cover: bad argument");
   member_deal_cover(strict != 0, counts);
+  return 0;
+}
+
+static_assert(GREB_FORCING_RECORD_FIELDS == kFrFields, "the record's field count mirrors the ABI");
+
+long long greb_forcing_record_offset(int row, int field, int lon) {
+  if (row < 0 || row >= kFrNy || field < 0 || field >= kFrFields || lon < 0 || lon >= kFrNx) return -1;
+  return (long long)forcing_record_offset(row, field, lon);
+}
+
+long long greb_forcing_record_field_bytes(int field) {
+  if (field < 0 || field >= kFrFields) return -1;
+  return (long long)(forcing_record_offset(0, field, 0) * sizeof(float));
+}
+
+int greb_forcing_record_field_static(int field) { return (field < 0 || field >= kFrFields) ? -1 : (field < kFrStaticFields ? 1 : 0); }
+
+long long greb_forcing_record_static_floats(void) { return (long long)kFrStaticFloats; }
+
+long long greb_forcing_record_step_floats(void) { return (long long)kFrStepFloats; }
+
+long long greb_forcing_record_bytes(void) { return (long long)kFrBytes; }
+
+const char* greb_forcing_record_field_name(int field) {
+  static const char* const names[kFrFields] = {"z_topo", "glacier", "z_ocean", "wz_air", "tclim", "cldclim", "mldclim", "mldclim_prev",
+                                               "swetclim", "wind_speed"};
+  return (field < 0 || field >= kFrFields) ? nullptr : names[field];
+}
+
+int greb_engine_get_forcing_record(greb_engine* e, int set, int step, float* out) {
+  const char* who = "get_forcing_record: ";
+  if (!e) return fail(nullptr, GREB_E_INVALID, std::string(who) + "no engine (greb_engine is NULL)");
+  if (!out || set < 0 || set >= (int)e->bound.size() || step < 1 || step > kNT)
+    return fail(e, GREB_E_INVALID, std::string(who) + "bad argument (set 0 ... sets made, step 1 ... 730)");
+  if (!e->bound[(size_t)set].frec)
+    return fail(e, GREB_E_UNSUPPORTED, std::string(who) + "this engine keeps no forcing records (they belong to the FAST fused member kernel)");
+  HIP_TRY(e, hipSetDevice(e->device));
+  HIP_TRY(e, hipStreamSynchronize(e->stream)); // the pack kernel runs on the engine's stream
+  const float* rec = e->bound[(size_t)set].frec;
+  HIP_TRY(e, hipMemcpy(out, rec, kFrStaticFloats * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(e, hipMemcpy(out + kFrStaticFloats, rec + kFrStaticFloats + (size_t)(step - 1) * kFrStepFloats, kFrStepFloats * sizeof(float),
+                       hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -51,6 +51,28 @@ constexpr int kBoundaryFields = 13; // pointers of a BoundarySet; the first kBou
 constexpr int kBoundaryInputs = 9;
 constexpr int kMaxBoundarySets = 16;
 
+// Forcing record of one boundary set (FAST fused 96x48 member kernel only): everything the point physics of
+// the default scenario and flux-correction quads reads from boundary data, packed in two parts: the four static fields
+// [row 0..47][field][96], then the step's fields [step 0..729][row 0..47][field][96] -- so that a quad's operands sit at a
+// scalar base (the static part, the step's slice) plus a 32-bit lane offset (row and quad) plus the field's instruction
+// immediate.  kFrWind is the wind-speed term of hydro (greb_device.h: wind_speed), evaluated once per set by the pack
+// kernel instead of per member and step.
+constexpr int kFrNx = 96, kFrNy = 48;
+enum { kFrZtopo, kFrGlacier, kFrZocean, kFrWzAir, kFrStaticFields,
+       kFrTclim = kFrStaticFields, kFrCld, kFrMld, kFrMldPrev, kFrSwet, kFrWind, kFrFields };
+constexpr int kFrStepFields = kFrFields - kFrStaticFields;
+// offset in floats of (row, field, longitude) inside the field's part -- the static part or one step's slice: host (pack
+// launch, read-back, layout query) and device
+constexpr unsigned forcing_record_offset(int row, int field, int lon) {
+  return field < kFrStaticFields ? ((unsigned)row * kFrStaticFields + (unsigned)field) * kFrNx + (unsigned)lon
+                                 : ((unsigned)row * kFrStepFields + (unsigned)(field - kFrStaticFields)) * kFrNx + (unsigned)lon;
+}
+constexpr unsigned kFrStaticFloats = forcing_record_offset(kFrNy, 0, 0), kFrStepFloats = forcing_record_offset(kFrNy, kFrStaticFields, 0);
+constexpr size_t kFrBytes = ((size_t)kFrStaticFloats + (size_t)kNT * kFrStepFloats) * sizeof(float);
+static_assert(forcing_record_offset(0, kFrFields - 1, 0) * sizeof(float) <= 4095 && forcing_record_offset(0, kFrStaticFields - 1, 0) * sizeof(float) <= 4095,
+              "a field's offset must fit the immediate of a global load");
+static_assert(kFrBytes < (1ull << 31), "offsets into a record are 32-bit");
+
 // Everything the fused member kernel needs (passed by value as a kernel argument).
 struct MemberArgs {
   int nx, ny, np;
@@ -106,6 +128,13 @@ struct MemberArgs {
   const BoundarySet* bsets;     // [1 + sets made]; entry 0 holds the thirteen pointers above
   const int* bset_m;            // [nm] each member's set; null: every member of the launch is on the engine's own data
 };
+
+// The set table on the device: kSetTableEntries BoundarySet, then as many forcing-record pointers (entry 0: the engine's
+// own data).  The FAST fused member kernel reads its record pointer there in every variant (greb_physics_step.h:
+// member_record), so its launches carry MemberArgs::bsets also where no member is on a set; MemberArgs stays as it was.
+constexpr int kSetTableEntries = kMaxBoundarySets + 1;
+constexpr size_t kSetTableBytes = kSetTableEntries * (sizeof(BoundarySet) + sizeof(const float*));
+inline const float** set_table_records(BoundarySet* table) { return (const float**)(table + kSetTableEntries); }
 
 // GREB_NBUDGET, GREB_B_*: the flux terms of one step in the order of include/greb_engine.h
 enum { kBsw, kBLWsurf, kBLWdown, kBLWabs, kBQsens, kBQlat, kBQlatAir, kBdqEva, kBdqRain, kBdTocean, kBdTo, kBdTaCrcl, kBdqCrcl, kNBudget };
@@ -167,6 +196,8 @@ bool member_layout_supported(const RowTables& tab, int nx, int ny);
 // how often the member kernel's static deal computes each row-quad of the 96x48 grid: counts[48 * 24]
 void member_deal_cover(bool strict, int* counts);
 hipError_t launch_member_kernel(const MemberArgs& a, int n_members, bool strict, hipStream_t s);
+// the forcing record (kFrBytes at `rec`) of the set whose thirteen device arrays `b` names (greb_member.hip)
+hipError_t launch_pack_forcing(const BoundarySet& b, float* rec, hipStream_t s);
 hipError_t launch_circulation_g96(const float* X, const float* wz, const float* u, const float* v, float* dX,
                                   const RowTables* tab_dev, int batch, int nsub, bool strict, hipStream_t s);
 

@@ -11,7 +11,10 @@
 //                 WX, WY [48][96]                 this step's winds, scaled by the row's advection
 //                                                 constants (FAST) or raw (STRICT and polar rows)
 //                 row constants, Jacobi row buffers of the polar rows
-//   HBM/L2        Tsurf, Tocean, cap_surf, accumulators, forcing: touched once per model step
+//   HBM/L2        Tsurf, Tocean, cap_surf, accumulators, forcing: touched once per model step.  FAST reads the
+//                 boundary data of the point physics from the set's packed forcing record (greb_kernels.h: static
+//                 part + one slice per step, wind speed finished; made by pack_forcing_kernel below), STRICT from
+//                 the raw arrays; the winds are staged from the raw uclim / vclim in both
 //   Registers hold nothing across sub-steps.
 //
 // The tracer interleave makes every FAST arithmetic instruction a packed v_pk_*_f32 on an aligned
@@ -974,6 +977,10 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
     const float co2 = FLUX ? co2_flux : a.co2[(size_t)m * a.co2_stride + a.co2_year0 + yr_rel]; // :924
     const MemberForce mf = member_force<FORCE>(a, m, ck);
     const BoundPtr B = member_boundary<BOUND>(a, bset);
+    // FAST: boundary data from the set's forcing record, everything else by scalar base + one 32-bit offset per quad
+    constexpr int ROUTE = STRICT ? kRouteArrays : kRouteRecord;
+    const float* rec = nullptr;
+    if constexpr (!STRICT) rec = member_record(a, bset);
     lfloat* Xf = lds + kOffX + cur * XB;       // the tracers after the 24 sub-steps
     lfloat* red = lds + kOffX + (cur ^ 1) * XB; // idle buffer: annual-mean reduction scratch
     // Each thread takes whole quads (4 consecutive longitudes): every load/store of the ~26
@@ -1002,8 +1009,8 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 #pragma unroll 1
       for (int qd = tid; qd < NP / 4; qd += kThreads) {
         const q8 xpair = ld8(Xf + (qd / NQ) * RS, qd % NQ);
-        const PhysIn in = physics_load<V>(a, qd, ck, state, acc, corr, xsw, mf, B);
-        (void)physics_compute<STRICT, V | kVBudget>(a, P, in, co2, comp(xpair, 0), comp(xpair, 1), xsw, bs, 4 * qd, mf);
+        const PhysIn in = physics_load<V, ROUTE>(a, qd, ck, state, acc, corr, xsw, mf, B, rec);
+        (void)physics_compute<STRICT, V | kVBudget, ROUTE>(a, P, in, co2, comp(xpair, 0), comp(xpair, 1), xsw, bs, 4 * qd, mf);
       }
     }
 #pragma unroll 1
@@ -1013,7 +1020,7 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 #endif
       const q8 xpair = ld8(Xf + (qd / NQ) * RS, qd % NQ);
       f4 oTa, oq, tsm;
-      physics_quad<STRICT, V & ~kVBudget>(a, P, m, qd, ck, co2, state, acc, corr, comp(xpair, 0), comp(xpair, 1), oTa, oq, tsm, xsw, mf, B);
+      physics_quad<STRICT, V & ~kVBudget, ROUTE>(a, P, m, qd, ck, co2, state, acc, corr, comp(xpair, 0), comp(xpair, 1), oTa, oq, tsm, xsw, mf, B, rec);
       st8(Xf + (qd / NQ) * RS, qd % NQ, zip(oTa, oq));
       if (ityr == kNT) st4(red + 4 * qd, tsm);
     }
@@ -1065,11 +1072,42 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
   // all five state fields were written back every step
 }
 
+// The forcing record of one boundary set (greb_kernels.h): one thread per (step, point).  The wind-speed term is
+// wind_speed<false>, the expression hydro<false> evaluates: the bits are those the member kernel used to compute itself.
+static_assert(kFrNx == NX && kFrNy == NY, "the forcing record is the fused kernel's grid");
+__global__ __launch_bounds__(256) void pack_forcing_kernel(BoundarySet b, float* __restrict__ rec) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= (unsigned)kNT * NP) return;
+  const unsigned step = i / NP, p = i - step * NP, row = p / NX, lon = p - row * NX;
+  const unsigned prev = step > 0 ? step - 1 : kNT - 1; // StepClock::offm
+  const float zt = b.z_topo[p];
+  if (step == 0) { // the static part, in front
+    float* o = rec + forcing_record_offset((int)row, 0, (int)lon);
+    o[forcing_record_offset(0, kFrZtopo, 0)] = zt;
+    o[forcing_record_offset(0, kFrGlacier, 0)] = b.glacier[p];
+    o[forcing_record_offset(0, kFrZocean, 0)] = b.z_ocean[p];
+    o[forcing_record_offset(0, kFrWzAir, 0)] = b.wz_air[p];
+  }
+  float* o = rec + kFrStaticFloats + (size_t)step * kFrStepFloats + forcing_record_offset((int)row, kFrStaticFields, (int)lon);
+  o[forcing_record_offset(0, kFrTclim, 0)] = b.tclim[i];
+  o[forcing_record_offset(0, kFrCld, 0)] = b.cldclim[i];
+  o[forcing_record_offset(0, kFrMld, 0)] = b.mldclim[i];
+  o[forcing_record_offset(0, kFrMldPrev, 0)] = b.mldclim[(size_t)prev * NP + p];
+  o[forcing_record_offset(0, kFrSwet, 0)] = b.swetclim[i];
+  o[forcing_record_offset(0, kFrWind, 0)] = wind_speed<false>(b.uclim[i], b.vclim[i], zt);
+}
+
+hipError_t launch_pack_forcing(const BoundarySet& b, float* rec, hipStream_t s) {
+  hipLaunchKernelGGL(pack_forcing_kernel, dim3((kNT * NP + 255) / 256), dim3(256), 0, s, b, rec);
+  return hipGetLastError();
+}
+
 template <bool STRICT, unsigned V>
 struct MemberFamily { static auto kernel() { return &member_kernel<STRICT, V>; } };
 
 hipError_t launch_member_kernel(const MemberArgs& a, int n_members, bool strict, hipStream_t s) {
   if (a.nx != NX || a.ny != NY) return hipErrorInvalidValue;
+  if (!strict && !a.bsets) return hipErrorInvalidValue; // the FAST kernels read their forcing record behind the set table
   unsigned v;
   if (hipError_t e = select_variant(a, &v); e != hipSuccess) return e;
   const auto kern = pick_variant<MemberFamily>(strict, v);

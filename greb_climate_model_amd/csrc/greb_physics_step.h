@@ -92,6 +92,24 @@ __device__ __forceinline__ BoundPtr member_boundary(const MemberArgs& a, int bse
 // field `f` of the member's set, or the launch's own
 #define GREB_BF(f) (BOUND ? (const float*)B->f : a.f)
 
+// Where a quad's operands come from (a compile-time route of physics_load / physics_compute / physics_store, not a variant):
+// kRouteArrays: one base pointer per array, any grid (the STRICT member kernel and the any-grid kernels);
+// kRouteRecord: the FAST fused 96x48 member kernel -- boundary data from the set's forcing record (greb_kernels.h), the
+// wind-speed term finished; everything else by a scalar base plus ONE opaque 32-bit byte offset per quad, so that every
+// access takes the scalar-base form and no 64-bit address lives across the quad's arithmetic.
+enum { kRouteArrays, kRouteRecord };
+// the record of the member's set (bset: 0 without kVBound), fetched from the set table where it is used, as
+// member_boundary fetches the set's pointers: one scalar load per model step, nothing of it lives across the sub-steps
+__device__ __forceinline__ const float* member_record(const MemberArgs& a, int bset) {
+  unsigned long long p = (unsigned long long)((const float* const*)(a.bsets + kSetTableEntries) + bset);
+  asm volatile("" : "+s"(p));
+  return *(const float* const __attribute__((address_space(4)))*)p;
+}
+// base + byte offset, the offset opaque to the optimiser (else it rebuilds a 64-bit induction variable per array)
+__device__ __forceinline__ const float* at_bytes(const float* base, unsigned boff) { return (const float*)((const char*)base + boff); }
+__device__ __forceinline__ float* at_bytes(float* base, unsigned boff) { return (float*)((char*)base + boff); }
+__device__ __forceinline__ unsigned opaque_v(unsigned x) { asm("" : "+v"(x)); return x; }
+
 // One quad in three pieces -- load, compute, store -- so that a caller with several quads per thread can request the
 // next quad's operands BETWEEN the arithmetic of the current one and its stores (vector-memory operations retire in
 // order: loads issued behind a quad's stores wait for those stores as well).
@@ -100,7 +118,8 @@ __device__ __forceinline__ BoundPtr member_boundary(const MemberArgs& a, int bse
 struct PhysIn {
   f4 Ts, Ta, To, q, cap;                      // state
   f4 zt, gl, zo, ez;                          // static fields
-  f4 tcl, cld, mld, mldm, swet, u, v;         // forcing of the step (mldm: previous step, :507-508)
+  f4 tcl, cld, mld, mldm, swet, u, v;         // forcing of the step (mldm: previous step, :507-508); u, v: kRouteArrays only
+  f4 wind;                                    // kRouteRecord only: the wind-speed term of hydro instead of u and v
   f4 c0, c1, c2;                              // flux: Toclim, qclim, -- ; scenario: TF, qF, ToF
   f4 acc0, acc1, acc2, acc3, acc4, acc5;      // monthly sums, annual Tsurf sum
   f4 qcl, tclp;                               // experiments only
@@ -112,12 +131,66 @@ struct PhysOut { // everything the stores need: the inputs are dead once this ex
   f4 s0, s1, s2, s3, s4; // the monthly sums including this step (:974)
 };
 
+// kRouteRecord (96x48; rec: the record of the member's set, member_record).  The quad's row comes from qd, the grid being
+// known; boundary data the record does not hold (the rare reads below) comes from the raw arrays.
 template <unsigned V>
+__device__ __forceinline__ PhysIn physics_load_record(const MemberArgs& a, int qd, const StepClock& ck, const float* __restrict__ state,
+                                                      const float* __restrict__ acc, const float* __restrict__ corr, unsigned xsw_member,
+                                                      const MemberForce& F, BoundPtr B, const float* __restrict__ rec) {
+  constexpr bool FLUX = V & kVFlux, EXP = V & kVExp, FORCE = V & kVForce, BOUND = V & kVBound;
+  constexpr int NQ = kFrNx / 4, np = kFrNx * kFrNy;
+  const int row = qd / NQ;
+  const size_t off = ck.off, offm = ck.offm;
+  const unsigned xsw = EXP ? xsw_member : 0u;
+  const unsigned bo = opaque_v(16u * (unsigned)qd);                                                      // the quad in an [np] array
+  const unsigned lon4 = 4u * (unsigned)(qd - row * NQ);
+  const unsigned ro_static = opaque_v((forcing_record_offset(row, 0, 0) + lon4) * 4u);              // ... in the record's static part
+  const unsigned ro = opaque_v((forcing_record_offset(row, kFrStaticFields, 0) + lon4) * 4u);       // ... in the step's slice
+  const float* slice = rec + kFrStaticFloats + (size_t)(ck.ityr - 1) * kFrStepFloats;
+  auto fr = [&](int field) {
+    return ld4(at_bytes(field < kFrStaticFields ? rec : slice, field < kFrStaticFields ? ro_static : ro) + forcing_record_offset(0, field, 0));
+  };
+  PhysIn i;
+  i.Ts = ld4(at_bytes(state, bo)); i.Ta = ld4(at_bytes(state + np, bo)); i.To = ld4(at_bytes(state + 2 * np, bo));
+  i.q = ld4(at_bytes(state + 3 * np, bo)); i.cap = ld4(at_bytes(state + 4 * np, bo));
+  i.zt = fr(kFrZtopo); i.gl = fr(kFrGlacier); i.zo = fr(kFrZocean); i.ez = fr(kFrWzAir);
+  i.tcl = fr(kFrTclim); i.cld = fr(kFrCld); i.mld = fr(kFrMld); i.mldm = fr(kFrMldPrev); i.swet = fr(kFrSwet); i.wind = fr(kFrWind);
+  const unsigned so = opaque_v(4u * (unsigned)row);
+  if (FORCE) {
+#pragma clang fp contract(off)
+    i.solar = *at_bytes(F.solar + (size_t)(ck.ityr - 1) * kFrNy, so) * F.scale; // one rounding, then sw = solar * (1 - albedo)
+  } else i.solar = *at_bytes(a.sw_solar + (size_t)(ck.ityr - 1) * kFrNy, so);
+  if (FLUX) { i.c0 = ld4(at_bytes(GREB_BF(toclim), bo)); i.c1 = ld4(at_bytes(GREB_BF(qclim) + off, bo)); i.c2 = zero4(); }
+  else {
+    i.c0 = ld4(at_bytes(corr + off, bo)); i.c1 = ld4(at_bytes(corr + (size_t)kNT * np + off, bo));
+    i.c2 = ld4(at_bytes(corr + (size_t)2 * kNT * np + off, bo));
+  }
+  i.acc0 = i.acc1 = i.acc2 = i.acc3 = i.acc4 = zero4();
+#ifdef GREB_TUNING
+  const bool no_acc = a.dbg & 1; // timing experiments (tools/stamp_member.py, GREB_DEBUG_PHYS)
+#else
+  constexpr bool no_acc = false;
+#endif
+  i.acc5 = no_acc ? zero4() : ld4(at_bytes(acc + 5 * np, bo));
+  if (!FLUX && !no_acc) {
+    i.acc0 = ld4(at_bytes(acc, bo)); i.acc1 = ld4(at_bytes(acc + np, bo)); i.acc2 = ld4(at_bytes(acc + 2 * np, bo));
+    i.acc3 = ld4(at_bytes(acc + 3 * np, bo)); i.acc4 = ld4(at_bytes(acc + 4 * np, bo));
+  }
+  i.qcl = zero4(); i.tclp = zero4();
+  if (EXP && (xsw & kXLwLinear)) i.qcl = FLUX ? i.c1 : ld4(at_bytes(GREB_BF(qclim) + off, bo));
+  if (EXP && !FLUX && (xsw & kXSstPlus1)) i.tclp = ld4(at_bytes(GREB_BF(tclim) + offm, bo));
+  i.fw = zero4();
+  if (FORCE && F.space) i.fw = ld4(at_bytes(F.space, bo));
+  return i;
+}
+
+template <unsigned V, int ROUTE = kRouteArrays>
 __device__ __forceinline__ PhysIn physics_load(const MemberArgs& a, int qd, const StepClock& ck, const float* __restrict__ state,
                                                const float* __restrict__ acc, const float* __restrict__ corr, unsigned xsw_member,
-                                               const MemberForce& F, BoundPtr B) {
+                                               const MemberForce& F, BoundPtr B, const float* __restrict__ rec = nullptr) {
   constexpr bool FLUX = V & kVFlux, EXP = V & kVExp, FORCE = V & kVForce, BOUND = V & kVBound;
   static_assert(variant_valid(V), "no such variant of the step kernels");
+  if constexpr (ROUTE == kRouteRecord) return physics_load_record<V>(a, qd, ck, state, acc, corr, xsw_member, F, B, rec);
   const int nx = a.nx, ny = a.ny, np = a.np, p0 = 4 * qd;
   const size_t off = ck.off, offm = ck.offm;
   const unsigned xsw = EXP ? xsw_member : 0u;
@@ -195,7 +268,7 @@ __device__ __forceinline__ void budget_add(const BudgetSink& b, int np, int term
 // budget sums (bs; p0: the quad's first point) -- under a member's switches they are what the update really used.
 // FORCE: CO2 is the member's scalar blended per point with its reference by the pattern's weight (forced_co2); the insolation
 // came forced from physics_load.
-template <bool STRICT, unsigned V>
+template <bool STRICT, unsigned V, int ROUTE = kRouteArrays>
 __device__ __forceinline__ PhysOut physics_compute(const MemberArgs& a, const Phys& P, const PhysIn& in, float co2, const f4& xTa,
                                                    const f4& xq, unsigned xsw_member, const BudgetSink& bs, int p0,
                                                    const MemberForce& F) {
@@ -229,7 +302,8 @@ __device__ __forceinline__ PhysOut physics_compute(const MemberArgs& a, const Ph
     budget_add<BUDGET>(bs, np, kBLWabs, p0 + e, LWabs);
     const float Qsens = P.ct_sens * (Ta1 - Ts1); // :295
     budget_add<BUDGET>(bs, np, kBQsens, p0 + e, Qsens);
-    hydro<STRICT>(P, Ts1, q1, in.u.v[e], in.v.v[e], zt, ez, in.swet.v[e], Qlat, Qlat_air, dq_eva, dq_rain, xsw);
+    if constexpr (ROUTE == kRouteRecord) hydro_wind<STRICT>(P, Ts1, q1, in.wind.v[e], ez, in.swet.v[e], Qlat, Qlat_air, dq_eva, dq_rain, xsw);
+    else hydro<STRICT>(P, Ts1, q1, in.u.v[e], in.v.v[e], zt, ez, in.swet.v[e], Qlat, Qlat_air, dq_eva, dq_rain, xsw);
     budget_add<BUDGET>(bs, np, kBQlat, p0 + e, Qlat); budget_add<BUDGET>(bs, np, kBQlatAir, p0 + e, Qlat_air);
     budget_add<BUDGET>(bs, np, kBdqEva, p0 + e, dq_eva); budget_add<BUDGET>(bs, np, kBdqRain, p0 + e, dq_rain);
     deep_ocean<STRICT>(P, Ts1, To1, zt, mld, in.mldm.v[e], in.zo.v[e], dT_ocean, dTo, xsw);
@@ -271,10 +345,64 @@ __device__ __forceinline__ PhysOut physics_compute(const MemberArgs& a, const Ph
 
 // state write-back, correction / accumulation / monthly records (:974-984), annual mean (:945-956).  Returns the
 // annual-mean Tsurf quad in tsmn_mean when ityr == 730 (the caller feeds the global-mean sum, :954).
+// kRouteRecord: the same stores through the quad's opaque byte offset
 template <bool FLUX>
+__device__ __forceinline__ void physics_store_record(const MemberArgs& a, int m, int qd, const StepClock& ck,
+                                                     const PhysOut& o, float* __restrict__ state, float* __restrict__ acc,
+                                                     float* __restrict__ corr, f4& tsmn_mean) {
+  constexpr int np = kFrNx * kFrNy;
+  const int mon = ck.mon;
+  const size_t off = ck.off;
+  const unsigned bo = opaque_v(16u * (unsigned)qd);
+#ifdef GREB_TUNING
+  const bool no_acc = a.dbg & 1, no_wb = a.dbg & 2;
+#else
+  constexpr bool no_acc = false, no_wb = false;
+#endif
+  if (!no_wb) {
+    st4(at_bytes(state, bo), o.Ts); st4(at_bytes(state + np, bo), o.Ta); st4(at_bytes(state + 2 * np, bo), o.To);
+    st4(at_bytes(state + 3 * np, bo), o.q); st4(at_bytes(state + 4 * np, bo), o.cap);
+  }
+  if (FLUX) {
+    st4(at_bytes(corr + off, bo), o.TF); st4(at_bytes(corr + (size_t)kNT * np + off, bo), o.qF);
+    st4(at_bytes(corr + (size_t)2 * kNT * np + off, bo), o.ToF);
+  } else {
+#pragma clang fp contract(off)
+    f4 s0 = o.s0, s1 = o.s1, s2 = o.s2, s3 = o.s3, s4 = o.s4;
+    if (mon >= 0) { // :975-984
+      const float ndm = (float)(kMonthDays[mon] * 2);
+      float* rec = a.monthly + (((size_t)m * a.monthly_years + (a.year_out0 + ck.yr_rel)) * 12 + mon) * 5 * np;
+      f4 r0, r1, r2, r3, r4;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        r0.v[e] = s0.v[e] / ndm; r1.v[e] = s1.v[e] / ndm; r2.v[e] = s2.v[e] / ndm; r3.v[e] = s3.v[e] / ndm; r4.v[e] = s4.v[e] / ndm;
+      }
+      st4_nt(at_bytes(rec, bo), r0); st4_nt(at_bytes(rec + np, bo), r1); st4_nt(at_bytes(rec + 2 * np, bo), r2);
+      st4_nt(at_bytes(rec + 3 * np, bo), r3); st4_nt(at_bytes(rec + 4 * np, bo), r4);
+      s0 = s1 = s2 = s3 = s4 = zero4();
+    }
+    if (!no_acc) {
+      st4(at_bytes(acc, bo), s0); st4(at_bytes(acc + np, bo), s1); st4(at_bytes(acc + 2 * np, bo), s2);
+      st4(at_bytes(acc + 3 * np, bo), s3); st4(at_bytes(acc + 4 * np, bo), s4);
+    }
+  }
+  if (ck.ityr == kNT) { // :948-956
+#pragma clang fp contract(off)
+    f4 t;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) t.v[e] = o.tsmn.v[e] / (float)kNT;
+    tsmn_mean = t;
+    if (!no_acc) st4(at_bytes(acc + 5 * np, bo), zero4());
+  } else {
+    if (!no_acc) st4(at_bytes(acc + 5 * np, bo), o.tsmn);
+  }
+}
+
+template <bool FLUX, int ROUTE = kRouteArrays>
 __device__ __forceinline__ void physics_store(const MemberArgs& a, int m, int qd, const StepClock& ck,
                                               const PhysOut& o, float* __restrict__ state, float* __restrict__ acc,
                                               float* __restrict__ corr, f4& tsmn_mean) {
+  if constexpr (ROUTE == kRouteRecord) { physics_store_record<FLUX>(a, m, qd, ck, o, state, acc, corr, tsmn_mean); return; }
   const int np = a.np, p0 = 4 * qd, mon = ck.mon;
   const size_t off = ck.off;
 #ifdef GREB_TUNING
@@ -318,15 +446,16 @@ __device__ __forceinline__ void physics_store(const MemberArgs& a, int m, int qd
 }
 
 // the three pieces in a row (one quad per thread: the any-grid engine)
-template <bool STRICT, unsigned V>
+template <bool STRICT, unsigned V, int ROUTE = kRouteArrays>
 __device__ __forceinline__ void physics_quad(const MemberArgs& a, const Phys& P, int m, int qd, const StepClock& ck,
                                              float co2, float* __restrict__ state, float* __restrict__ acc,
                                              float* __restrict__ corr, const f4& xTa, const f4& xq, f4& oTa_out,
-                                             f4& oq_out, f4& tsmn_mean, unsigned xsw, const MemberForce& F, BoundPtr B) {
+                                             f4& oq_out, f4& tsmn_mean, unsigned xsw, const MemberForce& F, BoundPtr B,
+                                             const float* __restrict__ rec = nullptr) {
   constexpr bool FLUX = V & kVFlux, BUDGET = V & kVBudget;
-  const PhysIn in = physics_load<V>(a, qd, ck, state, acc, corr, xsw, F, B);
-  const PhysOut o = physics_compute<STRICT, V>(a, P, in, co2, xTa, xq, xsw, budget_sink<BUDGET>(a, m, ck), 4 * qd, F);
-  physics_store<FLUX>(a, m, qd, ck, o, state, acc, corr, tsmn_mean);
+  const PhysIn in = physics_load<V, ROUTE>(a, qd, ck, state, acc, corr, xsw, F, B, rec);
+  const PhysOut o = physics_compute<STRICT, V, ROUTE>(a, P, in, co2, xTa, xq, xsw, budget_sink<BUDGET>(a, m, ck), 4 * qd, F);
+  physics_store<FLUX, ROUTE>(a, m, qd, ck, o, state, acc, corr, tsmn_mean);
   oTa_out = o.Ta; oq_out = o.q;
 }
 #undef GREB_BF

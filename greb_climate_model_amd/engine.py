@@ -62,7 +62,10 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_member_deal_cover", "greb_engine_set_forcing_tables", "greb_engine_set_member_forcing",
            "greb_engine_add_boundary_set", "greb_engine_set_member_boundary", "greb_step_variant", "greb_step_variants",
            "greb_clim_create", "greb_clim_destroy", "greb_clim_add_year_dev", "greb_clim_finish_dev", "greb_engine_run_clim",
-           "greb_ens_create", "greb_ens_destroy", "greb_ens_reduce_dev", "greb_engine_run_ens"]
+           "greb_ens_create", "greb_ens_destroy", "greb_ens_reduce_dev", "greb_engine_run_ens",
+           "greb_forcing_record_offset", "greb_forcing_record_field_bytes", "greb_forcing_record_step_floats",
+           "greb_forcing_record_bytes", "greb_forcing_record_field_name", "greb_engine_get_forcing_record",
+           "greb_forcing_record_field_static", "greb_forcing_record_static_floats"]
 
 
 def _check(rc: int, h=None):
@@ -400,6 +403,17 @@ class Engine:
             raise GrebError(-1, f"set_member_boundary: {self.nm} set ids expected")
         _check(lib().greb_engine_set_member_boundary(self.h, ids.ctypes.data_as(C.POINTER(C.c_int32)), C.c_uint(flags)), self.h)
 
+    def forcing_record(self, step: int, set_id: int = 0) -> np.ndarray:
+        """Debug read-back (greb_engine_get_forcing_record): step `step` (1 ... 730) of the packed forcing record of
+        boundary set `set_id` together with the record's static part, as [row][field][longitude] (fields:
+        forcing_record_layout().names)."""
+        lay = forcing_record_layout()
+        out = np.empty(lay.static_floats + lay.step_floats, np.float32)
+        _check(lib().greb_engine_get_forcing_record(self.h, int(set_id), int(step), abi.fptr(out)), self.h)
+        ns = sum(lay.static)
+        return np.concatenate([out[:lay.static_floats].reshape(lay.ny, ns, lay.nx),
+                               out[lay.static_floats:].reshape(lay.ny, len(lay.names) - ns, lay.nx)], axis=1)
+
     def point_physics(self, ityr: int, co2: float, in5) -> np.ndarray:
         in5 = np.ascontiguousarray(in5, np.float32)
         out = np.empty((15, self.ny, self.nx), np.float32)
@@ -477,6 +491,35 @@ def member_deal_cover(strict=False):
     out = np.zeros((48, 24), np.int32)
     _check(lib().greb_member_deal_cover(int(bool(strict)), out.ctypes.data_as(C.POINTER(C.c_int))))
     return out
+
+
+class RecordLayout:
+    """forcing_record_layout(): the packed forcing record of the FAST fused member kernel as the library lays it out."""
+
+    def __init__(self, names, static, offsets, field_bytes, static_floats, step_floats, record_bytes):
+        self.names, self.static, self.offsets, self.field_bytes = names, static, offsets, field_bytes
+        self.static_floats, self.step_floats, self.record_bytes = static_floats, step_floats, record_bytes
+        self.ny, _, self.nx = offsets.shape
+
+
+def forcing_record_layout(nx: int = 96, ny: int = 48) -> RecordLayout:
+    """Host-only diagnostic (include/greb_engine.h: greb_forcing_record_*): field names, which of them are static, the
+    offset in floats of every (row, field, longitude) inside the field's part (the static part or one step's slice) as an
+    int64 array [ny][fields][nx], every field's immediate offset in bytes, the floats of the static part and of a slice
+    and the bytes of a record."""
+    L = lib()
+    for f in (L.greb_forcing_record_offset, L.greb_forcing_record_field_bytes, L.greb_forcing_record_static_floats,
+              L.greb_forcing_record_step_floats, L.greb_forcing_record_bytes):
+        f.restype = C.c_longlong
+    L.greb_forcing_record_field_name.restype = C.c_char_p
+    names = []
+    while L.greb_forcing_record_field_name(len(names)) is not None:
+        names.append(L.greb_forcing_record_field_name(len(names)).decode())
+    nf = len(names)
+    off = np.array([[[L.greb_forcing_record_offset(k, f, i) for i in range(nx)] for f in range(nf)] for k in range(ny)], np.int64)
+    return RecordLayout(tuple(names), tuple(bool(L.greb_forcing_record_field_static(f)) for f in range(nf)), off,
+                        [int(L.greb_forcing_record_field_bytes(f)) for f in range(nf)], int(L.greb_forcing_record_static_floats()),
+                        int(L.greb_forcing_record_step_floats()), int(L.greb_forcing_record_bytes()))
 
 
 def step_variant(flux_phase=False, switches=False, budget=False, forced=False, on_sets=False):

@@ -513,6 +513,30 @@ int greb_circulation_launch_plan(const greb_params* p, int nx, int ny, int n_mem
  * Returns 0, < 0 on a bad argument. */
 int greb_member_deal_cover(int strict, int* counts);
 
+/* ---- forcing records (diagnostic) -------------------------------------------------------------------
+ * The FAST fused 96x48 member kernel reads the boundary data of the point physics from one packed, read-only record per
+ * boundary set, made on the device when the set's data is uploaded, in two parts: the static fields [row 0..47][field][96]
+ * -- z_topo, glacier, z_ocean, wz_air -- and behind them the fields of every step [step 0..729][row 0..47][field][96] --
+ * tclim, cldclim, mldclim, mldclim of the previous step (step 1 takes step 730), swetclim and the wind-speed term of the
+ * latent heat flux (src/greb.f90:455-457) evaluated from uclim, vclim and z_topo.  greb_forcing_record_field_name gives the
+ * ten in this order.  greb_engine_describe reports the bytes the records take.
+ * Layout queries, host only (no GPU call): whether a field is static (1 / 0, -1 outside), the offset in floats of (row,
+ * field, longitude) inside the field's part -- the static part or one step's slice (-1 outside) --, a field's offset in
+ * bytes from the first field of its row and part (what the kernel folds into an instruction immediate, so at most 4 095),
+ * the floats of the static part and of one step's slice, and the bytes of one record (the static part and 730 slices). */
+#define GREB_FORCING_RECORD_FIELDS 10
+int greb_forcing_record_field_static(int field);
+long long greb_forcing_record_offset(int row, int field, int lon);
+long long greb_forcing_record_field_bytes(int field);
+long long greb_forcing_record_static_floats(void);
+long long greb_forcing_record_step_floats(void);
+long long greb_forcing_record_bytes(void);
+const char* greb_forcing_record_field_name(int field); /* NULL outside 0 ... GREB_FORCING_RECORD_FIELDS - 1 */
+/* Debug read-back of set `set`'s record (0 = the engine's own data): the static part, then the slice of step `step`
+ * (1 ... 730), into out[greb_forcing_record_static_floats() + greb_forcing_record_step_floats()].  GREB_E_UNSUPPORTED on an
+ * engine that keeps none (STRICT, any-grid). */
+int greb_engine_get_forcing_record(greb_engine* e, int set, int step, float* out);
+
 /* Diagnostic, host only (no GPU call): the variant of the step kernels -- a mask of GREB_V_* -- that a launch takes in the
  * flux-correction (flux_phase != 0) or scenario phase when the engine has experiment switches set (switches), the call is
  * greb_engine_run_budget (budget), a member is forced (forced) or a member is on a boundary set (on_sets).  This is the
