@@ -16,8 +16,8 @@ LIB = os.path.join(PKG, "libgreb_hip.so")
 # the same sources with -DGREB_TUNING: the timing-experiment knobs of tools/ (GREB_DEBUG_SKIP, GREB_DEBUG_NSUB, ...)
 # exist only in this variant; the release library above never reads the environment
 LIB_TUNING = os.path.join(PKG, "libgreb_hip_tuning.so")
-SOURCES = ["greb_engine.cpp", "greb_kernels.hip", "greb_member.hip", "greb_ensemble.hip", "greb_rows.hip", "greb_step_rows.hip", "greb_circ_rows.hip", "greb_strip_order.cpp", "greb_diag.hip", "greb_clim.hip", "greb_ens.hip"]
-HEADERS = ["greb_device.h", "greb_kernels.h", "greb_stencil.h", "greb_chain6.h", "greb_rows.h", "greb_step_strip.h", "greb_pair.h", "greb_physics_step.h", "greb_diag.h", "greb_clim.h", "greb_ens.h", os.path.join(ROOT, "include", "greb_engine.h")]
+SOURCES = ["greb_engine.cpp", "greb_run.cpp", "greb_plans.cpp", "greb_members.cpp", "greb_batched.cpp", "greb_kernels.hip", "greb_member.hip", "greb_ensemble.hip", "greb_rows.hip", "greb_step_rows.hip", "greb_circ_rows.hip", "greb_strip_order.cpp", "greb_diag.hip", "greb_clim.hip", "greb_ens.hip"]
+HEADERS = ["greb_host.h", "greb_device.h", "greb_kernels.h", "greb_stencil.h", "greb_chain6.h", "greb_rows.h", "greb_step_strip.h", "greb_pair.h", "greb_physics_step.h", "greb_diag.h", "greb_clim.h", "greb_ens.h", os.path.join(ROOT, "include", "greb_engine.h")]
 # -O2: measured 1.4 % faster than -O3 on the fused member kernel (3 790 vs 3 735 yr/s), equal elsewhere
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value",
                "-I" + os.path.join(ROOT, "include")]
@@ -49,14 +49,19 @@ def needs_build(lib: str = LIB) -> bool:
     return any(os.path.getmtime(d) > t for s in SOURCES for d in _deps(s)) or os.path.getmtime(__file__) > t
 
 
-def build_lib(force: bool = False, verbose: bool = False, tuning: bool = False) -> str:
-    """One object per source (each with its own flags, rebuilt when the source, a header or this script is newer),
-    then one link.  No relocatable device code is needed: every device function lives in a header."""
-    lib = LIB_TUNING if tuning else LIB
-    if not force and not needs_build(lib):
-        return lib
+def _flags(tuning: bool) -> list[str]:
+    return [f for f in HIPCC_FLAGS if f != "-shared"] + (["-DGREB_TUNING"] if tuning else [])
+
+
+def _run(cmd: list[str], verbose: bool) -> None:
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True, cwd=CSRC)
+
+
+def _objects(tuning: bool, force: bool = False, verbose: bool = False) -> list[str]:
+    """One object per source, each with its own flags, rebuilt when the source, a header or this script is newer."""
     os.makedirs(OBJ_DIR, exist_ok=True)
-    flags = [f for f in HIPCC_FLAGS if f != "-shared"] + (["-DGREB_TUNING"] if tuning else [])
     objs = []
     for src in SOURCES:
         obj = os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ("_tuning.o" if tuning else ".o"))
@@ -64,15 +69,41 @@ def build_lib(force: bool = False, verbose: bool = False, tuning: bool = False) 
         newest = max(max(os.path.getmtime(d) for d in _deps(src)), os.path.getmtime(__file__))
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > newest:
             continue
-        cmd = [hipcc(), *flags, *EXTRA_FLAGS.get(src, []), "-c", os.path.join(CSRC, src), "-o", obj]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.run(cmd, check=True, cwd=CSRC)
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objs]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True, cwd=CSRC)
+        _run([hipcc(), *_flags(tuning), *EXTRA_FLAGS.get(src, []), "-c", os.path.join(CSRC, src), "-o", obj], verbose)
+    return objs
+
+
+def _link(lib: str, objs: list[str], verbose: bool) -> str:
+    _run([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objs], verbose)
     return lib
+
+
+def build_lib(force: bool = False, verbose: bool = False, tuning: bool = False) -> str:
+    """The objects, then one link.  No relocatable device code is needed: every device function lives in a header."""
+    lib = LIB_TUNING if tuning else LIB
+    if not force and not needs_build(lib):
+        return lib
+    return _link(lib, _objects(tuning, force, verbose), verbose)
+
+
+VARIANTS = os.path.join(ROOT, "variants")
+
+
+def build_variant(tag: str, recompile: dict[str, list[str]], tuning: bool = False, verbose: bool = False) -> str:
+    """variants/libgreb_<tag>.so for A/B runs of compile-time choices (GREB_LIB or GREB_BENCH_LIB selects it): the sources
+    in `recompile` are compiled with their usual flags and the extra ones given (a later -O wins), every other object
+    is the normal build's (SOURCES, EXTRA_FLAGS; built first where stale), tuning: of the -DGREB_TUNING library."""
+    unknown = sorted(set(recompile) - set(SOURCES))
+    if unknown:
+        raise ValueError(f"build_variant: {unknown} not in build.SOURCES")
+    os.makedirs(VARIANTS, exist_ok=True)
+    objs = _objects(tuning, verbose=verbose)
+    for i, src in enumerate(SOURCES):
+        if src in recompile:
+            objs[i] = os.path.join(VARIANTS, f"{os.path.splitext(src)[0]}_{tag}.o")
+            _run([hipcc(), *_flags(tuning), *EXTRA_FLAGS.get(src, []), *recompile[src], "-c", os.path.join(CSRC, src), "-o", objs[i]],
+                 verbose)
+    return _link(os.path.join(VARIANTS, f"libgreb_{tag}.so"), objs, verbose)
 
 
 LIB_ASAN = os.path.join(PKG, "libgreb_hip_asan.so")
@@ -157,6 +188,10 @@ def build_c_example(verbose: bool = False) -> str | None:
 
 
 if __name__ == "__main__":
+    import sys
+    if sys.argv[1:2] == ["variant"]:  # variant <tag> <release|tuning> <source,source,...> <extra flags...>
+        print(build_variant(sys.argv[2], {src: sys.argv[5:] for src in sys.argv[4].split(",")}, tuning=sys.argv[3] == "tuning", verbose=True))
+        sys.exit(0)
     print(build_lib(force=True, verbose=True))
     print(build_host(verbose=True))
     print(build_c_example(verbose=True))

@@ -21,7 +21,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import abi
+from . import _plan, abi
 
 SEASONS = ("DJF", "MAM", "JJA", "SON", "ANN")
 # the months of each season in the order they are added (DJF: Dec, Jan, Feb of the same calendar years)
@@ -61,10 +61,11 @@ class Result:
         return a[..., SEASONS.index(name), :, :, :]
 
 
-class Plan:
+class Plan(_plan.Handle):
     """greb_clim handle: grid, member count, each member's control member (-1: none; None: no control map) and the
     products (abi.C_* bits; default: MEAN, SEASONS and TREND, and their RESPONSE when there is a control map).  Host data
     only; creating one needs no GPU, and every argument error is a GrebError(-1) naming the offender."""
+    _destroy = "greb_clim_destroy"
 
     def __init__(self, nx: int, ny: int, n_members: int, control=None, what: int | None = None):
         from . import engine
@@ -78,39 +79,18 @@ class Plan:
             if ctl.shape != (self.nm,) or ctl.dtype.kind not in "iu":
                 raise engine.GrebError(-1, f"clim.Plan: control must hold {self.nm} integers, one per member")
             self.control = np.ascontiguousarray(ctl, np.int32)
-        self.h = C.c_void_p()
         cp = None if self.control is None else self.control.ctypes.data_as(C.POINTER(C.c_int32))
-        rc = engine.lib().greb_clim_create(self.nx, self.ny, self.nm, cp, C.c_uint(self.what & 0xFFFFFFFF), C.byref(self.h))
-        if rc != 0:
-            self.h = None
-            raise engine.GrebError(rc, engine.lib().greb_engine_last_error(None).decode())
-
-    def close(self):
-        if getattr(self, "h", None):
-            from . import engine
-            engine.lib().greb_clim_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create("greb_clim_create", self.nx, self.ny, self.nm, cp, C.c_uint(self.what & 0xFFFFFFFF))
 
 
 def add_year_dev(plan: Plan, monthly_year, k: int) -> None:
     """Year k (0-based) of the current period, a contiguous float32 GPU tensor [n_members][12][5][ny][nx], added to the
     plan's sums where it is (greb_clim_add_year_dev) on torch's current stream, without synchronising."""
-    import torch
     from . import engine
     x = monthly_year
     want = (plan.nm, 12, 5, plan.ny, plan.nx)
-    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()) or tuple(x.shape) != want:
-        raise engine.GrebError(-1, f"clim.add_year_dev: a contiguous float32 GPU tensor {list(want)} expected")
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        engine._check(engine.lib().greb_clim_add_year_dev(plan.h, int(dev), C.c_void_p(x.data_ptr()), int(k), C.c_void_p(stream)))
+    dev = _plan.gpu_tensor_check(x, tuple(x.shape) == want, "clim.add_year_dev", str(list(want)))
+    _plan.call_on_current_stream(dev, engine.lib().greb_clim_add_year_dev, plan.h, int(dev), _plan.ptr(x), int(k))
     plan._device = dev
 
 
@@ -125,11 +105,7 @@ def finish_dev(plan: Plan, n_years: int) -> Result:
     n = (12, 5, 12, 12, 5)
     out = [torch.empty((plan.nm, k, 5, plan.ny, plan.nx), dtype=torch.float32, device=f"cuda:{dev}") if on else None
            for k, on in zip(n, selected(plan.what))]
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        engine._check(engine.lib().greb_clim_finish_dev(plan.h, int(dev), int(n_years),
-                                                        *[None if t is None else C.c_void_p(t.data_ptr()) for t in out],
-                                                        C.c_void_p(stream)))
+    _plan.call_on_current_stream(dev, engine.lib().greb_clim_finish_dev, plan.h, int(dev), int(n_years), *map(_plan.ptr, out))
     return Result(*out)
 
 

@@ -376,7 +376,7 @@ template <bool EXACT> __device__ __forceinline__ float flog(float x) { return EX
 template <bool EXACT> __device__ __forceinline__ float fexp(float x) { return EXACT ? expf(x) : __expf(x); }
 template <bool EXACT> __device__ __forceinline__ float fsqrt(float x) { return EXACT ? sqrtf(x) : __builtin_amdgcn_sqrtf(x); }
 
-// experiment switches: mirror of GREB_X_* (include/greb_engine.h; equality asserted in greb_engine.cpp)
+// experiment switches: mirror of GREB_X_* (include/greb_engine.h; equality asserted in greb_members.cpp)
 constexpr unsigned kXNoIce = 1u << 0, kXNoHydro = 1u << 1, kXNoDeepOcean = 1u << 2, kXLwLinear = 1u << 3,
                    kXNoCirc = 1u << 4, kXNoQTransport = 1u << 5, kXQDiffOnly = 1u << 6, kXSstPlus1 = 1u << 7;
 

@@ -1,4 +1,4 @@
-// greb_kernels.h -- launch interface between the C-ABI host code (greb_engine.cpp) and the HIP
+// greb_kernels.h -- launch interface between the C-ABI host code (greb_host.h) and the HIP
 // kernels (greb_kernels.hip).  Internal; the public surface is include/greb_engine.h.
 #pragma once
 #include <hip/hip_runtime.h>

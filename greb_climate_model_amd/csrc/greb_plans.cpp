@@ -1,0 +1,619 @@
+// greb_plans.cpp -- the output plans (greb_diag, greb_clim, greb_ens): their _dev entry points and their scenario-run sinks.
+// A plan is host data only; what it needs on a device is made the first time it works there (PerDevice).
+#include "greb_host.h"
+
+#include <cmath>
+#include <cstdio>
+#include <new>
+
+#include "greb_diag.h"
+#include "greb_clim.h"
+#include "greb_ens.h"
+
+using namespace greb;
+using namespace greb::host;
+
+namespace {
+// A plan's device data: one T, which owns its arrays (DevBuf), per device the plan has worked on.
+template <typename T>
+class PerDevice {
+  std::map<int, T> devs_;
+ public:
+  // the entry of `device` (current); `make` fills a new one, and one it leaves half made frees itself
+  template <typename Make>
+  int get(int device, Make make, T** out) {
+    auto it = devs_.find(device);
+    if (it == devs_.end()) {
+      T n;
+      if (int rc = make(n)) return rc;
+      it = devs_.emplace(device, std::move(n)).first;
+    }
+    *out = &it->second;
+    return 0;
+  }
+  ~PerDevice() { // what is in flight on a device may still use the entry
+    int prev = 0;
+    const bool have_prev = !devs_.empty() && hipGetDevice(&prev) == hipSuccess;
+    for (auto it = devs_.begin(); it != devs_.end(); it = devs_.erase(it))
+      if (hipSetDevice(it->first) == hipSuccess) (void)hipDeviceSynchronize();
+    if (have_prev) (void)hipSetDevice(prev);
+  }
+};
+
+// ---- the checks every plan kind makes; `who` names the entry point
+int check_grid(const std::string& who, int nx, int ny) {
+  if (grid_ok(nx, ny)) return 0;
+  return fail(nullptr, GREB_E_INVALID, who + ": grid " + std::to_string(nx) + " x " + std::to_string(ny) +
+                                           " (nx % 4 == 0, nx >= 12, 5 <= ny <= " + std::to_string(kMaxNy) + ")");
+}
+int check_what(greb_engine* e, const std::string& who, unsigned what, unsigned all) {
+  if (what != 0 && !(what & ~all)) return 0;
+  return fail(e, GREB_E_INVALID, who + ": `what` = " + std::to_string(what) + " selects no product or an unknown one");
+}
+int check_aligned(const std::string& who, const void* p, const std::string& name) {
+  if (!(reinterpret_cast<uintptr_t>(p) & 15)) return 0;
+  return fail(nullptr, GREB_E_INVALID, who + ": " + name + " is not 16-byte aligned");
+}
+// the plan fits the engine: its grid and, where it has one (nm >= 0), its member count
+int check_engine(greb_engine* e, const std::string& who, int nx, int ny, int nm) {
+  if (nx != e->nx || ny != e->ny)
+    return fail(e, GREB_E_INVALID, who + ": the plan's grid " + std::to_string(nx) + " x " + std::to_string(ny) +
+                                       " differs from the engine's " + std::to_string(e->nx) + " x " + std::to_string(e->ny));
+  if (nm >= 0 && nm != e->nm)
+    return fail(e, GREB_E_INVALID, who + ": the plan is for " + std::to_string(nm) + " members, the engine has " + std::to_string(e->nm));
+  return 0;
+}
+
+// The five products of a climatology or an ensemble plan.  An output slot holds [row][record] of each selected product
+// in turn, 16-byte aligned (np % 4 == 0); the rows are the members (clim) or the groups (ens).
+struct Products {
+  const char* const* names; // the entry points' parameters (without "_dev")
+  const char* const* flags; // what selects each
+  size_t size[5] = {};      // floats of one row's record (0: not selected)
+  size_t rows = 0, at[5] = {}, out_slot = 0;
+  void layout(size_t n_rows) {
+    rows = n_rows; out_slot = 0;
+    for (int i = 0; i < 5; ++i) { at[i] = out_slot; out_slot += rows * size[i]; }
+  }
+  // every selected product has somewhere to go (suffix "_dev": on the device); what is not selected is ignored
+  int check(greb_engine* e, const std::string& who, float* p[5], const char* suffix, bool aligned) const {
+    for (int i = 0; i < 5; ++i) {
+      if (!size[i]) { p[i] = nullptr; continue; }
+      if (!p[i]) return fail(e, GREB_E_INVALID, who + ": " + flags[i] + " selected but `" + names[i] + suffix + "` is NULL");
+      if (aligned) if (int rc = check_aligned(who, p[i], std::string(names[i]) + suffix)) return rc;
+    }
+    return 0;
+  }
+  void pointers(float* slot, float* out[5]) const { for (int i = 0; i < 5; ++i) out[i] = size[i] ? slot + at[i] : nullptr; }
+};
+
+// What run_clim and run_ens share.  Unit u of n_units is made in output slot u & 1 of *buf (slot()), and every row's
+// record of it leaves from there to its place in the caller's [row][n_units][record] arrays.
+struct ProductSink {
+  greb_engine* e; const Products& pr; float** buf; size_t* cap; float* const* host; int n_units;
+  float* slot(int u) const { return *buf + (size_t)(u & 1) * pr.out_slot; }
+  void install(RunSink& s, std::function<int()> plan_on_device) const {
+    const ProductSink k = *this;
+    s.prepare = [k, plan_on_device]() -> int {
+      if (int rc = ensure(k.e, k.buf, k.cap, 2 * k.pr.out_slot)) return rc;
+      return plan_on_device();
+    };
+    s.deliver = [k](int u, int sl) -> int {
+      for (int i = 0; i < 5; ++i)
+        if (k.pr.size[i]) HIP_TRY(k.e, unit_to_host(k.e, k.host[i], k.n_units, u, k.slot(sl) + k.pr.at[i], k.pr.size[i], k.pr.rows));
+      return 0;
+    };
+  }
+};
+} // namespace
+
+// ---------------------------------------------------------------- reduced output (greb_diag.hip)
+// The combined weights w_r * cos(lat_j) of the globe and the caller's regions and the reciprocals of their sums, made
+// once in double.  Per device: their copies and the scratch array of the per-band partial sums.
+struct greb_diag {
+  int nx = 0, ny = 0, nr = 0;  // nr = 1 + n_regions
+  std::vector<double> w;       // [nr][ny][nx]
+  std::vector<double> inv_sum; // [nr]
+  struct Dev { DevBuf<double> w, inv_sum, partials; size_t partials_cap = 0; };
+  PerDevice<Dev> devs;
+};
+
+namespace {
+// the plan's tables on `device` (current), with room for the partial sums of `n_members` when regions are reduced
+int diag_on_device(greb_diag* d, int device, int n_members, bool regions, greb_diag::Dev** out) {
+  greb_diag::Dev* dv = nullptr;
+  auto make = [d](greb_diag::Dev& n) -> int {
+    HIP_TRY(nullptr, n.w.upload(d->w.data(), d->w.size()));
+    HIP_TRY(nullptr, n.inv_sum.upload(d->inv_sum.data(), d->inv_sum.size()));
+    return 0;
+  };
+  if (int rc = d->devs.get(device, make, &dv)) return rc;
+  const size_t need = regions ? diag_partials(d->nx, d->ny, n_members, d->nr) : 0;
+  if (dv->partials_cap < need) { // (a larger batch than before: an earlier reduction may still read the old array)
+    if (dv->partials) HIP_TRY(nullptr, hipDeviceSynchronize());
+    dv->partials_cap = 0;
+    HIP_TRY(nullptr, dv->partials.alloc(need));
+    dv->partials_cap = need;
+  }
+  *out = dv;
+  return 0;
+}
+
+DiagArgs diag_args(const greb_diag* d, const greb_diag::Dev* dv, const float* monthly, float* regions, size_t regions_stride,
+                   float* zonal, float* annual) {
+  DiagArgs a{};
+  a.monthly = monthly; a.nx = d->nx; a.ny = d->ny; a.nr = d->nr;
+  a.w = dv->w.get(); a.inv_sum = dv->inv_sum.get(); a.partials = dv->partials.get();
+  a.regions = regions; a.regions_stride = regions_stride; a.zonal = zonal; a.annual = annual;
+  return a;
+}
+} // namespace
+
+extern "C" {
+
+int greb_diag_create(int nx, int ny, const float* region_w, int n_regions, greb_diag** out) {
+  if (!out) return fail(nullptr, GREB_E_INVALID, "diag_create: `out` is NULL");
+  *out = nullptr;
+  if (int rc = check_grid("diag_create", nx, ny)) return rc;
+  if (n_regions < 0 || n_regions > kDiagMaxRegions)
+    return fail(nullptr, GREB_E_INVALID, "diag_create: n_regions = " + std::to_string(n_regions) + " (0 ... " +
+                                             std::to_string(kDiagMaxRegions) + "; the globe is region 0 on top of them)");
+  if (n_regions > 0 && !region_w) return fail(nullptr, GREB_E_INVALID, "diag_create: region_w is NULL with n_regions > 0");
+  const size_t np = (size_t)nx * ny;
+  for (int k = 0; k < n_regions; ++k)
+    for (size_t i = 0; i < np; ++i) {
+      const float v = region_w[(size_t)k * np + i];
+      if (!(v >= 0.f && v <= 1.f)) { // (a NaN fails both comparisons)
+        char buf[160];
+        std::snprintf(buf, sizeof(buf), "diag_create: region %d: weight %g at row %zu, column %zu is not in [0, 1]", k + 1,
+                      (double)v, i / (size_t)nx, i % (size_t)nx);
+        return fail(nullptr, GREB_E_INVALID, buf);
+      }
+    }
+  greb_diag* d = new (std::nothrow) greb_diag();
+  if (!d) return fail(nullptr, GREB_E_INVALID, "out of host memory");
+  d->nx = nx; d->ny = ny; d->nr = 1 + n_regions;
+  d->w.resize((size_t)d->nr * np);
+  d->inv_sum.resize((size_t)d->nr);
+  const double pi = 3.14159265358979323846; // the true pi: the area of a grid cell, not the model's constant
+  for (int r = 0; r < d->nr; ++r) {
+    double sum = 0.0;
+    for (int j = 0; j < ny; ++j) {
+      const double c = std::cos(((j + 0.5) * 180.0 / ny - 90.0) * pi / 180.0);
+      for (int i = 0; i < nx; ++i) {
+        const size_t q = (size_t)j * nx + i;
+        const double w = r == 0 ? c : (double)region_w[(size_t)(r - 1) * np + q] * c;
+        d->w[(size_t)r * np + q] = w;
+        sum += w;
+      }
+    }
+    if (!(sum > 0.0)) {
+      delete d;
+      return fail(nullptr, GREB_E_INVALID, "diag_create: region " + std::to_string(r) + " has zero weight everywhere");
+    }
+    d->inv_sum[(size_t)r] = 1.0 / sum;
+  }
+  *out = d;
+  return 0;
+}
+
+int greb_diag_destroy(greb_diag* d) {
+  delete d; // (PerDevice waits for each device before its tables go)
+  return 0;
+}
+
+int greb_diag_reduce_dev(greb_diag* d, int device, const float* monthly_year_dev, int n_members, float* regions_dev,
+                         float* zonal_dev, float* annual_dev, void* stream) {
+  if (!d) return fail(nullptr, GREB_E_INVALID, "diag_reduce_dev: no plan (greb_diag is NULL)");
+  if (!monthly_year_dev) return fail(nullptr, GREB_E_INVALID, "diag_reduce_dev: monthly_year_dev is NULL");
+  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "diag_reduce_dev: n_members = " + std::to_string(n_members));
+  if (!regions_dev && !zonal_dev && !annual_dev)
+    return fail(nullptr, GREB_E_INVALID, "diag_reduce_dev: regions_dev, zonal_dev and annual_dev are all NULL");
+  if (int rc = check_aligned("diag_reduce_dev", monthly_year_dev, "monthly_year_dev")) return rc;
+  if (int rc = check_aligned("diag_reduce_dev", annual_dev, "annual_dev")) return rc;
+  if (int rc = use_device("diag_reduce_dev: ", device)) return rc;
+  greb_diag::Dev* dv = nullptr;
+  if (int rc = diag_on_device(d, device, n_members, regions_dev != nullptr, &dv)) return rc;
+  const DiagArgs a = diag_args(d, dv, monthly_year_dev, regions_dev, (size_t)kDiagMonths * kDiagVars * d->nr, zonal_dev, annual_dev);
+  HIP_TRY(nullptr, launch_diag_year(a, n_members, (hipStream_t)stream));
+  return 0;
+}
+
+int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_diag* d, unsigned what, float* regions,
+                         float* zonal, float* annual, float* yearly) {
+  // argument errors first, before anything touches a device
+  if (!d) return fail(e, GREB_E_INVALID, "run_diag: no plan (greb_diag is NULL)");
+  if (int rc = check_what(e, "run_diag", what, GREB_D_REGIONS | GREB_D_ZONAL | GREB_D_ANNUAL)) return rc;
+  if ((what & GREB_D_REGIONS) && !regions) return fail(e, GREB_E_INVALID, "run_diag: GREB_D_REGIONS selected but `regions` is NULL");
+  if ((what & GREB_D_ZONAL) && !zonal) return fail(e, GREB_E_INVALID, "run_diag: GREB_D_ZONAL selected but `zonal` is NULL");
+  if ((what & GREB_D_ANNUAL) && !annual) return fail(e, GREB_E_INVALID, "run_diag: GREB_D_ANNUAL selected but `annual` is NULL");
+  if (!e || years < 1 || !co2_ppm) return fail(e, GREB_E_INVALID, "run_diag: bad argument (engine, years or co2_ppm)");
+  if (int rc = check_engine(e, "run_diag", d->nx, d->ny, -1)) return rc;
+  const size_t np = (size_t)e->np, nm = (size_t)e->nm;
+  const bool do_r = (what & GREB_D_REGIONS) != 0, do_z = (what & GREB_D_ZONAL) != 0, do_a = (what & GREB_D_ANNUAL) != 0;
+  const size_t reg_year = (size_t)12 * 5 * d->nr, zon_year = (size_t)12 * 5 * e->ny, ann_year = 5 * np; // floats per member-year
+  const size_t zon_slot = do_z ? nm * zon_year : 0, ann_slot = do_a ? nm * ann_year : 0, out_slot = zon_slot + ann_slot;
+  greb_diag::Dev* dv = nullptr;
+  // A unit is a year's zonal means and annual maps, made in output slot y & 1 of e->diag_out.  The region series -- the
+  // only thing on the device that grows with `years` besides the yearly scalars -- stays there for the whole call.
+  RunSink s;
+  s.prepare = [&]() -> int {
+    if (out_slot) if (int rc = ensure(e, &e->diag_out, &e->diag_out_cap, 2 * out_slot)) return rc;
+    if (do_r) if (int rc = ensure(e, &e->diag_reg, &e->diag_reg_cap, nm * years * reg_year)) return rc;
+    return diag_on_device(d, e->device, e->nm, do_r, &dv);
+  };
+  s.year = [&](const YearCalls& run, int y) -> int {
+    float* mon = staging_slot(e, y);
+    if (int rc = run.integrate(y, {mon, 1, 0})) return rc;
+    if (int rc = run.writing(y)) return rc; // (here, not before the year: only the reduction writes the slot)
+    float* out = out_slot ? e->diag_out + (size_t)(y & 1) * out_slot : nullptr;
+    const DiagArgs g = diag_args(d, dv, mon, do_r ? e->diag_reg + (size_t)y * reg_year : nullptr, (size_t)years * reg_year,
+                                 do_z ? out : nullptr, do_a ? out + zon_slot : nullptr);
+    HIP_TRY(e, launch_diag_year(g, e->nm, e->stream));
+    return run.complete(y);
+  };
+  s.deliver = [&](int y, int sl) -> int {
+    float* out = e->diag_out + (size_t)sl * out_slot;
+    if (do_z) HIP_TRY(e, unit_to_host(e, zonal, years, y, out, zon_year));
+    if (do_a) HIP_TRY(e, unit_to_host(e, annual, years, y, out + zon_slot, ann_year));
+    return 0;
+  };
+  s.finish = [&]() -> int {
+    if (do_r) HIP_TRY(e, hipMemcpy(regions, e->diag_reg, nm * years * reg_year * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+  };
+  return run_years(e, years, co2_ppm, yearly, s);
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- climatology output (greb_clim.hip)
+// Grid, member count, each member's control and the products.  Per device: the fp64 sums and the control map's copy.
+// `added` counts the years since the last finish: one period is summed at a time, on one device.
+struct greb_clim {
+  int nx = 0, ny = 0, nm = 0;
+  unsigned what = 0;
+  std::vector<int32_t> control; // [nm], or empty: no control map
+  int added = 0;                // years added since the last finish
+  int added_device = -1;        // ... on this device
+  struct Dev { DevBuf<double> S, T; DevBuf<int> control; };
+  PerDevice<Dev> devs;
+  size_t elems() const { return (size_t)nm * kClimMonths * kClimVars * nx * ny; }
+};
+
+namespace {
+int clim_on_device(greb_clim* c, int device, greb_clim::Dev** out) {
+  return c->devs.get(device, [c](greb_clim::Dev& n) -> int {
+    HIP_TRY(nullptr, n.S.alloc(c->elems()));
+    if (c->what & GREB_C_TREND) HIP_TRY(nullptr, n.T.alloc(c->elems()));
+    if (!c->control.empty()) HIP_TRY(nullptr, n.control.upload(c->control.data(), c->control.size()));
+    return 0;
+  }, out);
+}
+
+const char* const kClimOutNames[5] = {"mean", "seasons", "trend", "mean_resp", "seasons_resp"};
+const char* const kClimFlagNames[5] = {"GREB_C_MEAN", "GREB_C_SEASONS", "GREB_C_TREND", "GREB_C_RESPONSE with GREB_C_MEAN",
+                                       "GREB_C_RESPONSE with GREB_C_SEASONS"};
+// floats of one member's record of each product of one period: MEAN, SEASONS, TREND, the MEAN response, the SEASONS response
+Products clim_products(const greb_clim* c) {
+  const size_t np = (size_t)c->nx * c->ny, mon = (size_t)kClimMonths * kClimVars * np, sea = (size_t)kClimSeasons * kClimVars * np;
+  const bool resp = (c->what & GREB_C_RESPONSE) != 0;
+  Products pr{kClimOutNames, kClimFlagNames};
+  pr.size[0] = (c->what & GREB_C_MEAN) ? mon : 0;
+  pr.size[1] = (c->what & GREB_C_SEASONS) ? sea : 0;
+  pr.size[2] = (c->what & GREB_C_TREND) ? mon : 0;
+  pr.size[3] = resp && (c->what & GREB_C_MEAN) ? mon : 0;
+  pr.size[4] = resp && (c->what & GREB_C_SEASONS) ? sea : 0;
+  return pr;
+}
+
+ClimFinishArgs clim_finish_args(const greb_clim* c, const greb_clim::Dev* dv, int n_years, float* const out[5]) {
+  ClimFinishArgs a{};
+  a.S = dv->S.get(); a.T = dv->T.get(); a.control = dv->control.get();
+  a.np = (size_t)c->nx * c->ny; a.n_years = n_years;
+  a.mean = out[0]; a.seasons = out[1]; a.trend = out[2]; a.mean_resp = out[3]; a.seasons_resp = out[4];
+  return a;
+}
+} // namespace
+
+extern "C" {
+
+int greb_clim_create(int nx, int ny, int n_members, const int32_t* control, unsigned what, greb_clim** out) {
+  if (!out) return fail(nullptr, GREB_E_INVALID, "clim_create: `out` is NULL");
+  *out = nullptr;
+  if (int rc = check_grid("clim_create", nx, ny)) return rc;
+  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "clim_create: n_members = " + std::to_string(n_members));
+  if (int rc = check_what(nullptr, "clim_create", what, GREB_C_MEAN | GREB_C_SEASONS | GREB_C_TREND | GREB_C_RESPONSE)) return rc;
+  if ((what & GREB_C_RESPONSE) && !(what & (GREB_C_MEAN | GREB_C_SEASONS)))
+    return fail(nullptr, GREB_E_INVALID, "clim_create: GREB_C_RESPONSE needs GREB_C_MEAN or GREB_C_SEASONS (it is their difference to "
+                                         "the control)");
+  if ((what & GREB_C_RESPONSE) && !control)
+    return fail(nullptr, GREB_E_INVALID, "clim_create: GREB_C_RESPONSE selected but `control` is NULL");
+  if (control)
+    for (int m = 0; m < n_members; ++m)
+      if (control[m] < -1 || control[m] >= n_members)
+        return fail(nullptr, GREB_E_INVALID, "clim_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
+                                                 " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
+  greb_clim* c = new (std::nothrow) greb_clim();
+  if (!c) return fail(nullptr, GREB_E_INVALID, "out of host memory");
+  c->nx = nx; c->ny = ny; c->nm = n_members; c->what = what;
+  if (control) c->control.assign(control, control + n_members);
+  *out = c;
+  return 0;
+}
+
+int greb_clim_destroy(greb_clim* c) {
+  delete c; // (PerDevice waits for each device before its sums go)
+  return 0;
+}
+
+int greb_clim_add_year_dev(greb_clim* c, int device, const float* monthly_year_dev, int k, void* stream) {
+  if (!c) return fail(nullptr, GREB_E_INVALID, "clim_add_year_dev: no plan (greb_clim is NULL)");
+  if (!monthly_year_dev) return fail(nullptr, GREB_E_INVALID, "clim_add_year_dev: monthly_year_dev is NULL");
+  if (int rc = check_aligned("clim_add_year_dev", monthly_year_dev, "monthly_year_dev")) return rc;
+  if (k != c->added)
+    return fail(nullptr, GREB_E_INVALID, "clim_add_year_dev: k = " + std::to_string(k) + ", but " + std::to_string(c->added) +
+                                             " years were added since the last finish (years go in ascending order, k = 0 first)");
+  if (k > 0 && device != c->added_device)
+    return fail(nullptr, GREB_E_INVALID, "clim_add_year_dev: device " + std::to_string(device) + ", but this period's sums are on device " +
+                                             std::to_string(c->added_device));
+  if (int rc = use_device("clim_add_year_dev: ", device)) return rc;
+  greb_clim::Dev* dv = nullptr;
+  if (int rc = clim_on_device(c, device, &dv)) return rc;
+  HIP_TRY(nullptr, launch_clim_add_year(monthly_year_dev, dv->S.get(), dv->T.get(), c->elems(), k, (hipStream_t)stream));
+  c->added = k + 1; c->added_device = device;
+  return 0;
+}
+
+int greb_clim_finish_dev(greb_clim* c, int device, int n_years, float* mean_dev, float* seasons_dev, float* trend_dev,
+                         float* mean_resp_dev, float* seasons_resp_dev, void* stream) {
+  if (!c) return fail(nullptr, GREB_E_INVALID, "clim_finish_dev: no plan (greb_clim is NULL)");
+  const Products pr = clim_products(c);
+  float* out[5] = {mean_dev, seasons_dev, trend_dev, mean_resp_dev, seasons_resp_dev};
+  if (int rc = pr.check(nullptr, "clim_finish_dev", out, "_dev", true)) return rc;
+  if (n_years != c->added || n_years < 1)
+    return fail(nullptr, GREB_E_INVALID, "clim_finish_dev: n_years = " + std::to_string(n_years) + ", but " + std::to_string(c->added) +
+                                             " years were added since the last finish");
+  if (device != c->added_device)
+    return fail(nullptr, GREB_E_INVALID, "clim_finish_dev: device " + std::to_string(device) + ", but this period's sums are on device " +
+                                             std::to_string(c->added_device));
+  if (int rc = use_device("clim_finish_dev: ", device)) return rc;
+  greb_clim::Dev* dv = nullptr;
+  if (int rc = clim_on_device(c, device, &dv)) return rc;
+  HIP_TRY(nullptr, launch_clim_finish(clim_finish_args(c, dv, n_years, out), c->nm, (hipStream_t)stream));
+  c->added = 0; c->added_device = -1;
+  return 0;
+}
+
+int greb_engine_run_clim(greb_engine* e, int years, const float* co2_ppm, greb_clim* c, int n_periods, const int32_t* first_year,
+                         const int32_t* n_years, float* mean, float* seasons, float* trend, float* mean_resp, float* seasons_resp,
+                         float* yearly) {
+  // argument errors first, before anything touches a device: the plan, the periods, the outputs, then the engine
+  if (!c) return fail(e, GREB_E_INVALID, "run_clim: no plan (greb_clim is NULL)");
+  if (years < 1) return fail(e, GREB_E_INVALID, "run_clim: years = " + std::to_string(years));
+  if (n_periods < 1 || !first_year || !n_years)
+    return fail(e, GREB_E_INVALID, "run_clim: n_periods = " + std::to_string(n_periods) + " with first_year / n_years " +
+                                       (first_year && n_years ? "given" : "NULL") + " (at least one period is needed)");
+  for (int p = 0; p < n_periods; ++p) {
+    const std::string who = "run_clim: period " + std::to_string(p) + " (first_year " + std::to_string(first_year[p]) + ", n_years " +
+                            std::to_string(n_years[p]) + ")";
+    if (n_years[p] < 1) return fail(e, GREB_E_INVALID, who + " has no years");
+    if (first_year[p] < 0 || (long long)first_year[p] + n_years[p] > years)
+      return fail(e, GREB_E_INVALID, who + " is not inside the run's years 0 ... " + std::to_string(years - 1));
+    if (p > 0 && first_year[p] < first_year[p - 1])
+      return fail(e, GREB_E_INVALID, who + " starts before period " + std::to_string(p - 1) + ": periods must be ascending");
+    if (p > 0 && first_year[p] < first_year[p - 1] + n_years[p - 1])
+      return fail(e, GREB_E_INVALID, who + " overlaps period " + std::to_string(p - 1) + ", which ends with year " +
+                                         std::to_string(first_year[p - 1] + n_years[p - 1] - 1));
+  }
+  Products pr = clim_products(c);
+  float* host[5] = {mean, seasons, trend, mean_resp, seasons_resp};
+  if (int rc = pr.check(e, "run_clim", host, "", false)) return rc;
+  if (c->added != 0)
+    return fail(e, GREB_E_INVALID, "run_clim: the plan holds " + std::to_string(c->added) + " years of an unfinished period");
+  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, "run_clim: bad argument (engine or co2_ppm)");
+  if (int rc = check_engine(e, "run_clim", c->nx, c->ny, c->nm)) return rc;
+  pr.layout((size_t)e->nm);
+  greb_clim::Dev* dv = nullptr;
+  int p = 0; // the period the current year is in or before
+  // A unit is a period's products, made in output slot p & 1 of e->clim_out.  Nothing on the device grows with `years`
+  // or `n_periods` (besides the yearly scalars).
+  const ProductSink k{e, pr, &e->clim_out, &e->clim_out_cap, host, n_periods};
+  RunSink s;
+  k.install(s, [&]() -> int { return clim_on_device(c, e->device, &dv); });
+  s.year = [&](const YearCalls& run, int y) -> int {
+    float* mon = staging_slot(e, y);
+    if (int rc = run.integrate(y, {mon, 1, 0})) return rc;
+    while (p < n_periods && y >= first_year[p] + n_years[p]) ++p;
+    if (p >= n_periods || y < first_year[p]) return 0; // (a year outside every period is integrated, not summed)
+    const int yk = y - first_year[p];
+    HIP_TRY(e, launch_clim_add_year(mon, dv->S.get(), dv->T.get(), c->elems(), yk, e->stream));
+    if (yk < n_years[p] - 1) return 0;
+    if (int rc = run.writing(p)) return rc; // (here, not before the year: only the finish pass writes the slot)
+    float* out[5];
+    pr.pointers(k.slot(p), out);
+    HIP_TRY(e, launch_clim_finish(clim_finish_args(c, dv, n_years[p], out), e->nm, e->stream));
+    return run.complete(p);
+  };
+  return run_years(e, years, co2_ppm, yearly, s);
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- ensemble output (greb_ens.hip)
+// Grid, member count, the products, the probabilities and the member lists -- group g is member[offs[g] ... offs[g + 1])
+// in ascending member index, control[k] the control of member[k].  Per device: the lists' copy (one allocation: offs,
+// member, control).
+struct greb_ens {
+  int nx = 0, ny = 0, nm = 0, ng = 0;
+  unsigned what = 0;
+  EnsProbs probs{};
+  bool has_control = false;
+  std::vector<int> offs, member, control;
+  struct Dev { DevBuf<int> lists; };
+  PerDevice<Dev> devs;
+};
+
+namespace {
+int ens_on_device(greb_ens* s, int device, EnsLists* out) {
+  const size_t listed = s->member.size(), n_offs = s->offs.size();
+  greb_ens::Dev* dv = nullptr;
+  auto make = [s](greb_ens::Dev& n) -> int {
+    std::vector<int> all(s->offs);
+    all.insert(all.end(), s->member.begin(), s->member.end());
+    all.insert(all.end(), s->control.begin(), s->control.end());
+    HIP_TRY(nullptr, n.lists.upload(all.data(), all.size()));
+    return 0;
+  };
+  if (int rc = s->devs.get(device, make, &dv)) return rc;
+  int* const base = dv->lists.get();
+  out->offs = base; out->member = base + n_offs; out->control = s->has_control ? base + n_offs + listed : nullptr;
+  return 0;
+}
+
+// the five products: MEAN, VAR, the two of RANGE, QUANTILES
+const char* const kEnsOutNames[5] = {"mean", "var", "min", "max", "quant"};
+const char* const kEnsFlagNames[5] = {"GREB_S_MEAN", "GREB_S_VAR", "GREB_S_RANGE", "GREB_S_RANGE", "GREB_S_QUANTILES"};
+// floats of one group's record of each product, for rows of n elements
+Products ens_products(const greb_ens* s, size_t n) {
+  Products pr{kEnsOutNames, kEnsFlagNames};
+  pr.size[0] = (s->what & GREB_S_MEAN) ? n : 0;
+  pr.size[1] = (s->what & GREB_S_VAR) ? n : 0;
+  pr.size[2] = pr.size[3] = (s->what & GREB_S_RANGE) ? n : 0;
+  pr.size[4] = (s->what & GREB_S_QUANTILES) ? (size_t)s->probs.n * n : 0;
+  return pr;
+}
+
+// the moments launch and one quantile launch per group, of x[nm][n] into out[5] (null where not selected)
+int ens_launch(greb_engine* e, const greb_ens* s, const EnsLists& l, const float* x, size_t n, float* const out[5],
+               hipStream_t stream) {
+  if (out[0] || out[1] || out[2]) {
+    EnsMomentArgs a{x, n, l, out[0], out[1], out[2], out[3]};
+    HIP_TRY(e, launch_ens_moments(a, s->ng, stream));
+  }
+  for (int g = 0; out[4] && g < s->ng; ++g) {
+    const int k0 = s->offs[(size_t)g];
+    HIP_TRY(e, launch_ens_quantiles(x, n, l.member + k0, l.control ? l.control + k0 : nullptr, s->offs[(size_t)g + 1] - k0, s->probs,
+                                    out[4] + (size_t)g * s->probs.n * n, stream));
+  }
+  return 0;
+}
+} // namespace
+
+extern "C" {
+
+int greb_ens_create(int nx, int ny, int n_members, const int32_t* group, int n_groups, const int32_t* control,
+                    const float* probs, int n_probs, unsigned what, greb_ens** out) {
+  if (!out) return fail(nullptr, GREB_E_INVALID, "ens_create: `out` is NULL");
+  *out = nullptr;
+  if (int rc = check_grid("ens_create", nx, ny)) return rc;
+  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "ens_create: n_members = " + std::to_string(n_members));
+  if (n_groups < 1 || n_groups > kEnsMaxGroups)
+    return fail(nullptr, GREB_E_INVALID, "ens_create: n_groups = " + std::to_string(n_groups) + " (1 ... " +
+                                             std::to_string(kEnsMaxGroups) + ")");
+  if (!group) return fail(nullptr, GREB_E_INVALID, "ens_create: `group` is NULL");
+  if (int rc = check_what(nullptr, "ens_create", what, GREB_S_MEAN | GREB_S_VAR | GREB_S_RANGE | GREB_S_QUANTILES)) return rc;
+  std::vector<int> count((size_t)n_groups, 0);
+  for (int m = 0; m < n_members; ++m) {
+    if (group[m] < -1 || group[m] >= n_groups)
+      return fail(nullptr, GREB_E_INVALID, "ens_create: member " + std::to_string(m) + ": group = " + std::to_string(group[m]) +
+                                               " (-1 = none, or 0 ... " + std::to_string(n_groups - 1) + ")");
+    if (control && (control[m] < -1 || control[m] >= n_members))
+      return fail(nullptr, GREB_E_INVALID, "ens_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
+                                               " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
+    if (group[m] < 0) continue;
+    if (control && control[m] < 0)
+      return fail(nullptr, GREB_E_INVALID, "ens_create: member " + std::to_string(m) + " is in group " + std::to_string(group[m]) +
+                                               " but has no control (control = -1) while a control map is given");
+    ++count[(size_t)group[m]];
+  }
+  for (int g = 0; g < n_groups; ++g)
+    if (count[(size_t)g] == 0) return fail(nullptr, GREB_E_INVALID, "ens_create: group " + std::to_string(g) + " is empty");
+  EnsProbs pr{};
+  if (what & GREB_S_QUANTILES) {
+    if (n_probs < 1 || n_probs > kEnsMaxProbs || !probs)
+      return fail(nullptr, GREB_E_INVALID, "ens_create: GREB_S_QUANTILES with n_probs = " + std::to_string(n_probs) +
+                                               (probs ? "" : " and `probs` NULL") + " (1 ... " + std::to_string(kEnsMaxProbs) + ")");
+    pr.n = n_probs;
+    for (int i = 0; i < n_probs; ++i) {
+      if (!(probs[i] >= 0.f && probs[i] <= 1.f)) { // (a NaN fails both comparisons)
+        char buf[128];
+        std::snprintf(buf, sizeof(buf), "ens_create: probability %d = %g is not in [0, 1]", i, (double)probs[i]);
+        return fail(nullptr, GREB_E_INVALID, buf);
+      }
+      pr.p[i] = probs[i];
+    }
+    for (int g = 0; g < n_groups; ++g)
+      if (count[(size_t)g] > kEnsMaxSorted)
+        return fail(nullptr, GREB_E_UNSUPPORTED, "ens_create: GREB_S_QUANTILES with group " + std::to_string(g) + " of " +
+                                                     std::to_string(count[(size_t)g]) + " members (at most " +
+                                                     std::to_string(kEnsMaxSorted) + " are sorted in one compute unit's LDS)");
+  }
+  greb_ens* s = new (std::nothrow) greb_ens();
+  if (!s) return fail(nullptr, GREB_E_INVALID, "out of host memory");
+  s->nx = nx; s->ny = ny; s->nm = n_members; s->ng = n_groups; s->what = what; s->probs = pr; s->has_control = control != nullptr;
+  s->offs.assign((size_t)n_groups + 1, 0);
+  for (int g = 0; g < n_groups; ++g) s->offs[(size_t)g + 1] = s->offs[(size_t)g] + count[(size_t)g];
+  s->member.resize((size_t)s->offs[(size_t)n_groups]);
+  if (control) s->control.resize(s->member.size());
+  std::vector<int> at(s->offs.begin(), s->offs.end() - 1);
+  for (int m = 0; m < n_members; ++m) { // ascending member index inside every group
+    if (group[m] < 0) continue;
+    const size_t k = (size_t)at[(size_t)group[m]]++;
+    s->member[k] = m;
+    if (control) s->control[k] = control[m];
+  }
+  *out = s;
+  return 0;
+}
+
+int greb_ens_destroy(greb_ens* s) {
+  delete s; // (PerDevice waits for each device before its lists go)
+  return 0;
+}
+
+int greb_ens_reduce_dev(greb_ens* s, int device, const float* x_dev, size_t n, float* mean_dev, float* var_dev, float* min_dev,
+                        float* max_dev, float* quant_dev, void* stream) {
+  if (!s) return fail(nullptr, GREB_E_INVALID, "ens_reduce_dev: no plan (greb_ens is NULL)");
+  if (!x_dev) return fail(nullptr, GREB_E_INVALID, "ens_reduce_dev: x_dev is NULL");
+  if (int rc = check_aligned("ens_reduce_dev", x_dev, "x_dev")) return rc;
+  if (n < 1) return fail(nullptr, GREB_E_INVALID, "ens_reduce_dev: n = 0");
+  float* out[5] = {mean_dev, var_dev, min_dev, max_dev, quant_dev};
+  if (int rc = ens_products(s, n).check(nullptr, "ens_reduce_dev", out, "_dev", false)) return rc;
+  if (int rc = use_device("ens_reduce_dev: ", device)) return rc;
+  EnsLists l{};
+  if (int rc = ens_on_device(s, device, &l)) return rc;
+  return ens_launch(nullptr, s, l, x_dev, n, out, (hipStream_t)stream);
+}
+
+int greb_engine_run_ens(greb_engine* e, int years, const float* co2_ppm, greb_ens* s, float* mean, float* var, float* min,
+                        float* max, float* quant, float* yearly) {
+  // argument errors first, before anything touches a device: the plan, the outputs, then the engine
+  if (!s) return fail(e, GREB_E_INVALID, "run_ens: no plan (greb_ens is NULL)");
+  if (years < 1) return fail(e, GREB_E_INVALID, "run_ens: years = " + std::to_string(years));
+  const size_t n = (size_t)12 * 5 * s->nx * s->ny; // one member's model year
+  Products pr = ens_products(s, n);
+  float* host[5] = {mean, var, min, max, quant};
+  if (int rc = pr.check(e, "run_ens", host, "", false)) return rc;
+  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, "run_ens: bad argument (engine or co2_ppm)");
+  if (int rc = check_engine(e, "run_ens", s->nx, s->ny, s->nm)) return rc;
+  pr.layout((size_t)s->ng);
+  EnsLists l{};
+  // A unit is a year's statistics, made in output slot y & 1 of e->ens_out.  Nothing on the device grows with `years`
+  // (besides the yearly scalars).
+  const ProductSink k{e, pr, &e->ens_out, &e->ens_out_cap, host, years};
+  RunSink sink;
+  k.install(sink, [&]() -> int { return ens_on_device(s, e->device, &l); });
+  sink.year = [&](const YearCalls& run, int y) -> int {
+    float* mon = staging_slot(e, y);
+    if (int rc = run.integrate(y, {mon, 1, 0})) return rc;
+    if (int rc = run.writing(y)) return rc; // (here, not before the year: only the reduction writes the slot)
+    float* out[5];
+    pr.pointers(k.slot(y), out);
+    if (int rc = ens_launch(e, s, l, mon, n, out, e->stream)) return rc;
+    return run.complete(y);
+  };
+  return run_years(e, years, co2_ppm, yearly, sink);
+}
+
+} // extern "C"

@@ -14,12 +14,11 @@ kernel: it is what the tests hold the device against.
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import abi
+from . import _plan, abi
 
 ALL = abi.D_REGIONS | abi.D_ZONAL | abi.D_ANNUAL
 GLOBE = "globe"  # region 0 of every plan
@@ -45,9 +44,10 @@ class Result:
         return self.regions[..., self.names.index(name)]
 
 
-class Plan:
+class Plan(_plan.Handle):
     """greb_diag handle: the grid and the regions (name -> weights [ny][nx] in [0, 1]; the globe is always region 0).
     Host data only; creating one needs no GPU, and every argument error is a GrebError(-1) naming the offender."""
+    _destroy = "greb_diag_destroy"
 
     def __init__(self, nx: int, ny: int, regions: dict | None = None):
         from . import engine
@@ -60,27 +60,12 @@ class Plan:
                 raise engine.GrebError(-1, f"diag.Plan: region {k!r} has shape {np.shape(v)}, the grid is {(self.ny, self.nx)}")
         self.weights = (np.ascontiguousarray(np.stack([np.asarray(v, np.float32) for v in regions.values()]))
                         if regions else np.zeros((0, self.ny, self.nx), np.float32))
-        self.h = C.c_void_p()
-        rc = engine.lib().greb_diag_create(self.nx, self.ny, abi.fptr(self.weights) if regions else None, len(regions),
-                                           C.byref(self.h))
-        if rc != 0:
-            self.h = None
-            msg = engine.lib().greb_engine_last_error(None).decode()
-            for i, k in enumerate(regions):  # the library counts regions, the caller named them
-                msg = msg.replace(f"region {i + 1}:", f"region {i + 1} ({k!r}):").replace(f"region {i + 1} has", f"region {i + 1} ({k!r}) has")
-            raise engine.GrebError(rc, msg)
+        self._create("greb_diag_create", self.nx, self.ny, abi.fptr(self.weights) if regions else None, len(regions))
 
-    def close(self):
-        if getattr(self, "h", None):
-            from . import engine
-            engine.lib().greb_diag_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _reword(self, msg: str) -> str:
+        for i, k in enumerate(self.names[1:]):  # the library counts regions, the caller named them
+            msg = msg.replace(f"region {i + 1}:", f"region {i + 1} ({k!r}):").replace(f"region {i + 1} has", f"region {i + 1} ({k!r}) has")
+        return msg
 
 
 def reduce_dev(plan: Plan, monthly_year, what: int = ALL) -> Result:
@@ -89,18 +74,14 @@ def reduce_dev(plan: Plan, monthly_year, what: int = ALL) -> Result:
     import torch
     from . import engine
     x = monthly_year
-    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()) or tuple(x.shape[1:]) != (12, 5, plan.ny, plan.nx):
-        raise engine.GrebError(-1, f"diag.reduce_dev: a contiguous float32 GPU tensor [n][12][5][{plan.ny}][{plan.nx}] expected")
+    dev = _plan.gpu_tensor_check(x, tuple(x.shape[1:]) == (12, 5, plan.ny, plan.nx), "diag.reduce_dev", f"[n][12][5][{plan.ny}][{plan.nx}]")
     n = x.shape[0]
     mk = lambda *s: torch.empty((n,) + s, dtype=torch.float32, device=x.device)
     regions = mk(12, 5, plan.nr) if what & abi.D_REGIONS else None
     zonal = mk(12, 5, plan.ny) if what & abi.D_ZONAL else None
     annual = mk(5, plan.ny, plan.nx) if what & abi.D_ANNUAL else None
-    ptr = [C.c_void_p(t.data_ptr()) if t is not None else None for t in (regions, zonal, annual)]
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        engine._check(engine.lib().greb_diag_reduce_dev(plan.h, int(dev), C.c_void_p(x.data_ptr()), int(n), *ptr, C.c_void_p(stream)))
+    _plan.call_on_current_stream(dev, engine.lib().greb_diag_reduce_dev, plan.h, int(dev), _plan.ptr(x), int(n), _plan.ptr(regions),
+                                 _plan.ptr(zonal), _plan.ptr(annual))
     return Result(regions, zonal, annual, None, plan.names)
 
 

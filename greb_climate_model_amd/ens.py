@@ -25,7 +25,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import abi
+from . import _plan, abi
 
 MOMENTS = abi.S_MEAN | abi.S_VAR | abi.S_RANGE
 ALL = MOMENTS | abi.S_QUANTILES
@@ -65,12 +65,13 @@ class Result:
         return np.sqrt(self.var) if isinstance(self.var, np.ndarray) else self.var.sqrt()
 
 
-class Plan:
+class Plan(_plan.Handle):
     """greb_ens handle: grid, member count, each member's group (-1: in none; groups are 0 ... max(group)), each member's
     control member (None: no control map -- the statistics are of the records themselves), the probabilities of the
     quantiles and the products (abi.S_* bits; default: MEAN, VAR and RANGE, and QUANTILES when probs are given).  Host data
     only; creating one needs no GPU, and every argument error is a GrebError(-1) naming the offender (-4: a group of more
     than 4096 members with quantiles)."""
+    _destroy = "greb_ens_destroy"
 
     def __init__(self, nx: int, ny: int, n_members: int, group, control=None, probs=(), what: int | None = None):
         from . import engine
@@ -91,26 +92,9 @@ class Plan:
         self.group = members("group", group)
         self.control = None if control is None else members("control", control)
         self.ng = int(self.group.max()) + 1 if self.group.size else 0
-        self.h = C.c_void_p()
         ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
-        rc = engine.lib().greb_ens_create(self.nx, self.ny, self.nm, ip(self.group), self.ng, ip(self.control),
-                                          abi.fptr(self.probs) if len(self.probs) else None, len(self.probs),
-                                          self.what & 0xFFFFFFFF, C.byref(self.h))
-        if rc != 0:
-            self.h = None
-            raise engine.GrebError(rc, engine.lib().greb_engine_last_error(None).decode())
-
-    def close(self):
-        if getattr(self, "h", None):
-            from . import engine
-            engine.lib().greb_ens_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create("greb_ens_create", self.nx, self.ny, self.nm, ip(self.group), self.ng, ip(self.control),
+                     abi.fptr(self.probs) if len(self.probs) else None, len(self.probs), self.what & 0xFFFFFFFF)
 
 
 def reduce_dev(plan: Plan, x) -> Result:
@@ -119,18 +103,12 @@ def reduce_dev(plan: Plan, x) -> Result:
     (greb_ens_reduce_dev)."""
     import torch
     from . import engine
-    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()) or x.dim() < 1 or x.shape[0] != plan.nm or x.numel() == 0:
-        raise engine.GrebError(-1, f"ens.reduce_dev: a contiguous float32 GPU tensor [{plan.nm}][...] expected")
+    dev = _plan.gpu_tensor_check(x, x.dim() >= 1 and x.shape[0] == plan.nm and x.numel() > 0, "ens.reduce_dev", f"[{plan.nm}][...]")
     rec = tuple(x.shape[1:])
     n = x.numel() // plan.nm
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
     out = [torch.empty((plan.ng,) + ((len(plan.probs),) if i == 4 else ()) + rec, dtype=torch.float32, device=f"cuda:{dev}")
            if on else None for i, on in enumerate(selected(plan.what))]
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        engine._check(engine.lib().greb_ens_reduce_dev(plan.h, int(dev), C.c_void_p(x.data_ptr()), n,
-                                                       *[None if t is None else C.c_void_p(t.data_ptr()) for t in out],
-                                                       C.c_void_p(stream)))
+    _plan.call_on_current_stream(dev, engine.lib().greb_ens_reduce_dev, plan.h, int(dev), _plan.ptr(x), n, *map(_plan.ptr, out))
     return Result(*out)
 
 

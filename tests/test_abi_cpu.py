@@ -88,3 +88,23 @@ def test_release_library_never_reads_the_environment(lib):
     for knob in (b"GREB_DEBUG_SKIP", b"GREB_DEBUG_NSUB", b"GREB_BAND_LIMIT_KB", b"GREB_NO_STREAM", b"GREB_STREAM_WGS",
                  b"GREB_PAIR_ROWS"):
         assert knob not in raw, knob
+
+
+@pytest.mark.skipif(not os.path.exists(build.hipcc()), reason="no hipcc: a variant library cannot be built")
+def test_variant_library_is_whole(lib):
+    """tools/build_member_variant.sh links every source of the release library (build.SOURCES): the variant exports what
+    the release library exports, and no kernel launcher (greb::launch_*) is left undefined."""
+    import subprocess
+
+    def symbols(path, which):
+        out = subprocess.run(["nm", "-D", which, path], capture_output=True, text=True, check=True).stdout
+        return {line.split()[-1] for line in out.splitlines() if line.strip()}
+
+    run = subprocess.run([os.path.join(ROOT, "tools", "build_member_variant.sh"), "probe", "-DGREB_VARIANT_PROBE=1"],
+                         capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr[-2000:]
+    variant = os.path.join(ROOT, "variants", "libgreb_member_probe.so")
+    assert run.stdout.strip().splitlines()[-1] == variant and os.path.exists(variant)
+    greb = lambda names: {n for n in names if n.startswith("greb_")}
+    assert greb(symbols(variant, "--defined-only")) == greb(symbols(build.LIB, "--defined-only")) >= set(engine.EXPORTS)
+    assert not [n for n in symbols(variant, "--undefined-only") if "launch_" in n]
