@@ -19,6 +19,11 @@ D_MAX_REGIONS = 15
 C_MEAN, C_SEASONS, C_TREND, C_RESPONSE = 1, 2, 4, 8  # climatology products, GREB_C_* of include/greb_engine.h
 S_MEAN, S_VAR, S_RANGE, S_QUANTILES = 1, 2, 4, 8  # ensemble-output products, GREB_S_* of include/greb_engine.h
 ENS_MAX_GROUPS, ENS_MAX_PROBS, ENS_MAX_SORTED = 64, 16, 4096  # GREB_ENS_MAX_*
+L_COEF, L_RSS = 1, 2  # linear-model products, GREB_L_* of include/greb_engine.h
+LIN_MAX_TERMS = 64    # GREB_LIN_MAX_TERMS
+# the names of the switches, GREB_X_* of include/greb_engine.h, bit 0 first
+X_NAMES = ("GREB_X_NO_ICE", "GREB_X_NO_HYDRO", "GREB_X_NO_DEEP_OCEAN", "GREB_X_LW_LINEAR_VAPOR", "GREB_X_NO_CIRCULATION",
+           "GREB_X_NO_VAPOR_TRANSPORT", "GREB_X_VAPOR_DIFFUSION_ONLY", "GREB_X_SST_PLUS1")
 # budget output, GREB_NBUDGET / GREB_B_* of include/greb_engine.h: the flux terms of the update in its order, sign and unit
 BUDGET_NAMES = ("sw", "LW_surf", "LWair_down", "LW_abs", "Q_sens", "Q_lat", "Q_lat_air", "dq_eva", "dq_rain", "dT_ocean",
                 "dTo", "dTa_crcl", "dq_crcl")
@@ -130,6 +135,17 @@ def ens_prototypes(lib) -> None:
     lib.greb_ens_reduce_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
     lib.greb_engine_run_ens.argtypes = [vp, C.c_int, c_float_p, vp] + [c_float_p] * 6
     for f in (lib.greb_ens_create, lib.greb_ens_destroy, lib.greb_ens_reduce_dev, lib.greb_engine_run_ens):
+        f.restype = C.c_int
+
+
+def lin_prototypes(lib) -> None:
+    """The argument types of greb_lin_* and greb_engine_run_lin."""
+    i32p, f64p, vp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_void_p
+    lib.greb_lin_create.argtypes = [C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, i32p, f64p, C.c_uint, C.POINTER(vp)]
+    lib.greb_lin_destroy.argtypes = [vp]
+    lib.greb_lin_reduce_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, vp, vp]
+    lib.greb_engine_run_lin.argtypes = [vp, C.c_int, c_float_p, vp, c_float_p, c_float_p, c_float_p]
+    for f in (lib.greb_lin_create, lib.greb_lin_destroy, lib.greb_lin_reduce_dev, lib.greb_engine_run_lin):
         f.restype = C.c_int
 
 

@@ -71,6 +71,7 @@ struct greb_engine {
   float* diag_reg = nullptr; size_t diag_reg_cap = 0; // run_diag: the region series of the whole call
   float* clim_out = nullptr; size_t clim_out_cap = 0; // run_clim: the products of two periods (one per output slot)
   float* ens_out = nullptr; size_t ens_out_cap = 0;   // run_ens: the group statistics of two years (one per output slot)
+  float* lin_out = nullptr; size_t lin_out_cap = 0;   // run_lin: the coefficients and the residual map of two years (likewise)
   // host copies needed later
   std::vector<greb::RowTables> h_tabs;
   std::vector<int> h_tab_index;

@@ -1,4 +1,4 @@
-// greb_plans.cpp -- the output plans (greb_diag, greb_clim, greb_ens): their _dev entry points and their scenario-run sinks.
+// greb_plans.cpp -- the output plans (greb_diag, greb_clim, greb_ens, greb_lin): their _dev entry points and their scenario-run sinks.
 // A plan is host data only; what it needs on a device is made the first time it works there (PerDevice).
 #include "greb_host.h"
 
@@ -9,6 +9,7 @@
 #include "greb_diag.h"
 #include "greb_clim.h"
 #include "greb_ens.h"
+#include "greb_lin.h"
 
 using namespace greb;
 using namespace greb::host;
@@ -612,6 +613,174 @@ int greb_engine_run_ens(greb_engine* e, int years, const float* co2_ppm, greb_en
     pr.pointers(k.slot(y), out);
     if (int rc = ens_launch(e, s, l, mon, n, out, e->stream)) return rc;
     return run.complete(y);
+  };
+  return run_years(e, years, co2_ppm, yearly, sink);
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- linear-model output (greb_lin.hip)
+// Grid, member count, the products and the tables of the USED members in ascending member index: member[k], control[k],
+// and per used member a row of `stride` = 16 * ceil(K / 16) doubles of weights (and of the design), zero behind term
+// K - 1.  Per device: the tables' copies (one allocation of ints, one of doubles).
+struct greb_lin {
+  int nx = 0, ny = 0, nm = 0, nk = 0, stride = 0;
+  unsigned what = 0;
+  bool has_control = false;
+  std::vector<int> member, control;   // [n_used]
+  std::vector<double> weight, design; // [n_used][stride]; design empty without one
+  struct Dev { DevBuf<int> lists; DevBuf<double> tables; };
+  PerDevice<Dev> devs;
+};
+
+namespace {
+int lin_on_device(greb_lin* l, int device, LinTables* out) {
+  greb_lin::Dev* dv = nullptr;
+  auto make = [l](greb_lin::Dev& n) -> int {
+    std::vector<int> lists(l->member);
+    lists.insert(lists.end(), l->control.begin(), l->control.end());
+    std::vector<double> tables(l->weight);
+    tables.insert(tables.end(), l->design.begin(), l->design.end());
+    HIP_TRY(nullptr, n.lists.upload(lists.data(), lists.size()));
+    HIP_TRY(nullptr, n.tables.upload(tables.data(), tables.size()));
+    return 0;
+  };
+  if (int rc = l->devs.get(device, make, &dv)) return rc;
+  const size_t used = l->member.size();
+  out->member = dv->lists.get();
+  out->control = l->has_control ? dv->lists.get() + used : nullptr;
+  out->weight = dv->tables.get();
+  out->design = l->design.empty() ? nullptr : dv->tables.get() + l->weight.size();
+  out->n_used = (int)used; out->n_terms = l->nk; out->stride = l->stride;
+  return 0;
+}
+
+// The two products: `coef` has K rows of a record, `rss` one.  An output slot holds coef [K][n], then rss [n].
+struct LinOut {
+  size_t n, coef, rss; // floats of a record; of each product in a slot (0: not selected)
+  LinOut(const greb_lin* l, size_t rec) : n(rec), coef((l->what & GREB_L_COEF) ? (size_t)l->nk * rec : 0), rss((l->what & GREB_L_RSS) ? rec : 0) {}
+  size_t slot() const { return coef + rss; }
+  // every selected product has somewhere to go (suffix "_dev": on the device); what is not selected is ignored
+  int check(greb_engine* e, const std::string& who, float** c, float** r, const char* suffix) const {
+    if (!coef) *c = nullptr;
+    if (!rss) *r = nullptr;
+    if (coef && !*c) return fail(e, GREB_E_INVALID, who + ": GREB_L_COEF selected but `coef" + suffix + "` is NULL");
+    if (rss && !*r) return fail(e, GREB_E_INVALID, who + ": GREB_L_RSS selected but `rss" + suffix + "` is NULL");
+    return 0;
+  }
+};
+
+int lin_launch(greb_engine* e, const LinTables& t, const float* x, size_t n, float* coef, float* rss, hipStream_t stream) {
+  if (coef) HIP_TRY(e, launch_lin_coef(x, n, t, coef, stream));
+  if (rss) HIP_TRY(e, launch_lin_rss(x, n, t, rss, stream));
+  return 0;
+}
+} // namespace
+
+extern "C" {
+
+int greb_lin_create(int nx, int ny, int n_members, const double* weight, int n_terms, const int32_t* use, const int32_t* control,
+                    const double* design, unsigned what, greb_lin** out) {
+  if (!out) return fail(nullptr, GREB_E_INVALID, "lin_create: `out` is NULL");
+  *out = nullptr;
+  if (int rc = check_grid("lin_create", nx, ny)) return rc;
+  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "lin_create: n_members = " + std::to_string(n_members));
+  if (n_terms < 1 || n_terms > kLinMaxTerms)
+    return fail(nullptr, GREB_E_INVALID, "lin_create: n_terms = " + std::to_string(n_terms) + " (1 ... " + std::to_string(kLinMaxTerms) + ")");
+  if (int rc = check_what(nullptr, "lin_create", what, GREB_L_COEF | GREB_L_RSS)) return rc;
+  if (!weight) return fail(nullptr, GREB_E_INVALID, "lin_create: `weight` is NULL");
+  if ((what & GREB_L_RSS) && !design)
+    return fail(nullptr, GREB_E_INVALID, "lin_create: GREB_L_RSS selected but `design` is NULL (the residual is that of the fit design * coef)");
+  int n_used = 0;
+  for (int m = 0; m < n_members; ++m) {
+    if (control && (control[m] < -1 || control[m] >= n_members))
+      return fail(nullptr, GREB_E_INVALID, "lin_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
+                                               " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
+    if (use && !use[m]) continue;
+    if (control && control[m] < 0)
+      return fail(nullptr, GREB_E_INVALID, "lin_create: member " + std::to_string(m) +
+                                               " is used but has no control (control = -1) while a control map is given");
+    ++n_used;
+  }
+  if (n_used == 0) return fail(nullptr, GREB_E_INVALID, "lin_create: no used member (`use` is zero everywhere)");
+  for (int m = 0; m < n_members; ++m) {
+    if (use && !use[m]) continue;
+    for (int k = 0; k < n_terms; ++k) {
+      const bool w_ok = std::isfinite(weight[(size_t)k * n_members + m]);
+      if (w_ok && (!design || std::isfinite(design[(size_t)m * n_terms + k]))) continue;
+      char buf[160];
+      std::snprintf(buf, sizeof(buf), "lin_create: %s of term %d, member %d = %g is not finite", w_ok ? "design" : "weight", k, m,
+                    w_ok ? design[(size_t)m * n_terms + k] : weight[(size_t)k * n_members + m]);
+      return fail(nullptr, GREB_E_INVALID, buf);
+    }
+  }
+  greb_lin* l = new (std::nothrow) greb_lin();
+  if (!l) return fail(nullptr, GREB_E_INVALID, "out of host memory");
+  l->nx = nx; l->ny = ny; l->nm = n_members; l->nk = n_terms; l->what = what; l->has_control = control != nullptr;
+  l->stride = kLinChunk * ((n_terms + kLinChunk - 1) / kLinChunk);
+  l->member.reserve((size_t)n_used);
+  l->weight.assign((size_t)n_used * l->stride, 0.0);
+  if (design) l->design.assign((size_t)n_used * l->stride, 0.0);
+  for (int m = 0; m < n_members; ++m) { // ascending member index
+    if (use && !use[m]) continue;
+    const size_t at = l->member.size() * (size_t)l->stride;
+    l->member.push_back(m);
+    if (control) l->control.push_back(control[m]);
+    for (int k = 0; k < n_terms; ++k) {
+      l->weight[at + k] = weight[(size_t)k * n_members + m];
+      if (design) l->design[at + k] = design[(size_t)m * n_terms + k];
+    }
+  }
+  *out = l;
+  return 0;
+}
+
+int greb_lin_destroy(greb_lin* l) {
+  delete l; // (PerDevice waits for each device before its tables go)
+  return 0;
+}
+
+int greb_lin_reduce_dev(greb_lin* l, int device, const float* x_dev, size_t n, float* coef_dev, float* rss_dev, void* stream) {
+  if (!l) return fail(nullptr, GREB_E_INVALID, "lin_reduce_dev: no plan (greb_lin is NULL)");
+  if (!x_dev) return fail(nullptr, GREB_E_INVALID, "lin_reduce_dev: x_dev is NULL");
+  if (int rc = check_aligned("lin_reduce_dev", x_dev, "x_dev")) return rc;
+  if (n < 1) return fail(nullptr, GREB_E_INVALID, "lin_reduce_dev: n = 0");
+  if (int rc = LinOut(l, n).check(nullptr, "lin_reduce_dev", &coef_dev, &rss_dev, "_dev")) return rc;
+  if (int rc = use_device("lin_reduce_dev: ", device)) return rc;
+  LinTables t{};
+  if (int rc = lin_on_device(l, device, &t)) return rc;
+  return lin_launch(nullptr, t, x_dev, n, coef_dev, rss_dev, (hipStream_t)stream);
+}
+
+int greb_engine_run_lin(greb_engine* e, int years, const float* co2_ppm, greb_lin* l, float* coef, float* rss, float* yearly) {
+  // argument errors first, before anything touches a device: the plan, the outputs, then the engine
+  if (!l) return fail(e, GREB_E_INVALID, "run_lin: no plan (greb_lin is NULL)");
+  if (years < 1) return fail(e, GREB_E_INVALID, "run_lin: years = " + std::to_string(years));
+  const size_t n = (size_t)12 * 5 * l->nx * l->ny; // one member's model year
+  const LinOut o(l, n);
+  if (int rc = o.check(e, "run_lin", &coef, &rss, "")) return rc;
+  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, "run_lin: bad argument (engine or co2_ppm)");
+  if (int rc = check_engine(e, "run_lin", l->nx, l->ny, l->nm)) return rc;
+  LinTables t{};
+  // A unit is a year's coefficients and residual map, made in output slot y & 1 of e->lin_out.  Nothing on the device
+  // grows with `years` (besides the yearly scalars).
+  auto slot = [&](int u) { return e->lin_out + (size_t)(u & 1) * o.slot(); };
+  RunSink sink;
+  sink.prepare = [&]() -> int {
+    if (int rc = ensure(e, &e->lin_out, &e->lin_out_cap, 2 * o.slot())) return rc;
+    return lin_on_device(l, e->device, &t);
+  };
+  sink.year = [&](const YearCalls& run, int y) -> int {
+    float* mon = staging_slot(e, y);
+    if (int rc = run.integrate(y, {mon, 1, 0})) return rc;
+    if (int rc = run.writing(y)) return rc; // (here, not before the year: only the reduction writes the slot)
+    if (int rc = lin_launch(e, t, mon, n, o.coef ? slot(y) : nullptr, o.rss ? slot(y) + o.coef : nullptr, e->stream)) return rc;
+    return run.complete(y);
+  };
+  sink.deliver = [&](int y, int sl) -> int {
+    if (o.coef) HIP_TRY(e, unit_to_host(e, coef, years, y, slot(sl), n, (size_t)l->nk));
+    if (o.rss) HIP_TRY(e, unit_to_host(e, rss, years, y, slot(sl) + o.coef, n, 1));
+    return 0;
   };
   return run_years(e, years, co2_ppm, yearly, sink);
 }

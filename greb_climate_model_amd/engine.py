@@ -46,6 +46,7 @@ def lib() -> C.CDLL:
         L.greb_device_info.restype = C.c_char_p
         L.greb_params_default.restype = None
         abi.ens_prototypes(L)
+        abi.lin_prototypes(L)
         _lib = L
     return _lib
 
@@ -63,6 +64,7 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_engine_add_boundary_set", "greb_engine_set_member_boundary", "greb_step_variant", "greb_step_variants",
            "greb_clim_create", "greb_clim_destroy", "greb_clim_add_year_dev", "greb_clim_finish_dev", "greb_engine_run_clim",
            "greb_ens_create", "greb_ens_destroy", "greb_ens_reduce_dev", "greb_engine_run_ens",
+           "greb_lin_create", "greb_lin_destroy", "greb_lin_reduce_dev", "greb_engine_run_lin",
            "greb_forcing_record_offset", "greb_forcing_record_field_bytes", "greb_forcing_record_step_floats",
            "greb_forcing_record_bytes", "greb_forcing_record_field_name", "greb_engine_get_forcing_record",
            "greb_forcing_record_field_static", "greb_forcing_record_static_floats"]
@@ -305,6 +307,19 @@ class Engine:
         _check(lib().greb_engine_run_ens(self.h, int(years), abi.fptr(co2), plan.h,
                                          *[None if a is None else abi.fptr(a) for a in out], abi.fptr(yearly)), self.h)
         return ens.Result(*out, yearly)
+
+    def run_lin(self, years: int, co2_ppm, plan):
+        """The scenario run of run() that hands back only the linear model of `plan` (lin.Plan) across the members, of every
+        monthly record of every year: made on the device year by year (greb_engine_run_lin).  Returns a lin.Result: coef
+        [n_terms][years][12][5][ny][nx] -- effects, slopes, whatever the plan's weights state -- and rss
+        [years][12][5][ny][nx], the residual sum of squares of the fit (a product the plan does not select is None).
+        State, clock and yearly are those of run() over the same years."""
+        from . import lin
+        co2, yearly = self._run_arrays(years, co2_ppm)
+        coef, rss = lin.empty_products(plan, (years,), (12, 5, self.ny, self.nx))
+        _check(lib().greb_engine_run_lin(self.h, int(years), abi.fptr(co2), plan.h, None if coef is None else abi.fptr(coef),
+                                         None if rss is None else abi.fptr(rss), abi.fptr(yearly)), self.h)
+        return lin.Result(coef, rss, yearly)
 
     def state(self, member: int = 0) -> np.ndarray:
         s = np.empty((5, self.ny, self.nx), np.float32)

@@ -166,6 +166,41 @@ module greb_c_api
        real(c_float), intent(in) :: co2_ppm(*)
        real(c_float), intent(out) :: yearly(*)
      end function
+     ! linear-model output (greb_lin.hip): a plan = grid, member count, weight(n_members,n_terms) (double), use(n_members)
+     ! (nonzero = the member enters the sums; c_null_ptr: all do), control(n_members) (0-based, -1 = none; c_null_ptr: no
+     ! control map), design(n_terms,n_members) (double; c_null_ptr: none) and the products `what` (1 coefficients, 2
+     ! residual sum of squares, which needs the design)
+     integer(c_int) function greb_lin_create(nx, ny, n_members, weight, n_terms, use, control, design, what, plan) &
+          bind(C, name="greb_lin_create")
+       import :: c_int, c_ptr, c_double
+       integer(c_int), value :: nx, ny, n_members, n_terms, what
+       real(c_double), intent(in) :: weight(*)
+       type(c_ptr), value :: use, control, design
+       type(c_ptr), intent(out) :: plan
+     end function
+     integer(c_int) function greb_lin_destroy(plan) bind(C, name="greb_lin_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan
+     end function
+     ! device pointers (c_ptr): x_dev(n,n_members) -> coef_dev(n,n_terms), rss_dev(n); a product the plan does not select
+     ! may be c_null_ptr; launches on `stream`, no synchronisation
+     integer(c_int) function greb_lin_reduce_dev(plan, device, x_dev, n, coef_dev, rss_dev, stream) &
+          bind(C, name="greb_lin_reduce_dev")
+       import :: c_int, c_ptr, c_size_t
+       type(c_ptr), value :: plan, x_dev, coef_dev, rss_dev, stream
+       integer(c_int), value :: device
+       integer(c_size_t), value :: n
+     end function
+     ! greb_engine_run that delivers only the plan's linear model of every year's monthly records:
+     ! coef (nx,ny,5,12,years,n_terms); rss (nx,ny,5,12,years); a product the plan does not select may be c_null_ptr
+     integer(c_int) function greb_engine_run_lin(eng, years, co2_ppm, plan, coef, rss, yearly) &
+          bind(C, name="greb_engine_run_lin")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, plan, coef, rss
+       integer(c_int), value :: years
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
      ! greb_engine_run that also delivers the monthly means of the 13 flux terms of the update (GREB_B_* of greb_engine.h):
      ! budget(nx,ny,13,12,years,n_members); monthly as in greb_engine_run, or c_null_ptr for a budget-only run
      integer(c_int) function greb_engine_run_budget(eng, years, co2_ppm, monthly, budget, yearly, run_flags) &

@@ -343,6 +343,55 @@ int greb_ens_reduce_dev(greb_ens* s, int device, const float* x_dev, size_t n, f
 int greb_engine_run_ens(greb_engine* e, int years, const float* co2_ppm, greb_ens* s, float* mean, float* var, float* min,
                         float* max, float* quant, float* yearly);
 
+/* ---- linear-model output: effects and sensitivities across members, made on the device -------------
+ * An ensemble whose members differ by design -- the factorial of the process switches, perturbed physics -- is read through
+ * a linear model across its members: the main effect of each process and the interactions between them, or the regression
+ * slope of the response on each parameter.  All of these are linear contrasts along the member axis, out_k = sum_m
+ * w[k][m] v_m: factorial effects with weights +-1/M, least-squares coefficients with W = pinv(X), a weighted mean or a
+ * difference of two group means likewise.  A plan holds weight[n_terms][n_members] (fp64), optionally use[n_members]
+ * (nonzero: the member enters the sums; NULL: all do), control[n_members] (as greb_ens: -1 ... n_members-1, control[m] = m
+ * is legal) and design[n_members][n_terms] (fp64; needed by GREB_L_RSS).  Per element i of x[n_members][n], over the USED
+ * members in ascending member index, with the samples
+ *   v = x[m][i]                          without a control map
+ *   v = x[m][i] - x[control[m]][i]       with one, as ONE fp32 subtraction
+ * all in fp64, each product rounded to fp32 exactly once:
+ *   GREB_L_COEF  b_k = sum weight[k][m] (double)v, each term an fp64 multiply followed by an fp64 add, from +0.0;
+ *                coef[k][i] = (float)b_k
+ *   GREB_L_RSS   per used member, in ascending m: f = sum_k design[m][k] b_k over ascending k from +0.0 (multiply, then
+ *                add; the unrounded fp64 b_k), r = (double)v - f, R = R + r r from +0.0;  rss[i] = (float)R: the residual
+ *                sum of squares of the fit design * b (for W = pinv(X): what the least-squares fit leaves unexplained)
+ * The order of these operations is the definition of the results (no fused multiply-add); every output element has one
+ * owner (no atomics), so results are deterministic and depend neither on what else the call holds nor on the other
+ * product.  A member with use[m] = 0 that is no used member's control is never read: its row may hold NaN. */
+#define GREB_L_COEF 1u
+#define GREB_L_RSS  2u
+#define GREB_LIN_MAX_TERMS 64
+typedef struct greb_lin greb_lin;
+/* A plan: grid, member count, weight[n_terms][n_members], use[n_members] or NULL, control[n_members] or NULL,
+ * design[n_members][n_terms] or NULL and the products `what` (GREB_L_*).  Host work only, validated without touching a
+ * device.  GREB_E_INVALID with a message that names the offender (greb_engine_last_error(NULL)): a grid greb_diag_create
+ * does not take, n_members < 1, n_terms outside 1 ... 64, `what` zero or with unknown bits, `weight` NULL, GREB_L_RSS
+ * without `design`, a control index out of range, a used member whose control is -1 while a control map is given, no
+ * used member, a weight or design entry of a used member that is not finite (the message names term and member; what
+ * belongs to an unused member is not looked at).  A plan serves any number of calls and engines. */
+int greb_lin_create(int nx, int ny, int n_members, const double* weight, int n_terms, const int32_t* use, const int32_t* control,
+                    const double* design, unsigned what, greb_lin** out);
+int greb_lin_destroy(greb_lin* l); /* waits for the device before it frees the tables */
+/* x_dev[n_members][n] on HIP device `device` (16-byte aligned; n is arbitrary, a model year's staging slot is
+ * n = 12 * 5 * ny * nx) -> coef_dev [n_terms][n] and rss_dev [n].  A pointer whose product the plan does not select is
+ * ignored and may be NULL; a selected product with a NULL pointer is GREB_E_INVALID.  Launches on `stream` (a
+ * hipStream_t, may be NULL) and does not synchronise.  Arguments are checked before any device query; without a device:
+ * GREB_E_NOGPU (no CPU path). */
+int greb_lin_reduce_dev(greb_lin* l, int device, const float* x_dev, size_t n, float* coef_dev, float* rss_dev, void* stream);
+/* greb_engine_run that delivers ONLY the plan's products of each model year's monthly records, to host memory:
+ *   coef  [n_terms][years][12][5][ny][nx]      rss  [years][12][5][ny][nx]
+ * (unselected products as above; a plan made for another grid or member count is GREB_E_INVALID; all of it is decided
+ * before any device work).  Each year is integrated into one of the engine's two one-year staging slots and reduced
+ * there into one of two device output slots, which leaves on the copy stream while the following year integrates.
+ * Device memory does not grow with `years` (the yearly scalars aside).  co2_ppm, yearly, the model clock, the state the
+ * engine is left in and the kernels that integrate are those of greb_engine_run over the same years, bit for bit. */
+int greb_engine_run_lin(greb_engine* e, int years, const float* co2_ppm, greb_lin* l, float* coef, float* rss, float* yearly);
+
 /* ---- per-member forcing: regional and seasonal CO2, insolation tables and scale --------------------
  * Members of one engine may differ in the forcing itself, not only in the CO2 level: CO2 raised in one hemisphere, over
  * land or ocean only or in one half of the year, a changed solar constant, a changed latitudinal or seasonal distribution
