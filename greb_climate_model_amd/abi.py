@@ -149,6 +149,26 @@ def lin_prototypes(lib) -> None:
         f.restype = C.c_int
 
 
+MAX_RECORD_VARS = 16  # GREB_MAX_RECORD_VARS: variables per month of the records a diag or clim plan reduces
+
+
+def budget_prototypes(lib) -> None:
+    """The argument types of the plans with a variable count, of greb_budget_combine_dev (it takes a size_t) and of the
+    four reduced runs over the budget records."""
+    i32p, vp = C.POINTER(C.c_int32), C.c_void_p
+    lib.greb_diag_create_vars.argtypes = [C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, C.POINTER(vp)]
+    lib.greb_clim_create_vars.argtypes = [C.c_int, C.c_int, C.c_int, i32p, C.c_uint, C.c_int, C.POINTER(vp)]
+    lib.greb_budget_combine_dev.argtypes = [c_float_p, C.c_int, vp, C.c_int, C.c_size_t, vp, vp]
+    head = [vp, C.c_int, c_float_p, c_float_p, C.c_int, vp]  # engine, years, co2_ppm, combo, n_out, plan
+    lib.greb_engine_run_budget_diag.argtypes = head + [C.c_uint] + [c_float_p] * 4
+    lib.greb_engine_run_budget_clim.argtypes = head + [C.c_int, i32p, i32p] + [c_float_p] * 6
+    lib.greb_engine_run_budget_ens.argtypes = head + [c_float_p] * 6
+    lib.greb_engine_run_budget_lin.argtypes = head + [c_float_p] * 3
+    for f in (lib.greb_diag_create_vars, lib.greb_clim_create_vars, lib.greb_budget_combine_dev, lib.greb_engine_run_budget_diag,
+              lib.greb_engine_run_budget_clim, lib.greb_engine_run_budget_ens, lib.greb_engine_run_budget_lin):
+        f.restype = C.c_int
+
+
 def nan_overrides(n: int):
     arr = (GrebMemberOverrides * n)()
     for o in arr:

@@ -37,10 +37,10 @@ def selected(what: int) -> tuple:
             resp and bool(what & abi.C_MEAN), resp and bool(what & abi.C_SEASONS))
 
 
-def empty_products(what: int, lead: tuple, ny: int, nx: int) -> list:
-    """Host arrays for the selected products, lead + [12 or 5][5][ny][nx] (None where not selected)."""
+def empty_products(what: int, lead: tuple, ny: int, nx: int, n_vars: int = 5) -> list:
+    """Host arrays for the selected products, lead + [12 or 5][n_vars][ny][nx] (None where not selected)."""
     n = (12, 5, 12, 12, 5)
-    return [np.empty(tuple(lead) + (k, 5, ny, nx), np.float32) if on else None for k, on in zip(n, selected(what))]
+    return [np.empty(tuple(lead) + (k, n_vars, ny, nx), np.float32) if on else None for k, on in zip(n, selected(what))]
 
 
 @dataclass
@@ -48,13 +48,15 @@ class Result:
     """What run_clim / finish_dev / reference hand back; a product that was not selected is None.
     mean, trend, mean_resp [..][12][5][ny][nx]; seasons, seasons_resp [..][5: SEASONS][5][ny][nx]; `..` =
     [n_members][n_periods] from Engine.run_clim and [n_members] from finish_dev and reference.  The responses are member
-    minus its control; a member without one (control -1) holds NaN there."""
+    minus its control; a member without one (control -1) holds NaN there.  Where the plan has another n_vars than 5
+    (budget records: Engine.run_clim(records=...)), that count stands in place of the variables' [5]."""
     mean: object
     seasons: object
     trend: object
     mean_resp: object
     seasons_resp: object
     yearly: object = None
+    vars: tuple = None  # the names of the variables (the axis the shapes call [5]) where the run knows them
 
     def season(self, name: str, response: bool = False):
         a = self.seasons_resp if response else self.seasons
@@ -64,12 +66,13 @@ class Result:
 class Plan(_plan.Handle):
     """greb_clim handle: grid, member count, each member's control member (-1: none; None: no control map) and the
     products (abi.C_* bits; default: MEAN, SEASONS and TREND, and their RESPONSE when there is a control map).  Host data
-    only; creating one needs no GPU, and every argument error is a GrebError(-1) naming the offender."""
+    only; creating one needs no GPU, and every argument error is a GrebError(-1) naming the offender.  n_vars: the
+    variables per month of the records it sums (5: a year of state records; 1 ... abi.MAX_RECORD_VARS)."""
     _destroy = "greb_clim_destroy"
 
-    def __init__(self, nx: int, ny: int, n_members: int, control=None, what: int | None = None):
+    def __init__(self, nx: int, ny: int, n_members: int, control=None, what: int | None = None, n_vars: int = 5):
         from . import engine
-        self.nx, self.ny, self.nm = int(nx), int(ny), int(n_members)
+        self.nx, self.ny, self.nm, self.nv = int(nx), int(ny), int(n_members), int(n_vars)
         if what is None:
             what = ALL if control is not None else ALL & ~abi.C_RESPONSE
         self.what = int(what)
@@ -80,15 +83,15 @@ class Plan(_plan.Handle):
                 raise engine.GrebError(-1, f"clim.Plan: control must hold {self.nm} integers, one per member")
             self.control = np.ascontiguousarray(ctl, np.int32)
         cp = None if self.control is None else self.control.ctypes.data_as(C.POINTER(C.c_int32))
-        self._create("greb_clim_create", self.nx, self.ny, self.nm, cp, C.c_uint(self.what & 0xFFFFFFFF))
+        self._create("greb_clim_create_vars", self.nx, self.ny, self.nm, cp, C.c_uint(self.what & 0xFFFFFFFF), self.nv)
 
 
 def add_year_dev(plan: Plan, monthly_year, k: int) -> None:
-    """Year k (0-based) of the current period, a contiguous float32 GPU tensor [n_members][12][5][ny][nx], added to the
+    """Year k (0-based) of the current period, a contiguous float32 GPU tensor [n_members][12][plan.nv][ny][nx], added to the
     plan's sums where it is (greb_clim_add_year_dev) on torch's current stream, without synchronising."""
     from . import engine
     x = monthly_year
-    want = (plan.nm, 12, 5, plan.ny, plan.nx)
+    want = (plan.nm, 12, plan.nv, plan.ny, plan.nx)
     dev = _plan.gpu_tensor_check(x, tuple(x.shape) == want, "clim.add_year_dev", str(list(want)))
     _plan.call_on_current_stream(dev, engine.lib().greb_clim_add_year_dev, plan.h, int(dev), _plan.ptr(x), int(k))
     plan._device = dev
@@ -103,7 +106,7 @@ def finish_dev(plan: Plan, n_years: int) -> Result:
     if dev is None:
         raise engine.GrebError(-1, "clim.finish_dev: no year was added to this plan")
     n = (12, 5, 12, 12, 5)
-    out = [torch.empty((plan.nm, k, 5, plan.ny, plan.nx), dtype=torch.float32, device=f"cuda:{dev}") if on else None
+    out = [torch.empty((plan.nm, k, plan.nv, plan.ny, plan.nx), dtype=torch.float32, device=f"cuda:{dev}") if on else None
            for k, on in zip(n, selected(plan.what))]
     _plan.call_on_current_stream(dev, engine.lib().greb_clim_finish_dev, plan.h, int(dev), int(n_years), *map(_plan.ptr, out))
     return Result(*out)
@@ -111,7 +114,8 @@ def finish_dev(plan: Plan, n_years: int) -> Result:
 
 def reference(monthly_years, control=None, what: int | None = None) -> Result:
     """The products in numpy fp64, operation by operation as csrc/greb_clim.hip performs them (include/greb_engine.h
-    states them): monthly_years [n_years][n_members][12][5][ny][nx] float32 (any sequence of years), control
+    states them): monthly_years [n_years][n_members][12][V][ny][nx] float32 (any sequence of years; V = 5 for state
+    records, any other count for budget records), control
     [n_members] or None.  Returns a Result of float32 arrays [n_members]...; products not in `what` are None."""
     if what is None:
         what = ALL if control is not None else ALL & ~abi.C_RESPONSE
@@ -121,8 +125,8 @@ def reference(monthly_years, control=None, what: int | None = None) -> Result:
     S = T = None
     for k in range(n):  # ascending years; year 0 stores
         x = np.asarray(monthly_years[k])
-        if x.dtype != np.float32 or x.ndim != 5 or x.shape[1:3] != (12, 5):
-            raise ValueError("reference: float32 years [n_members][12][5][ny][nx] expected")
+        if x.dtype != np.float32 or x.ndim != 5 or x.shape[1] != 12 or (S is not None and x.shape != S.shape):
+            raise ValueError("reference: float32 years [n_members][12][V][ny][nx] expected, all of one shape")
         x = x.astype(np.float64)
         if k == 0:
             S, T = x, np.zeros_like(x)

@@ -1,7 +1,7 @@
 // greb_clim.hip -- climatology output (include/greb_engine.h: greb_clim_*): the reduction along the TIME axis.
 //
 // The reference leaves multi-year means, seasonal maps and the difference to a control run to R scripts over the output
-// files of separate processes.  Here an ensemble's model year sits in HBM as [member][12][5][ny][nx] -- one staging slot
+// files of separate processes.  Here an ensemble's model year sits in HBM as [member][12][n_vars][ny][nx] -- one staging slot
 // of greb_engine_run -- with the control member beside the others, so:
 //
 //   clim_add_year_kernel  adds one model year into per-element fp64 sums S (and, for the trend, T = sum of k x with k the
@@ -111,11 +111,11 @@ __global__ __launch_bounds__(kClimThreads) void clim_finish_kernel(ClimFinishArg
                                                                    double sxx) {
   const size_t i = (size_t)blockIdx.x * kClimThreads + threadIdx.x; // [member][variable][group of four points]
   if (i >= lanes) return;
-  const size_t gp = a.np >> 2;
-  const size_t member = i / (kClimVars * gp), var = (i / gp) % kClimVars, p = 4 * (i % gp);
-  const size_t rec = a.np * kClimVars; // one month of one member
-  const size_t at_mon = (member * kClimMonths * kClimVars + var) * a.np + p;   // month mo: + mo * rec
-  const size_t at_sea = (member * kClimSeasons * kClimVars + var) * a.np + p;  // season s: + s * rec
+  const size_t gp = a.np >> 2, nv = (size_t)a.nv;
+  const size_t member = i / (nv * gp), var = (i / gp) % nv, p = 4 * (i % gp);
+  const size_t rec = a.np * nv; // one month of one member
+  const size_t at_mon = (member * kClimMonths * nv + var) * a.np + p;   // month mo: + mo * rec
+  const size_t at_sea = (member * kClimSeasons * nv + var) * a.np + p;  // season s: + s * rec
   Q mean[kClimMonths], sea[kClimSeasons];
 #pragma unroll
   for (int mo = 0; mo < kClimMonths; ++mo) {
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(kClimThreads) void clim_finish_kernel(ClimFinishArg
       for (int s = 0; s < kClimSeasons; ++s) store4(a.seasons_resp + at_sea + s * rec, nan);
     return;
   }
-  const size_t ctl_mon = ((size_t)c * kClimMonths * kClimVars + var) * a.np + p;
+  const size_t ctl_mon = ((size_t)c * kClimMonths * nv + var) * a.np + p;
   Q cmean[kClimMonths];
 #pragma unroll
   for (int mo = 0; mo < kClimMonths; ++mo) { // the control's means again from its sums: the same operations, the same bits
@@ -194,7 +194,7 @@ hipError_t launch_clim_add_year(const float* x, double* S, double* T, size_t n, 
 }
 
 hipError_t launch_clim_finish(const ClimFinishArgs& a, int n_members, hipStream_t s) {
-  const size_t lanes = (size_t)n_members * kClimVars * (a.np >> 2);
+  const size_t lanes = (size_t)n_members * a.nv * (a.np >> 2);
   if (lanes == 0) return hipSuccess;
   const double n = (double)a.n_years;
   const double kbar = (n - 1.0) / 2.0, sxx = n * (n * n - 1.0) / 12.0; // mean and sum of squares about it of 0 ... n-1 (exact)

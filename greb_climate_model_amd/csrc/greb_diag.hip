@@ -1,8 +1,8 @@
 // greb_diag.hip -- one model year of monthly records reduced on the device (include/greb_engine.h: greb_diag_*).
 //
 // The reference leaves every diagnostic to R scripts over the output file (R/analyse_output_fields.R: a global-mean
-// series from the full records).  Here a year of an ensemble sits in HBM as [member][12][5][ny][nx] -- one staging
-// slot of greb_engine_run -- and what an analysis wants of it is small: area-weighted regional means, zonal means and
+// series from the full records).  Here a year of an ensemble sits in HBM as [member][12][n_vars][ny][nx] -- one staging
+// slot of greb_engine_run has the five state records, a budget run up to sixteen -- and what an analysis wants of it is small: area-weighted regional means, zonal means and
 // the annual-mean map.  All three come out of ONE pass over the slot:
 //
 //   diag_year_kernel   a workgroup owns (member, variable, band of rows) across the twelve months.  A lane owns one
@@ -46,7 +46,8 @@ __global__ __launch_bounds__(kDiagThreads) void diag_year_kernel(DiagArgs a, int
   const int rows = min(band_rows, a.ny - j0);
   const int band_groups = rows * gpr;
   const bool do_regions = a.regions != nullptr;
-  const float* src = a.monthly + ((size_t)member * kDiagMonths * kDiagVars + var) * np; // month m: + m * 5 * np
+  const int nv = a.nv; // variables per month
+  const float* src = a.monthly + ((size_t)member * kDiagMonths * nv + var) * np; // month m: + m * nv * np
 
   if (do_regions) {
     for (int t = tid; t < kWaves * kDiagMonths * kMaxNr; t += kDiagThreads) (&red[0][0][0])[t] = 0.0;
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(kDiagThreads) void diag_year_kernel(DiagArgs a, int
     float4 x[kDiagMonths];
 #pragma unroll
     for (int m = 0; m < kDiagMonths; ++m)
-      x[m] = valid ? *reinterpret_cast<const float4*>(src + (size_t)m * kDiagVars * np + p) : make_float4(0.f, 0.f, 0.f, 0.f);
+      x[m] = valid ? *reinterpret_cast<const float4*>(src + (size_t)m * nv * np + p) : make_float4(0.f, 0.f, 0.f, 0.f);
 
     if (a.annual && valid) { // sum jday_mon[m] * X_m / 365
       double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(kDiagThreads) void diag_year_kernel(DiagArgs a, int
         s0 = fma(jday[m], (double)x[m].x, s0); s1 = fma(jday[m], (double)x[m].y, s1);
         s2 = fma(jday[m], (double)x[m].z, s2); s3 = fma(jday[m], (double)x[m].w, s3);
       }
-      *reinterpret_cast<float4*>(a.annual + ((size_t)member * kDiagVars + var) * np + p) =
+      *reinterpret_cast<float4*>(a.annual + ((size_t)member * nv + var) * np + p) =
           make_float4((float)(s0 / 365.0), (float)(s1 / 365.0), (float)(s2 / 365.0), (float)(s3 / 365.0));
     }
 
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(kDiagThreads) void diag_year_kernel(DiagArgs a, int
           s = zcarry;
         }
         if (last)
-          a.zonal[(((size_t)member * kDiagMonths + m) * kDiagVars + var) * a.ny + j0 + row] = (float)(s / (double)nx);
+          a.zonal[(((size_t)member * kDiagMonths + m) * nv + var) * a.ny + j0 + row] = (float)(s / (double)nx);
       }
       __syncthreads();
     }
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(kDiagThreads) void diag_year_kernel(DiagArgs a, int
   }
   if (do_regions) {
     __syncthreads();
-    double* out = a.partials + (((size_t)member * kDiagVars + var) * nbands + band) * kDiagMonths * a.nr;
+    double* out = a.partials + (((size_t)member * nv + var) * nbands + band) * kDiagMonths * a.nr;
     for (int t = tid; t < kDiagMonths * a.nr; t += kDiagThreads) {
       const int m = t / a.nr, r = t % a.nr;
       out[t] = ((red[0][m][r] + red[1][m][r]) + red[2][m][r]) + red[3][m][r];
@@ -121,13 +122,13 @@ __global__ __launch_bounds__(kDiagThreads) void diag_year_kernel(DiagArgs a, int
 }
 
 __global__ __launch_bounds__(kDiagThreads) void diag_regions_kernel(DiagArgs a, int nbands, int n_members) {
-  const size_t per_member = (size_t)kDiagMonths * kDiagVars * a.nr;
+  const size_t per_member = (size_t)kDiagMonths * a.nv * a.nr;
   const size_t i = (size_t)blockIdx.x * kDiagThreads + threadIdx.x; // output order: [member][month][variable][region]
   if (i >= per_member * n_members) return;
   const int member = (int)(i / per_member);
   const int rest = (int)(i % per_member);
-  const int r = rest % a.nr, var = (rest / a.nr) % kDiagVars, m = rest / (a.nr * kDiagVars);
-  const double* part = a.partials + ((size_t)member * kDiagVars + var) * nbands * kDiagMonths * a.nr + (size_t)m * a.nr + r;
+  const int r = rest % a.nr, var = (rest / a.nr) % a.nv, m = rest / (a.nr * a.nv);
+  const double* part = a.partials + ((size_t)member * a.nv + var) * nbands * kDiagMonths * a.nr + (size_t)m * a.nr + r;
   double s = 0.0;
   for (int b = 0; b < nbands; ++b) s += part[(size_t)b * kDiagMonths * a.nr]; // south to north
   a.regions[(size_t)member * a.regions_stride + rest] = (float)(s * a.inv_sum[r]);
@@ -141,14 +142,14 @@ hipError_t launch_diag_year(const DiagArgs& a, int n_members, hipStream_t s) {
   for (int m0 = 0; m0 < n_members; m0 += 65535) { // (grid.z)
     const int n = n_members - m0 < 65535 ? n_members - m0 : 65535;
     DiagArgs b = a;
-    b.monthly += (size_t)m0 * kDiagMonths * kDiagVars * a.nx * a.ny;
-    if (b.partials) b.partials += diag_partials(a.nx, a.ny, m0, a.nr);
+    b.monthly += (size_t)m0 * kDiagMonths * a.nv * a.nx * a.ny;
+    if (b.partials) b.partials += diag_partials(a.nx, a.ny, m0, a.nr, a.nv);
     if (b.regions) b.regions += (size_t)m0 * a.regions_stride;
-    if (b.zonal) b.zonal += (size_t)m0 * kDiagMonths * kDiagVars * a.ny;
-    if (b.annual) b.annual += (size_t)m0 * kDiagVars * a.nx * a.ny;
-    hipLaunchKernelGGL(diag_year_kernel, dim3((unsigned)nbands, kDiagVars, (unsigned)n), dim3(kDiagThreads), 0, s, b, band_rows, nbands);
+    if (b.zonal) b.zonal += (size_t)m0 * kDiagMonths * a.nv * a.ny;
+    if (b.annual) b.annual += (size_t)m0 * a.nv * a.nx * a.ny;
+    hipLaunchKernelGGL(diag_year_kernel, dim3((unsigned)nbands, (unsigned)a.nv, (unsigned)n), dim3(kDiagThreads), 0, s, b, band_rows, nbands);
     if (b.regions) {
-      const size_t total = (size_t)n * kDiagMonths * kDiagVars * a.nr;
+      const size_t total = (size_t)n * kDiagMonths * a.nv * a.nr;
       hipLaunchKernelGGL(diag_regions_kernel, dim3((unsigned)((total + kDiagThreads - 1) / kDiagThreads)), dim3(kDiagThreads), 0, s,
                          b, nbands, n);
     }

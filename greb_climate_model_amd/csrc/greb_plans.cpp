@@ -10,11 +10,104 @@
 #include "greb_clim.h"
 #include "greb_ens.h"
 #include "greb_lin.h"
+#include "greb_fluxes.h"
 
 using namespace greb;
 using namespace greb::host;
 
+static_assert(kFluxTerms == GREB_NBUDGET && kFluxMaxOut == GREB_MAX_RECORD_VARS, "greb_fluxes.h mirrors include/greb_engine.h");
+
 namespace {
+constexpr int kStateVars = GREB_NVAR_OUT; // the variables of a year of state records
+
+int check_n_vars(const std::string& who, int n_vars) {
+  if (n_vars >= 1 && n_vars <= GREB_MAX_RECORD_VARS) return 0;
+  return fail(nullptr, GREB_E_INVALID, who + ": n_vars = " + std::to_string(n_vars) + " (1 ... " + std::to_string(GREB_MAX_RECORD_VARS) + ")");
+}
+
+// combo[n_out][GREB_NBUDGET] checked and packed for the kernel arguments
+int make_combo(greb_engine* e, const std::string& who, const float* combo, int n_out, FluxCombo* out) {
+  if (!combo) return fail(e, GREB_E_INVALID, who + ": `combo` is NULL");
+  if (n_out < 1 || n_out > GREB_MAX_RECORD_VARS)
+    return fail(e, GREB_E_INVALID, who + ": n_out = " + std::to_string(n_out) + " (1 ... " + std::to_string(GREB_MAX_RECORD_VARS) + ")");
+  FluxCombo c{};
+  c.n_out = n_out;
+  for (int k = 0; k < n_out; ++k) {
+    unsigned row = 0;
+    for (int j = 0; j < GREB_NBUDGET; ++j) {
+      const float v = combo[(size_t)k * GREB_NBUDGET + j];
+      if (!std::isfinite(v)) {
+        char buf[160];
+        std::snprintf(buf, sizeof(buf), ": combo row %d, term %d (%s) = %g is not finite", k, j, greb_budget_name(j), (double)v);
+        return fail(e, GREB_E_INVALID, who + buf);
+      }
+      c.c[k][j] = v;
+      if (v != 0.f) row |= 1u << j;
+    }
+    if (!row)
+      return fail(e, GREB_E_INVALID, who + ": combo row " + std::to_string(k) + " is zero in every term 0 ... " +
+                                         std::to_string(GREB_NBUDGET - 1) + " (an output must use at least one term)");
+    c.used |= row;
+  }
+  *out = c;
+  return 0;
+}
+
+// Where the records a reduced run hands its plan come from: the year's five state records (greb_engine_run_diag, ...), or
+// its budget records -- the thirteen terms as the step kernels leave them, or their combinations (greb_engine_run_budget_diag,
+// ...).  One year at a time in e->budget_dev: the terms in front, the combinations behind them; everything that reads a
+// year is enqueued on the compute stream before the next year's kernels.
+struct Records {
+  int nv = kStateVars; // variables per month
+  bool budget = false, combine = false;
+  FluxCombo combo{};
+  // the state records, the terms (combo == NULL) or the rows of combo; `who` names the entry point
+  int init(greb_engine* e, const std::string& who, bool from_budget, const float* c, int n_out) {
+    budget = from_budget;
+    if (!budget) return 0;
+    nv = GREB_NBUDGET;
+    if (!c) return 0;
+    if (int rc = make_combo(e, who, c, n_out, &combo)) return rc;
+    combine = true; nv = n_out;
+    return 0;
+  }
+  // a diag or clim plan is made for a variable count
+  int check_plan(greb_engine* e, const std::string& who, int plan_vars) const {
+    if (plan_vars == nv) return 0;
+    return fail(e, GREB_E_INVALID, who + ": the plan is for n_vars = " + std::to_string(plan_vars) + ", this run reduces records of " +
+                                       std::to_string(nv) + " variables");
+  }
+  size_t year(const greb_engine* e) const { return (size_t)e->nm * 12 * nv * (size_t)e->np; } // floats of every member's year
+  static size_t terms_year(const greb_engine* e) { return (size_t)e->nm * 12 * GREB_NBUDGET * (size_t)e->np; }
+  // as run_records with a budget: the sums made and zeroed on first use, the call counted
+  int prepare(greb_engine* e) const {
+    if (!budget) return 0;
+    if (!e->bsum) {
+      const size_t n = (size_t)e->nm * GREB_NBUDGET * (size_t)e->np;
+      HIP_TRY(e, dev_alloc(&e->bsum, n));
+      HIP_TRY(e, hipMemsetAsync(e->bsum, 0, n * sizeof(float), e->stream));
+    }
+    ++e->budget_runs;
+    return ensure(e, &e->budget_dev, &e->budget_cap, terms_year(e) + (combine ? year(e) : 0));
+  }
+  // enqueue year y; *rec: where its records [member][12][nv][np] are once it is done
+  int integrate(greb_engine* e, const YearCalls& run, int y, const float** rec) const {
+    if (!budget) {
+      float* mon = staging_slot(e, y);
+      *rec = mon;
+      return run.integrate(y, {mon, 1, 0});
+    }
+    // (the kernels write their five records regardless -- into a staging slot nobody reads)
+    if (int rc = run.integrate(y, {staging_slot(e, 0), 1, 0, e->budget_dev, 1, 0})) return rc;
+    *rec = e->budget_dev;
+    if (!combine) return 0;
+    float* out = e->budget_dev + terms_year(e);
+    HIP_TRY(e, launch_budget_combine(combo, e->budget_dev, e->nm, (size_t)e->np, out, e->stream));
+    *rec = out;
+    return 0;
+  }
+};
+
 // A plan's device data: one T, which owns its arrays (DevBuf), per device the plan has worked on.
 template <typename T>
 class PerDevice {
@@ -113,6 +206,7 @@ struct ProductSink {
 // once in double.  Per device: their copies and the scratch array of the per-band partial sums.
 struct greb_diag {
   int nx = 0, ny = 0, nr = 0;  // nr = 1 + n_regions
+  int nv = kStateVars;         // variables per month of the records it reduces
   std::vector<double> w;       // [nr][ny][nx]
   std::vector<double> inv_sum; // [nr]
   struct Dev { DevBuf<double> w, inv_sum, partials; size_t partials_cap = 0; };
@@ -129,7 +223,7 @@ int diag_on_device(greb_diag* d, int device, int n_members, bool regions, greb_d
     return 0;
   };
   if (int rc = d->devs.get(device, make, &dv)) return rc;
-  const size_t need = regions ? diag_partials(d->nx, d->ny, n_members, d->nr) : 0;
+  const size_t need = regions ? diag_partials(d->nx, d->ny, n_members, d->nr, d->nv) : 0;
   if (dv->partials_cap < need) { // (a larger batch than before: an earlier reduction may still read the old array)
     if (dv->partials) HIP_TRY(nullptr, hipDeviceSynchronize());
     dv->partials_cap = 0;
@@ -143,7 +237,7 @@ int diag_on_device(greb_diag* d, int device, int n_members, bool regions, greb_d
 DiagArgs diag_args(const greb_diag* d, const greb_diag::Dev* dv, const float* monthly, float* regions, size_t regions_stride,
                    float* zonal, float* annual) {
   DiagArgs a{};
-  a.monthly = monthly; a.nx = d->nx; a.ny = d->ny; a.nr = d->nr;
+  a.monthly = monthly; a.nx = d->nx; a.ny = d->ny; a.nr = d->nr; a.nv = d->nv;
   a.w = dv->w.get(); a.inv_sum = dv->inv_sum.get(); a.partials = dv->partials.get();
   a.regions = regions; a.regions_stride = regions_stride; a.zonal = zonal; a.annual = annual;
   return a;
@@ -153,9 +247,14 @@ DiagArgs diag_args(const greb_diag* d, const greb_diag::Dev* dv, const float* mo
 extern "C" {
 
 int greb_diag_create(int nx, int ny, const float* region_w, int n_regions, greb_diag** out) {
+  return greb_diag_create_vars(nx, ny, region_w, n_regions, kStateVars, out);
+}
+
+int greb_diag_create_vars(int nx, int ny, const float* region_w, int n_regions, int n_vars, greb_diag** out) {
   if (!out) return fail(nullptr, GREB_E_INVALID, "diag_create: `out` is NULL");
   *out = nullptr;
   if (int rc = check_grid("diag_create", nx, ny)) return rc;
+  if (int rc = check_n_vars("diag_create", n_vars)) return rc;
   if (n_regions < 0 || n_regions > kDiagMaxRegions)
     return fail(nullptr, GREB_E_INVALID, "diag_create: n_regions = " + std::to_string(n_regions) + " (0 ... " +
                                              std::to_string(kDiagMaxRegions) + "; the globe is region 0 on top of them)");
@@ -173,7 +272,7 @@ int greb_diag_create(int nx, int ny, const float* region_w, int n_regions, greb_
     }
   greb_diag* d = new (std::nothrow) greb_diag();
   if (!d) return fail(nullptr, GREB_E_INVALID, "out of host memory");
-  d->nx = nx; d->ny = ny; d->nr = 1 + n_regions;
+  d->nx = nx; d->ny = ny; d->nr = 1 + n_regions; d->nv = n_vars;
   d->w.resize((size_t)d->nr * np);
   d->inv_sum.resize((size_t)d->nr);
   const double pi = 3.14159265358979323846; // the true pi: the area of a grid cell, not the model's constant
@@ -215,24 +314,31 @@ int greb_diag_reduce_dev(greb_diag* d, int device, const float* monthly_year_dev
   if (int rc = use_device("diag_reduce_dev: ", device)) return rc;
   greb_diag::Dev* dv = nullptr;
   if (int rc = diag_on_device(d, device, n_members, regions_dev != nullptr, &dv)) return rc;
-  const DiagArgs a = diag_args(d, dv, monthly_year_dev, regions_dev, (size_t)kDiagMonths * kDiagVars * d->nr, zonal_dev, annual_dev);
+  const DiagArgs a = diag_args(d, dv, monthly_year_dev, regions_dev, (size_t)kDiagMonths * d->nv * d->nr, zonal_dev, annual_dev);
   HIP_TRY(nullptr, launch_diag_year(a, n_members, (hipStream_t)stream));
   return 0;
 }
 
-int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_diag* d, unsigned what, float* regions,
-                         float* zonal, float* annual, float* yearly) {
+} // extern "C"
+
+namespace {
+// The four reduced runs, of the state records (greb_engine_run_diag, ...: `who` "run_diag") or of the budget records
+// (greb_engine_run_budget_diag, ...: "run_budget_diag").  Everything but where a year's records come from (Records) and how
+// many variables they have is the same.
+int run_diag(const std::string& who, Records src, greb_engine* e, int years, const float* co2_ppm, greb_diag* d, unsigned what,
+             float* regions, float* zonal, float* annual, float* yearly) {
   // argument errors first, before anything touches a device
-  if (!d) return fail(e, GREB_E_INVALID, "run_diag: no plan (greb_diag is NULL)");
-  if (int rc = check_what(e, "run_diag", what, GREB_D_REGIONS | GREB_D_ZONAL | GREB_D_ANNUAL)) return rc;
-  if ((what & GREB_D_REGIONS) && !regions) return fail(e, GREB_E_INVALID, "run_diag: GREB_D_REGIONS selected but `regions` is NULL");
-  if ((what & GREB_D_ZONAL) && !zonal) return fail(e, GREB_E_INVALID, "run_diag: GREB_D_ZONAL selected but `zonal` is NULL");
-  if ((what & GREB_D_ANNUAL) && !annual) return fail(e, GREB_E_INVALID, "run_diag: GREB_D_ANNUAL selected but `annual` is NULL");
-  if (!e || years < 1 || !co2_ppm) return fail(e, GREB_E_INVALID, "run_diag: bad argument (engine, years or co2_ppm)");
-  if (int rc = check_engine(e, "run_diag", d->nx, d->ny, -1)) return rc;
-  const size_t np = (size_t)e->np, nm = (size_t)e->nm;
+  if (!d) return fail(e, GREB_E_INVALID, who + ": no plan (greb_diag is NULL)");
+  if (int rc = src.check_plan(e, who, d->nv)) return rc;
+  if (int rc = check_what(e, who, what, GREB_D_REGIONS | GREB_D_ZONAL | GREB_D_ANNUAL)) return rc;
+  if ((what & GREB_D_REGIONS) && !regions) return fail(e, GREB_E_INVALID, who + ": GREB_D_REGIONS selected but `regions` is NULL");
+  if ((what & GREB_D_ZONAL) && !zonal) return fail(e, GREB_E_INVALID, who + ": GREB_D_ZONAL selected but `zonal` is NULL");
+  if ((what & GREB_D_ANNUAL) && !annual) return fail(e, GREB_E_INVALID, who + ": GREB_D_ANNUAL selected but `annual` is NULL");
+  if (!e || years < 1 || !co2_ppm) return fail(e, GREB_E_INVALID, who + ": bad argument (engine, years or co2_ppm)");
+  if (int rc = check_engine(e, who, d->nx, d->ny, -1)) return rc;
+  const size_t np = (size_t)e->np, nm = (size_t)e->nm, nv = (size_t)src.nv;
   const bool do_r = (what & GREB_D_REGIONS) != 0, do_z = (what & GREB_D_ZONAL) != 0, do_a = (what & GREB_D_ANNUAL) != 0;
-  const size_t reg_year = (size_t)12 * 5 * d->nr, zon_year = (size_t)12 * 5 * e->ny, ann_year = 5 * np; // floats per member-year
+  const size_t reg_year = (size_t)12 * nv * d->nr, zon_year = (size_t)12 * nv * e->ny, ann_year = nv * np; // floats per member-year
   const size_t zon_slot = do_z ? nm * zon_year : 0, ann_slot = do_a ? nm * ann_year : 0, out_slot = zon_slot + ann_slot;
   greb_diag::Dev* dv = nullptr;
   // A unit is a year's zonal means and annual maps, made in output slot y & 1 of e->diag_out.  The region series -- the
@@ -241,11 +347,12 @@ int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_d
   s.prepare = [&]() -> int {
     if (out_slot) if (int rc = ensure(e, &e->diag_out, &e->diag_out_cap, 2 * out_slot)) return rc;
     if (do_r) if (int rc = ensure(e, &e->diag_reg, &e->diag_reg_cap, nm * years * reg_year)) return rc;
+    if (int rc = src.prepare(e)) return rc;
     return diag_on_device(d, e->device, e->nm, do_r, &dv);
   };
   s.year = [&](const YearCalls& run, int y) -> int {
-    float* mon = staging_slot(e, y);
-    if (int rc = run.integrate(y, {mon, 1, 0})) return rc;
+    const float* mon = nullptr;
+    if (int rc = src.integrate(e, run, y, &mon)) return rc;
     if (int rc = run.writing(y)) return rc; // (here, not before the year: only the reduction writes the slot)
     float* out = out_slot ? e->diag_out + (size_t)(y & 1) * out_slot : nullptr;
     const DiagArgs g = diag_args(d, dv, mon, do_r ? e->diag_reg + (size_t)y * reg_year : nullptr, (size_t)years * reg_year,
@@ -265,6 +372,37 @@ int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_d
   };
   return run_years(e, years, co2_ppm, yearly, s);
 }
+} // namespace
+
+extern "C" {
+
+int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_diag* d, unsigned what, float* regions,
+                         float* zonal, float* annual, float* yearly) {
+  return run_diag("run_diag", Records{}, e, years, co2_ppm, d, what, regions, zonal, annual, yearly);
+}
+
+int greb_engine_run_budget_diag(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_diag* d,
+                                unsigned what, float* regions, float* zonal, float* annual, float* yearly) {
+  Records src;
+  if (int rc = src.init(e, "run_budget_diag", true, combo, n_out)) return rc;
+  return run_diag("run_budget_diag", src, e, years, co2_ppm, d, what, regions, zonal, annual, yearly);
+}
+
+int greb_budget_combine_dev(const float* combo, int n_out, const float* budget_year_dev, int n_members, size_t np, float* out_dev,
+                            void* stream) {
+  FluxCombo c{};
+  if (int rc = make_combo(nullptr, "budget_combine_dev", combo, n_out, &c)) return rc;
+  if (!budget_year_dev || !out_dev) return fail(nullptr, GREB_E_INVALID, "budget_combine_dev: budget_year_dev or out_dev is NULL");
+  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "budget_combine_dev: n_members = " + std::to_string(n_members));
+  if (np < 4 || (np & 3)) return fail(nullptr, GREB_E_INVALID, "budget_combine_dev: np = " + std::to_string(np) + " (a multiple of four)");
+  if (int rc = check_aligned("budget_combine_dev", budget_year_dev, "budget_year_dev")) return rc;
+  if (int rc = check_aligned("budget_combine_dev", out_dev, "out_dev")) return rc;
+  int ndev = 0, device = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || hipGetDevice(&device) != hipSuccess)
+    return fail(nullptr, GREB_E_NOGPU, "budget_combine_dev: no HIP device (no CPU path)");
+  HIP_TRY(nullptr, launch_budget_combine(c, budget_year_dev, n_members, np, out_dev, (hipStream_t)stream));
+  return 0;
+}
 
 } // extern "C"
 
@@ -273,13 +411,14 @@ int greb_engine_run_diag(greb_engine* e, int years, const float* co2_ppm, greb_d
 // `added` counts the years since the last finish: one period is summed at a time, on one device.
 struct greb_clim {
   int nx = 0, ny = 0, nm = 0;
+  int nv = kStateVars;          // variables per month of the records it sums
   unsigned what = 0;
   std::vector<int32_t> control; // [nm], or empty: no control map
   int added = 0;                // years added since the last finish
   int added_device = -1;        // ... on this device
   struct Dev { DevBuf<double> S, T; DevBuf<int> control; };
   PerDevice<Dev> devs;
-  size_t elems() const { return (size_t)nm * kClimMonths * kClimVars * nx * ny; }
+  size_t elems() const { return (size_t)nm * kClimMonths * nv * nx * ny; }
 };
 
 namespace {
@@ -297,7 +436,7 @@ const char* const kClimFlagNames[5] = {"GREB_C_MEAN", "GREB_C_SEASONS", "GREB_C_
                                        "GREB_C_RESPONSE with GREB_C_SEASONS"};
 // floats of one member's record of each product of one period: MEAN, SEASONS, TREND, the MEAN response, the SEASONS response
 Products clim_products(const greb_clim* c) {
-  const size_t np = (size_t)c->nx * c->ny, mon = (size_t)kClimMonths * kClimVars * np, sea = (size_t)kClimSeasons * kClimVars * np;
+  const size_t np = (size_t)c->nx * c->ny, mon = (size_t)kClimMonths * c->nv * np, sea = (size_t)kClimSeasons * c->nv * np;
   const bool resp = (c->what & GREB_C_RESPONSE) != 0;
   Products pr{kClimOutNames, kClimFlagNames};
   pr.size[0] = (c->what & GREB_C_MEAN) ? mon : 0;
@@ -311,7 +450,7 @@ Products clim_products(const greb_clim* c) {
 ClimFinishArgs clim_finish_args(const greb_clim* c, const greb_clim::Dev* dv, int n_years, float* const out[5]) {
   ClimFinishArgs a{};
   a.S = dv->S.get(); a.T = dv->T.get(); a.control = dv->control.get();
-  a.np = (size_t)c->nx * c->ny; a.n_years = n_years;
+  a.np = (size_t)c->nx * c->ny; a.nv = c->nv; a.n_years = n_years;
   a.mean = out[0]; a.seasons = out[1]; a.trend = out[2]; a.mean_resp = out[3]; a.seasons_resp = out[4];
   return a;
 }
@@ -320,9 +459,14 @@ ClimFinishArgs clim_finish_args(const greb_clim* c, const greb_clim::Dev* dv, in
 extern "C" {
 
 int greb_clim_create(int nx, int ny, int n_members, const int32_t* control, unsigned what, greb_clim** out) {
+  return greb_clim_create_vars(nx, ny, n_members, control, what, kStateVars, out);
+}
+
+int greb_clim_create_vars(int nx, int ny, int n_members, const int32_t* control, unsigned what, int n_vars, greb_clim** out) {
   if (!out) return fail(nullptr, GREB_E_INVALID, "clim_create: `out` is NULL");
   *out = nullptr;
   if (int rc = check_grid("clim_create", nx, ny)) return rc;
+  if (int rc = check_n_vars("clim_create", n_vars)) return rc;
   if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "clim_create: n_members = " + std::to_string(n_members));
   if (int rc = check_what(nullptr, "clim_create", what, GREB_C_MEAN | GREB_C_SEASONS | GREB_C_TREND | GREB_C_RESPONSE)) return rc;
   if ((what & GREB_C_RESPONSE) && !(what & (GREB_C_MEAN | GREB_C_SEASONS)))
@@ -337,7 +481,7 @@ int greb_clim_create(int nx, int ny, int n_members, const int32_t* control, unsi
                                                  " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
   greb_clim* c = new (std::nothrow) greb_clim();
   if (!c) return fail(nullptr, GREB_E_INVALID, "out of host memory");
-  c->nx = nx; c->ny = ny; c->nm = n_members; c->what = what;
+  c->nx = nx; c->ny = ny; c->nm = n_members; c->what = what; c->nv = n_vars;
   if (control) c->control.assign(control, control + n_members);
   *out = c;
   return 0;
@@ -386,17 +530,21 @@ int greb_clim_finish_dev(greb_clim* c, int device, int n_years, float* mean_dev,
   return 0;
 }
 
-int greb_engine_run_clim(greb_engine* e, int years, const float* co2_ppm, greb_clim* c, int n_periods, const int32_t* first_year,
-                         const int32_t* n_years, float* mean, float* seasons, float* trend, float* mean_resp, float* seasons_resp,
-                         float* yearly) {
+} // extern "C"
+
+namespace {
+int run_clim(const std::string& name, Records src, greb_engine* e, int years, const float* co2_ppm, greb_clim* c, int n_periods,
+             const int32_t* first_year, const int32_t* n_years, float* mean, float* seasons, float* trend, float* mean_resp,
+             float* seasons_resp, float* yearly) {
   // argument errors first, before anything touches a device: the plan, the periods, the outputs, then the engine
-  if (!c) return fail(e, GREB_E_INVALID, "run_clim: no plan (greb_clim is NULL)");
-  if (years < 1) return fail(e, GREB_E_INVALID, "run_clim: years = " + std::to_string(years));
+  if (!c) return fail(e, GREB_E_INVALID, name + ": no plan (greb_clim is NULL)");
+  if (int rc = src.check_plan(e, name, c->nv)) return rc;
+  if (years < 1) return fail(e, GREB_E_INVALID, name + ": years = " + std::to_string(years));
   if (n_periods < 1 || !first_year || !n_years)
-    return fail(e, GREB_E_INVALID, "run_clim: n_periods = " + std::to_string(n_periods) + " with first_year / n_years " +
+    return fail(e, GREB_E_INVALID, name + ": n_periods = " + std::to_string(n_periods) + " with first_year / n_years " +
                                        (first_year && n_years ? "given" : "NULL") + " (at least one period is needed)");
   for (int p = 0; p < n_periods; ++p) {
-    const std::string who = "run_clim: period " + std::to_string(p) + " (first_year " + std::to_string(first_year[p]) + ", n_years " +
+    const std::string who = name + ": period " + std::to_string(p) + " (first_year " + std::to_string(first_year[p]) + ", n_years " +
                             std::to_string(n_years[p]) + ")";
     if (n_years[p] < 1) return fail(e, GREB_E_INVALID, who + " has no years");
     if (first_year[p] < 0 || (long long)first_year[p] + n_years[p] > years)
@@ -409,11 +557,11 @@ int greb_engine_run_clim(greb_engine* e, int years, const float* co2_ppm, greb_c
   }
   Products pr = clim_products(c);
   float* host[5] = {mean, seasons, trend, mean_resp, seasons_resp};
-  if (int rc = pr.check(e, "run_clim", host, "", false)) return rc;
+  if (int rc = pr.check(e, name, host, "", false)) return rc;
   if (c->added != 0)
-    return fail(e, GREB_E_INVALID, "run_clim: the plan holds " + std::to_string(c->added) + " years of an unfinished period");
-  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, "run_clim: bad argument (engine or co2_ppm)");
-  if (int rc = check_engine(e, "run_clim", c->nx, c->ny, c->nm)) return rc;
+    return fail(e, GREB_E_INVALID, name + ": the plan holds " + std::to_string(c->added) + " years of an unfinished period");
+  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, name + ": bad argument (engine or co2_ppm)");
+  if (int rc = check_engine(e, name, c->nx, c->ny, c->nm)) return rc;
   pr.layout((size_t)e->nm);
   greb_clim::Dev* dv = nullptr;
   int p = 0; // the period the current year is in or before
@@ -421,10 +569,13 @@ int greb_engine_run_clim(greb_engine* e, int years, const float* co2_ppm, greb_c
   // or `n_periods` (besides the yearly scalars).
   const ProductSink k{e, pr, &e->clim_out, &e->clim_out_cap, host, n_periods};
   RunSink s;
-  k.install(s, [&]() -> int { return clim_on_device(c, e->device, &dv); });
+  k.install(s, [&]() -> int {
+    if (int rc = src.prepare(e)) return rc;
+    return clim_on_device(c, e->device, &dv);
+  });
   s.year = [&](const YearCalls& run, int y) -> int {
-    float* mon = staging_slot(e, y);
-    if (int rc = run.integrate(y, {mon, 1, 0})) return rc;
+    const float* mon = nullptr;
+    if (int rc = src.integrate(e, run, y, &mon)) return rc;
     while (p < n_periods && y >= first_year[p] + n_years[p]) ++p;
     if (p >= n_periods || y < first_year[p]) return 0; // (a year outside every period is integrated, not summed)
     const int yk = y - first_year[p];
@@ -437,6 +588,25 @@ int greb_engine_run_clim(greb_engine* e, int years, const float* co2_ppm, greb_c
     return run.complete(p);
   };
   return run_years(e, years, co2_ppm, yearly, s);
+}
+} // namespace
+
+extern "C" {
+
+int greb_engine_run_clim(greb_engine* e, int years, const float* co2_ppm, greb_clim* c, int n_periods, const int32_t* first_year,
+                         const int32_t* n_years, float* mean, float* seasons, float* trend, float* mean_resp, float* seasons_resp,
+                         float* yearly) {
+  return run_clim("run_clim", Records{}, e, years, co2_ppm, c, n_periods, first_year, n_years, mean, seasons, trend, mean_resp,
+                  seasons_resp, yearly);
+}
+
+int greb_engine_run_budget_clim(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_clim* c,
+                                int n_periods, const int32_t* first_year, const int32_t* n_years, float* mean, float* seasons,
+                                float* trend, float* mean_resp, float* seasons_resp, float* yearly) {
+  Records src;
+  if (int rc = src.init(e, "run_budget_clim", true, combo, n_out)) return rc;
+  return run_clim("run_budget_clim", src, e, years, co2_ppm, c, n_periods, first_year, n_years, mean, seasons, trend, mean_resp,
+                  seasons_resp, yearly);
 }
 
 } // extern "C"
@@ -587,27 +757,33 @@ int greb_ens_reduce_dev(greb_ens* s, int device, const float* x_dev, size_t n, f
   return ens_launch(nullptr, s, l, x_dev, n, out, (hipStream_t)stream);
 }
 
-int greb_engine_run_ens(greb_engine* e, int years, const float* co2_ppm, greb_ens* s, float* mean, float* var, float* min,
-                        float* max, float* quant, float* yearly) {
+} // extern "C"
+
+namespace {
+int run_ens(const std::string& who, Records src, greb_engine* e, int years, const float* co2_ppm, greb_ens* s, float* mean,
+            float* var, float* min, float* max, float* quant, float* yearly) {
   // argument errors first, before anything touches a device: the plan, the outputs, then the engine
-  if (!s) return fail(e, GREB_E_INVALID, "run_ens: no plan (greb_ens is NULL)");
-  if (years < 1) return fail(e, GREB_E_INVALID, "run_ens: years = " + std::to_string(years));
-  const size_t n = (size_t)12 * 5 * s->nx * s->ny; // one member's model year
+  if (!s) return fail(e, GREB_E_INVALID, who + ": no plan (greb_ens is NULL)");
+  if (years < 1) return fail(e, GREB_E_INVALID, who + ": years = " + std::to_string(years));
+  const size_t n = (size_t)12 * src.nv * s->nx * s->ny; // one member's model year
   Products pr = ens_products(s, n);
   float* host[5] = {mean, var, min, max, quant};
-  if (int rc = pr.check(e, "run_ens", host, "", false)) return rc;
-  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, "run_ens: bad argument (engine or co2_ppm)");
-  if (int rc = check_engine(e, "run_ens", s->nx, s->ny, s->nm)) return rc;
+  if (int rc = pr.check(e, who, host, "", false)) return rc;
+  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, who + ": bad argument (engine or co2_ppm)");
+  if (int rc = check_engine(e, who, s->nx, s->ny, s->nm)) return rc;
   pr.layout((size_t)s->ng);
   EnsLists l{};
   // A unit is a year's statistics, made in output slot y & 1 of e->ens_out.  Nothing on the device grows with `years`
   // (besides the yearly scalars).
   const ProductSink k{e, pr, &e->ens_out, &e->ens_out_cap, host, years};
   RunSink sink;
-  k.install(sink, [&]() -> int { return ens_on_device(s, e->device, &l); });
+  k.install(sink, [&]() -> int {
+    if (int rc = src.prepare(e)) return rc;
+    return ens_on_device(s, e->device, &l);
+  });
   sink.year = [&](const YearCalls& run, int y) -> int {
-    float* mon = staging_slot(e, y);
-    if (int rc = run.integrate(y, {mon, 1, 0})) return rc;
+    const float* mon = nullptr;
+    if (int rc = src.integrate(e, run, y, &mon)) return rc;
     if (int rc = run.writing(y)) return rc; // (here, not before the year: only the reduction writes the slot)
     float* out[5];
     pr.pointers(k.slot(y), out);
@@ -615,6 +791,21 @@ int greb_engine_run_ens(greb_engine* e, int years, const float* co2_ppm, greb_en
     return run.complete(y);
   };
   return run_years(e, years, co2_ppm, yearly, sink);
+}
+} // namespace
+
+extern "C" {
+
+int greb_engine_run_ens(greb_engine* e, int years, const float* co2_ppm, greb_ens* s, float* mean, float* var, float* min,
+                        float* max, float* quant, float* yearly) {
+  return run_ens("run_ens", Records{}, e, years, co2_ppm, s, mean, var, min, max, quant, yearly);
+}
+
+int greb_engine_run_budget_ens(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_ens* s,
+                               float* mean, float* var, float* min, float* max, float* quant, float* yearly) {
+  Records src;
+  if (int rc = src.init(e, "run_budget_ens", true, combo, n_out)) return rc;
+  return run_ens("run_budget_ens", src, e, years, co2_ppm, s, mean, var, min, max, quant, yearly);
 }
 
 } // extern "C"
@@ -752,15 +943,19 @@ int greb_lin_reduce_dev(greb_lin* l, int device, const float* x_dev, size_t n, f
   return lin_launch(nullptr, t, x_dev, n, coef_dev, rss_dev, (hipStream_t)stream);
 }
 
-int greb_engine_run_lin(greb_engine* e, int years, const float* co2_ppm, greb_lin* l, float* coef, float* rss, float* yearly) {
+} // extern "C"
+
+namespace {
+int run_lin(const std::string& who, Records src, greb_engine* e, int years, const float* co2_ppm, greb_lin* l, float* coef,
+            float* rss, float* yearly) {
   // argument errors first, before anything touches a device: the plan, the outputs, then the engine
-  if (!l) return fail(e, GREB_E_INVALID, "run_lin: no plan (greb_lin is NULL)");
-  if (years < 1) return fail(e, GREB_E_INVALID, "run_lin: years = " + std::to_string(years));
-  const size_t n = (size_t)12 * 5 * l->nx * l->ny; // one member's model year
+  if (!l) return fail(e, GREB_E_INVALID, who + ": no plan (greb_lin is NULL)");
+  if (years < 1) return fail(e, GREB_E_INVALID, who + ": years = " + std::to_string(years));
+  const size_t n = (size_t)12 * src.nv * l->nx * l->ny; // one member's model year
   const LinOut o(l, n);
-  if (int rc = o.check(e, "run_lin", &coef, &rss, "")) return rc;
-  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, "run_lin: bad argument (engine or co2_ppm)");
-  if (int rc = check_engine(e, "run_lin", l->nx, l->ny, l->nm)) return rc;
+  if (int rc = o.check(e, who, &coef, &rss, "")) return rc;
+  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, who + ": bad argument (engine or co2_ppm)");
+  if (int rc = check_engine(e, who, l->nx, l->ny, l->nm)) return rc;
   LinTables t{};
   // A unit is a year's coefficients and residual map, made in output slot y & 1 of e->lin_out.  Nothing on the device
   // grows with `years` (besides the yearly scalars).
@@ -768,11 +963,12 @@ int greb_engine_run_lin(greb_engine* e, int years, const float* co2_ppm, greb_li
   RunSink sink;
   sink.prepare = [&]() -> int {
     if (int rc = ensure(e, &e->lin_out, &e->lin_out_cap, 2 * o.slot())) return rc;
+    if (int rc = src.prepare(e)) return rc;
     return lin_on_device(l, e->device, &t);
   };
   sink.year = [&](const YearCalls& run, int y) -> int {
-    float* mon = staging_slot(e, y);
-    if (int rc = run.integrate(y, {mon, 1, 0})) return rc;
+    const float* mon = nullptr;
+    if (int rc = src.integrate(e, run, y, &mon)) return rc;
     if (int rc = run.writing(y)) return rc; // (here, not before the year: only the reduction writes the slot)
     if (int rc = lin_launch(e, t, mon, n, o.coef ? slot(y) : nullptr, o.rss ? slot(y) + o.coef : nullptr, e->stream)) return rc;
     return run.complete(y);
@@ -783,6 +979,20 @@ int greb_engine_run_lin(greb_engine* e, int years, const float* co2_ppm, greb_li
     return 0;
   };
   return run_years(e, years, co2_ppm, yearly, sink);
+}
+} // namespace
+
+extern "C" {
+
+int greb_engine_run_lin(greb_engine* e, int years, const float* co2_ppm, greb_lin* l, float* coef, float* rss, float* yearly) {
+  return run_lin("run_lin", Records{}, e, years, co2_ppm, l, coef, rss, yearly);
+}
+
+int greb_engine_run_budget_lin(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_lin* l,
+                               float* coef, float* rss, float* yearly) {
+  Records src;
+  if (int rc = src.init(e, "run_budget_lin", true, combo, n_out)) return rc;
+  return run_lin("run_budget_lin", src, e, years, co2_ppm, l, coef, rss, yearly);
 }
 
 } // extern "C"

@@ -33,26 +33,29 @@ def latitudes(ny: int) -> np.ndarray:
 class Result:
     """What run_diag / reduce_dev hand back; a product that was not asked for is None.
     regions [..][12][5][1 + n_regions], zonal [..][12][5][ny], annual [..][5][ny][nx]; `..` = [n_members][years] from
-    Engine.run_diag and [n_members] from reduce_dev.  names[r] is the name of region r (names[0] the globe)."""
+    Engine.run_diag and [n_members] from reduce_dev.  names[r] is the name of region r (names[0] the globe).  Where the
+    plan has another n_vars than 5 (budget records: Engine.run_diag(records=...)), that count stands in place of [5]."""
     regions: object
     zonal: object
     annual: object
     yearly: object
     names: tuple
+    vars: tuple = None  # the names of the variables (the axis the shapes call [5]) where the run knows them
 
     def region(self, name: str):
         return self.regions[..., self.names.index(name)]
 
 
 class Plan(_plan.Handle):
-    """greb_diag handle: the grid and the regions (name -> weights [ny][nx] in [0, 1]; the globe is always region 0).
+    """greb_diag handle: the grid, the regions (name -> weights [ny][nx] in [0, 1]; the globe is always region 0) and
+    n_vars, the variables per month of the records it reduces (5: a year of state records; 1 ... abi.MAX_RECORD_VARS).
     Host data only; creating one needs no GPU, and every argument error is a GrebError(-1) naming the offender."""
     _destroy = "greb_diag_destroy"
 
-    def __init__(self, nx: int, ny: int, regions: dict | None = None):
+    def __init__(self, nx: int, ny: int, regions: dict | None = None, n_vars: int = 5):
         from . import engine
         regions = dict(regions or {})
-        self.nx, self.ny = int(nx), int(ny)
+        self.nx, self.ny, self.nv = int(nx), int(ny), int(n_vars)
         self.names = (GLOBE,) + tuple(regions)
         self.nr = len(self.names)
         for k, v in regions.items():
@@ -60,7 +63,7 @@ class Plan(_plan.Handle):
                 raise engine.GrebError(-1, f"diag.Plan: region {k!r} has shape {np.shape(v)}, the grid is {(self.ny, self.nx)}")
         self.weights = (np.ascontiguousarray(np.stack([np.asarray(v, np.float32) for v in regions.values()]))
                         if regions else np.zeros((0, self.ny, self.nx), np.float32))
-        self._create("greb_diag_create", self.nx, self.ny, abi.fptr(self.weights) if regions else None, len(regions))
+        self._create("greb_diag_create_vars", self.nx, self.ny, abi.fptr(self.weights) if regions else None, len(regions), self.nv)
 
     def _reword(self, msg: str) -> str:
         for i, k in enumerate(self.names[1:]):  # the library counts regions, the caller named them
@@ -69,17 +72,18 @@ class Plan(_plan.Handle):
 
 
 def reduce_dev(plan: Plan, monthly_year, what: int = ALL) -> Result:
-    """One model year on the GPU, a contiguous float32 torch tensor [n_members][12][5][ny][nx], reduced where it is
+    """One model year on the GPU, a contiguous float32 torch tensor [n_members][12][plan.nv][ny][nx], reduced where it is
     (greb_diag_reduce_dev) on torch's current stream, without synchronising.  Returns torch tensors on the same device."""
     import torch
     from . import engine
     x = monthly_year
-    dev = _plan.gpu_tensor_check(x, tuple(x.shape[1:]) == (12, 5, plan.ny, plan.nx), "diag.reduce_dev", f"[n][12][5][{plan.ny}][{plan.nx}]")
+    dev = _plan.gpu_tensor_check(x, tuple(x.shape[1:]) == (12, plan.nv, plan.ny, plan.nx), "diag.reduce_dev",
+                                f"[n][12][{plan.nv}][{plan.ny}][{plan.nx}]")
     n = x.shape[0]
     mk = lambda *s: torch.empty((n,) + s, dtype=torch.float32, device=x.device)
-    regions = mk(12, 5, plan.nr) if what & abi.D_REGIONS else None
-    zonal = mk(12, 5, plan.ny) if what & abi.D_ZONAL else None
-    annual = mk(5, plan.ny, plan.nx) if what & abi.D_ANNUAL else None
+    regions = mk(12, plan.nv, plan.nr) if what & abi.D_REGIONS else None
+    zonal = mk(12, plan.nv, plan.ny) if what & abi.D_ZONAL else None
+    annual = mk(plan.nv, plan.ny, plan.nx) if what & abi.D_ANNUAL else None
     _plan.call_on_current_stream(dev, engine.lib().greb_diag_reduce_dev, plan.h, int(dev), _plan.ptr(x), int(n), _plan.ptr(regions),
                                  _plan.ptr(zonal), _plan.ptr(annual))
     return Result(regions, zonal, annual, None, plan.names)
@@ -97,13 +101,13 @@ def standard_regions(inp) -> dict:
 
 
 def reduce_reference(monthly_year, weights=None):
-    """The three products in numpy fp64, from their definitions: monthly_year [..][12][5][ny][nx], weights
-    [n_regions][ny][nx] (the globe is added in front).  Returns (regions [..][12][5][1 + n_regions], zonal
-    [..][12][5][ny], annual [..][5][ny][nx]) as float64."""
+    """The three products in numpy fp64, from their definitions: monthly_year [..][12][V][ny][nx] (V = 5 for state
+    records, any other count for budget records), weights [n_regions][ny][nx] (the globe is added in front).  Returns
+    (regions [..][12][V][1 + n_regions], zonal [..][12][V][ny], annual [..][V][ny][nx]) as float64."""
     x = np.asarray(monthly_year, np.float64)
     ny, nx = x.shape[-2:]
-    if x.shape[-4:-2] != (12, 5):
-        raise ValueError("reduce_reference: [..][12][5][ny][nx] expected")
+    if x.ndim < 4 or x.shape[-4] != 12:
+        raise ValueError("reduce_reference: [..][12][V][ny][nx] expected")
     area = np.cos(np.deg2rad(latitudes(ny)))[:, None] * np.ones((ny, nx))
     w = [area] if weights is None else [area] + [np.asarray(wr, np.float64) * area for wr in weights]
     w = np.stack(w).reshape(len(w), ny * nx)

@@ -47,6 +47,7 @@ def lib() -> C.CDLL:
         L.greb_params_default.restype = None
         abi.ens_prototypes(L)
         abi.lin_prototypes(L)
+        abi.budget_prototypes(L)
         _lib = L
     return _lib
 
@@ -67,7 +68,9 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_lin_create", "greb_lin_destroy", "greb_lin_reduce_dev", "greb_engine_run_lin",
            "greb_forcing_record_offset", "greb_forcing_record_field_bytes", "greb_forcing_record_step_floats",
            "greb_forcing_record_bytes", "greb_forcing_record_field_name", "greb_engine_get_forcing_record",
-           "greb_forcing_record_field_static", "greb_forcing_record_static_floats"]
+           "greb_forcing_record_field_static", "greb_forcing_record_static_floats",
+           "greb_diag_create_vars", "greb_clim_create_vars", "greb_budget_combine_dev", "greb_engine_run_budget_diag",
+           "greb_engine_run_budget_clim", "greb_engine_run_budget_ens", "greb_engine_run_budget_lin"]
 
 
 def _check(rc: int, h=None):
@@ -264,62 +267,84 @@ class Engine:
                  abi.fptr(yearly), 0), self.h)
         return monthly, budget, yearly
 
-    def run_diag(self, years: int, co2_ppm, plan, what: int | None = None):
+    def _reduced(self, name: str, records, co2, plan, *args):
+        """Call the reduced run `name` ("diag", "clim", "ens", "lin") over `records`: "state" -- the year's five state
+        records (greb_engine_run_<name>) --, "budget" -- its thirteen flux terms -- or a budget.Combo -- sums of them
+        (greb_engine_run_budget_<name>).  `args`: what follows the plan in the C call."""
+        from . import budget
+        if isinstance(records, str) and records == "state":
+            _check(getattr(lib(), "greb_engine_run_" + name)(self.h, int(co2.shape[1]), abi.fptr(co2), plan.h, *args), self.h)
+            return
+        cb = budget.as_combo(records)
+        _check(getattr(lib(), "greb_engine_run_budget_" + name)(self.h, int(co2.shape[1]), abi.fptr(co2),
+                                                                None if cb is None else abi.fptr(cb.matrix),
+                                                                0 if cb is None else len(cb.names), plan.h, *args), self.h)
+
+    def run_diag(self, years: int, co2_ppm, plan, what: int | None = None, records="state"):
         """The scenario run of run() that hands back only the reduced products of `plan` (diag.Plan): regional means,
         zonal means and annual-mean maps made on the device year by year (greb_engine_run_diag).  what: abi.D_* bits,
         default all three.  Returns a diag.Result (regions, zonal, annual, yearly, region names; a product that was
-        not selected is None).  State, clock and yearly are those of run() over the same years."""
-        from . import diag
+        not selected is None).  State, clock and yearly are those of run() over the same years.
+        records: "state" (the five state records), "budget" (the thirteen flux terms of run_budget) or a budget.combo(...)
+        (sums of them); the plan's n_vars must be that count, which stands where the shapes say 5, and the result
+        carries the variables' names (Result.vars)."""
+        from . import budget, diag
         what = diag.ALL if what is None else int(what)
         co2, yearly = self._run_arrays(years, co2_ppm)
-        regions = np.empty((self.nm, years, 12, 5, plan.nr), np.float32) if what & abi.D_REGIONS else None
-        zonal = np.empty((self.nm, years, 12, 5, self.ny), np.float32) if what & abi.D_ZONAL else None
-        annual = np.empty((self.nm, years, 5, self.ny, self.nx), np.float32) if what & abi.D_ANNUAL else None
+        names = budget.record_names(records)
+        nv = len(names)
+        regions = np.empty((self.nm, years, 12, nv, plan.nr), np.float32) if what & abi.D_REGIONS else None
+        zonal = np.empty((self.nm, years, 12, nv, self.ny), np.float32) if what & abi.D_ZONAL else None
+        annual = np.empty((self.nm, years, nv, self.ny, self.nx), np.float32) if what & abi.D_ANNUAL else None
         ptr = [None if a is None else abi.fptr(a) for a in (regions, zonal, annual)]
-        _check(lib().greb_engine_run_diag(self.h, int(years), abi.fptr(co2), plan.h, C.c_uint(what), *ptr, abi.fptr(yearly)),
-               self.h)
-        return diag.Result(regions, zonal, annual, yearly, plan.names)
+        self._reduced("diag", records, co2, plan, C.c_uint(what), *ptr, abi.fptr(yearly))
+        return diag.Result(regions, zonal, annual, yearly, plan.names, names)
 
-    def run_clim(self, years: int, co2_ppm, plan, periods):
+    def run_clim(self, years: int, co2_ppm, plan, periods, records="state"):
         """The scenario run of run() that hands back only the climatology products of `plan` (clim.Plan) over `periods`, a
         list of (first_year, n_years) inside this call's years -- ascending, not overlapping; years outside every period
         are integrated but not summed (greb_engine_run_clim).  Returns a clim.Result of arrays [n_members][n_periods]...
-        (a product the plan does not select is None).  State, clock and yearly are those of run() over the same years."""
-        from . import clim
+        (a product the plan does not select is None).  State, clock and yearly are those of run() over the same years.
+        records: as in run_diag."""
+        from . import budget, clim
         co2, yearly = self._run_arrays(years, co2_ppm)
+        names = budget.record_names(records)
         per = np.ascontiguousarray(periods, np.int32).reshape(-1, 2)
         first, count = np.ascontiguousarray(per[:, 0]), np.ascontiguousarray(per[:, 1])
-        out = clim.empty_products(plan.what, (self.nm, len(per)), self.ny, self.nx)
+        out = clim.empty_products(plan.what, (self.nm, len(per)), self.ny, self.nx, len(names))
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        _check(lib().greb_engine_run_clim(self.h, int(years), abi.fptr(co2), plan.h, len(per), ip(first), ip(count),
-                                          *[None if a is None else abi.fptr(a) for a in out], abi.fptr(yearly)), self.h)
-        return clim.Result(*out, yearly)
+        self._reduced("clim", records, co2, plan, len(per), ip(first), ip(count),
+                      *[None if a is None else abi.fptr(a) for a in out], abi.fptr(yearly))
+        return clim.Result(*out, yearly, names)
 
-    def run_ens(self, years: int, co2_ppm, plan):
+    def run_ens(self, years: int, co2_ppm, plan, records="state"):
         """The scenario run of run() that hands back only the statistics across the members of each group of `plan`
         (ens.Plan), of every monthly record of every year: made on the device year by year, of the records or of each
         member's difference to its control member (greb_engine_run_ens).  Returns an ens.Result of arrays
         [n_groups][years][12][5][ny][nx], quant [n_groups][years][n_probs][12][5][ny][nx] (a product the plan does not
-        select is None).  State, clock and yearly are those of run() over the same years."""
-        from . import ens
+        select is None).  State, clock and yearly are those of run() over the same years.
+        records: as in run_diag (an ens plan serves any variable count)."""
+        from . import budget, ens
         co2, yearly = self._run_arrays(years, co2_ppm)
-        out = ens.empty_products(plan, (years,), (12, 5, self.ny, self.nx))
-        _check(lib().greb_engine_run_ens(self.h, int(years), abi.fptr(co2), plan.h,
-                                         *[None if a is None else abi.fptr(a) for a in out], abi.fptr(yearly)), self.h)
-        return ens.Result(*out, yearly)
+        names = budget.record_names(records)
+        out = ens.empty_products(plan, (years,), (12, len(names), self.ny, self.nx))
+        self._reduced("ens", records, co2, plan, *[None if a is None else abi.fptr(a) for a in out], abi.fptr(yearly))
+        return ens.Result(*out, yearly, names)
 
-    def run_lin(self, years: int, co2_ppm, plan):
+    def run_lin(self, years: int, co2_ppm, plan, records="state"):
         """The scenario run of run() that hands back only the linear model of `plan` (lin.Plan) across the members, of every
         monthly record of every year: made on the device year by year (greb_engine_run_lin).  Returns a lin.Result: coef
         [n_terms][years][12][5][ny][nx] -- effects, slopes, whatever the plan's weights state -- and rss
         [years][12][5][ny][nx], the residual sum of squares of the fit (a product the plan does not select is None).
-        State, clock and yearly are those of run() over the same years."""
-        from . import lin
+        State, clock and yearly are those of run() over the same years.  records: as in run_diag (a lin plan serves any
+        variable count)."""
+        from . import budget, lin
         co2, yearly = self._run_arrays(years, co2_ppm)
-        coef, rss = lin.empty_products(plan, (years,), (12, 5, self.ny, self.nx))
-        _check(lib().greb_engine_run_lin(self.h, int(years), abi.fptr(co2), plan.h, None if coef is None else abi.fptr(coef),
-                                         None if rss is None else abi.fptr(rss), abi.fptr(yearly)), self.h)
-        return lin.Result(coef, rss, yearly)
+        names = budget.record_names(records)
+        coef, rss = lin.empty_products(plan, (years,), (12, len(names), self.ny, self.nx))
+        self._reduced("lin", records, co2, plan, None if coef is None else abi.fptr(coef), None if rss is None else abi.fptr(rss),
+                      abi.fptr(yearly))
+        return lin.Result(coef, rss, yearly, names)
 
     def state(self, member: int = 0) -> np.ndarray:
         s = np.empty((5, self.ny, self.nx), np.float32)

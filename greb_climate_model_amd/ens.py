@@ -56,6 +56,7 @@ class Result:
     max: object
     quant: object
     yearly: object = None
+    vars: tuple = None  # the names of the variables (the axis the shapes call [5]) where the run knows them
 
     @property
     def std(self):

@@ -52,6 +52,7 @@ class Result:
     coef: object
     rss: object
     yearly: object = None
+    vars: tuple = None  # the names of the variables (the axis the shapes call [5]) where the run knows them
 
 
 class Plan(_plan.Handle):

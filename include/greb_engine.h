@@ -392,6 +392,52 @@ int greb_lin_reduce_dev(greb_lin* l, int device, const float* x_dev, size_t n, f
  * engine is left in and the kernels that integrate are those of greb_engine_run over the same years, bit for bit. */
 int greb_engine_run_lin(greb_engine* e, int years, const float* co2_ppm, greb_lin* l, float* coef, float* rss, float* yearly);
 
+/* ---- budget output through the plans: flux terms and their sums, reduced on the device --------------
+ * The four plans above read a model year as [n_members][12][n_vars][ny][nx]; with n_vars = 5 that is a year of state
+ * records.  The thirteen flux terms of greb_engine_run_budget exist only in the step loop and, in full, leave the device as
+ * [n_members][years][12][13][ny][nx] -- which a many-member run cannot hold.  Here a year's budget records are reduced by
+ * the same plans where they lie, either the thirteen terms themselves or up to GREB_MAX_RECORD_VARS linear combinations of
+ * them (the surface net flux, the atmospheric net flux, evaporation plus rain: the right-hand sides of src/greb.f90:258,
+ * :260, :263), formed BEFORE the reduction so that variances, ranges, quantiles and residuals are those of the sum. */
+#define GREB_MAX_RECORD_VARS 16
+/* greb_diag_create / greb_clim_create for records of n_vars variables per month, 1 ... GREB_MAX_RECORD_VARS (the two above
+ * are these with n_vars = 5): every shape that says [5] above reads [n_vars] (seasons: [5 seasons][n_vars]), the arithmetic
+ * and the order of every sum are the same.  The _dev calls take the count from the plan.  n_vars out of range is
+ * GREB_E_INVALID with a message that names the value, decided on the host before any device query. */
+int greb_diag_create_vars(int nx, int ny, const float* region_w, int n_regions, int n_vars, greb_diag** out);
+int greb_clim_create_vars(int nx, int ny, int n_members, const int32_t* control, unsigned what, int n_vars, greb_clim** out);
+/* The combination stage (greb_fluxes.hip): budget_year_dev [n_members][12][GREB_NBUDGET][np] -> out_dev
+ * [n_members][12][n_out][np], np = ny * nx a multiple of four, both device pointers, 16-byte aligned and not overlapping;
+ * combo[n_out][GREB_NBUDGET] is fp32 in HOST memory and travels by value in the kernel arguments.  Per element and output
+ * k, over the terms j in ascending order, skipping those with combo[k][j] == 0: the first term used gives
+ * acc = combo[k][j] * b_j, every later one acc = acc + combo[k][j] * b_j -- an fp32 multiply, then an fp32 add, never
+ * fused.  A row with a single coefficient 1 copies the term's bits (-0.0 included).  Launches on the current device on
+ * `stream` (a hipStream_t, may be NULL) and does not synchronise.  GREB_E_INVALID, with a message that names row and term:
+ * n_out outside 1 ... GREB_MAX_RECORD_VARS, a row of zeros, a coefficient that is not finite.  Arguments are checked before
+ * any device query; without a device: GREB_E_NOGPU (no CPU path). */
+int greb_budget_combine_dev(const float* combo, int n_out, const float* budget_year_dev, int n_members, size_t np,
+                            float* out_dev, void* stream);
+/* greb_engine_run_diag / _clim / _ens / _lin over the year's BUDGET records instead of its state records: V variables per
+ * month, V = GREB_NBUDGET with combo == NULL (the thirteen terms themselves; the combination stage does not run), else
+ * V = n_out and the variables are the rows of combo.  Output shapes, delivery and device memory are those of the state
+ * driver of the same name with 5 replaced by V: nothing on the device grows with `years` beyond what that driver keeps.
+ * The year is integrated by the budget variant of the step kernels, as in greb_engine_run_budget (the five state records go
+ * to a staging slot nobody reads); co2_ppm, yearly, the model clock and the state the engine is left in are those of
+ * greb_engine_run over the same years, bit for bit, and switches, member forcing and boundary sets act as they do in
+ * greb_engine_run_budget.  These calls, greb_engine_run and greb_engine_run_budget may alternate freely.
+ * GREB_E_INVALID, decided before any device work and leaving the engine as it was: a diag or clim plan whose n_vars is not
+ * V (the message names both numbers; likewise greb_engine_run_diag / greb_engine_run_clim with a plan whose n_vars is not
+ * 5), a bad combo (as above), and whatever the state driver of the same name rejects. */
+int greb_engine_run_budget_diag(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_diag* d,
+                                unsigned what, float* regions, float* zonal, float* annual, float* yearly);
+int greb_engine_run_budget_clim(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_clim* c,
+                                int n_periods, const int32_t* first_year, const int32_t* n_years, float* mean, float* seasons,
+                                float* trend, float* mean_resp, float* seasons_resp, float* yearly);
+int greb_engine_run_budget_ens(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_ens* s,
+                               float* mean, float* var, float* min, float* max, float* quant, float* yearly);
+int greb_engine_run_budget_lin(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_lin* l,
+                               float* coef, float* rss, float* yearly);
+
 /* ---- per-member forcing: regional and seasonal CO2, insolation tables and scale --------------------
  * Members of one engine may differ in the forcing itself, not only in the CO2 level: CO2 raised in one hemisphere, over
  * land or ocean only or in one half of the year, a changed solar constant, a changed latitudinal or seasonal distribution
