@@ -21,6 +21,7 @@ S_MEAN, S_VAR, S_RANGE, S_QUANTILES = 1, 2, 4, 8  # ensemble-output products, GR
 ENS_MAX_GROUPS, ENS_MAX_PROBS, ENS_MAX_SORTED = 64, 16, 4096  # GREB_ENS_MAX_*
 L_COEF, L_RSS = 1, 2  # linear-model products, GREB_L_* of include/greb_engine.h
 LIN_MAX_TERMS = 64    # GREB_LIN_MAX_TERMS
+GRAM_MAX_BLOCKS, GRAM_MAX_USED = 16, 1024  # GREB_GRAM_MAX_*: blocks of records and used members of a covariance plan
 # the names of the switches, GREB_X_* of include/greb_engine.h, bit 0 first
 X_NAMES = ("GREB_X_NO_ICE", "GREB_X_NO_HYDRO", "GREB_X_NO_DEEP_OCEAN", "GREB_X_LW_LINEAR_VAPOR", "GREB_X_NO_CIRCULATION",
            "GREB_X_NO_VAPOR_TRANSPORT", "GREB_X_VAPOR_DIFFUSION_ONLY", "GREB_X_SST_PLUS1")
@@ -146,6 +147,19 @@ def lin_prototypes(lib) -> None:
     lib.greb_lin_reduce_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, vp, vp]
     lib.greb_engine_run_lin.argtypes = [vp, C.c_int, c_float_p, vp, c_float_p, c_float_p, c_float_p]
     for f in (lib.greb_lin_create, lib.greb_lin_destroy, lib.greb_lin_reduce_dev, lib.greb_engine_run_lin):
+        f.restype = C.c_int
+
+
+def gram_prototypes(lib) -> None:
+    """The argument types of greb_gram_* and of the two runs that deliver Gram matrices (doubles)."""
+    i32p, f64p, vp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_void_p
+    lib.greb_gram_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, i32p, C.c_int, i32p, i32p, c_float_p, C.POINTER(vp)]
+    lib.greb_gram_destroy.argtypes = [vp]
+    lib.greb_gram_reduce_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, vp]
+    lib.greb_engine_run_gram.argtypes = [vp, C.c_int, c_float_p, vp, f64p, c_float_p]
+    lib.greb_engine_run_budget_gram.argtypes = [vp, C.c_int, c_float_p, c_float_p, C.c_int, vp, f64p, c_float_p]
+    for f in (lib.greb_gram_create, lib.greb_gram_destroy, lib.greb_gram_reduce_dev, lib.greb_engine_run_gram,
+              lib.greb_engine_run_budget_gram):
         f.restype = C.c_int
 
 

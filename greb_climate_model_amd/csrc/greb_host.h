@@ -72,6 +72,7 @@ struct greb_engine {
   float* clim_out = nullptr; size_t clim_out_cap = 0; // run_clim: the products of two periods (one per output slot)
   float* ens_out = nullptr; size_t ens_out_cap = 0;   // run_ens: the group statistics of two years (one per output slot)
   float* lin_out = nullptr; size_t lin_out_cap = 0;   // run_lin: the coefficients and the residual map of two years (likewise)
+  double* gram_out = nullptr; size_t gram_out_cap = 0; // run_gram: the matrices of two years (likewise), in doubles
   // host copies needed later
   std::vector<greb::RowTables> h_tabs;
   std::vector<int> h_tab_index;

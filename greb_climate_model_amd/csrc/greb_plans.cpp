@@ -1,4 +1,4 @@
-// greb_plans.cpp -- the output plans (greb_diag, greb_clim, greb_ens, greb_lin): their _dev entry points and their scenario-run sinks.
+// greb_plans.cpp -- the output plans (greb_diag, greb_clim, greb_ens, greb_lin, greb_gram): their _dev entry points and their scenario-run sinks.
 // A plan is host data only; what it needs on a device is made the first time it works there (PerDevice).
 #include "greb_host.h"
 
@@ -10,11 +10,13 @@
 #include "greb_clim.h"
 #include "greb_ens.h"
 #include "greb_lin.h"
+#include "greb_gram.h"
 #include "greb_fluxes.h"
 
 using namespace greb;
 using namespace greb::host;
 
+static_assert(kGramMaxUsed == GREB_GRAM_MAX_USED && kGramMaxBlocks == GREB_GRAM_MAX_BLOCKS, "greb_gram.h mirrors include/greb_engine.h");
 static_assert(kFluxTerms == GREB_NBUDGET && kFluxMaxOut == GREB_MAX_RECORD_VARS, "greb_fluxes.h mirrors include/greb_engine.h");
 
 namespace {
@@ -993,6 +995,200 @@ int greb_engine_run_budget_lin(greb_engine* e, int years, const float* co2_ppm, 
   Records src;
   if (int rc = src.init(e, "run_budget_lin", true, combo, n_out)) return rc;
   return run_lin("run_budget_lin", src, e, years, co2_ppm, l, coef, rss, yearly);
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- covariance output (greb_gram.hip)
+// Grid, member count, record count and: the USED members in ascending member index (member[k], control[k]); the records
+// that enter a matrix, sorted by block and ascending inside each (record[q], offs[b] ... offs[b + 1] - 1 those of block
+// b); the scale map.  Per device: the lists' copy (one allocation: member, control, record, offs), the scale's, and the
+// scratch array of the per-record matrices.
+struct greb_gram {
+  int nx = 0, ny = 0, nm = 0, nrec = 0, nb = 0;
+  bool has_control = false;
+  std::vector<int> member, control, record, offs;
+  std::vector<float> scale; // [ny][nx], or empty: none
+  struct Dev { DevBuf<int> lists; DevBuf<float> scale; DevBuf<double> partial; };
+  PerDevice<Dev> devs;
+  size_t used() const { return member.size(); }
+  size_t matrix() const { return (size_t)nb * used() * used(); } // doubles of one call's output
+};
+
+namespace {
+int gram_on_device(greb_gram* g, int device, GramTables* out) {
+  greb_gram::Dev* dv = nullptr;
+  auto make = [g](greb_gram::Dev& n) -> int {
+    std::vector<int> lists(g->member);
+    lists.insert(lists.end(), g->control.begin(), g->control.end());
+    lists.insert(lists.end(), g->record.begin(), g->record.end());
+    lists.insert(lists.end(), g->offs.begin(), g->offs.end());
+    HIP_TRY(nullptr, n.lists.upload(lists.data(), lists.size()));
+    if (!g->scale.empty()) HIP_TRY(nullptr, n.scale.upload(g->scale.data(), g->scale.size()));
+    HIP_TRY(nullptr, n.partial.alloc(g->record.size() * g->used() * g->used()));
+    return 0;
+  };
+  if (int rc = g->devs.get(device, make, &dv)) return rc;
+  const size_t used = g->used(), ctl = g->control.size();
+  int* const base = dv->lists.get();
+  out->member = base;
+  out->control = g->has_control ? base + used : nullptr;
+  out->record = base + used + ctl;
+  out->offs = base + used + ctl + g->record.size();
+  out->scale = dv->scale.get();
+  out->partial = dv->partial.get();
+  out->n_used = (int)used; out->n_listed = (int)g->record.size(); out->n_blocks = g->nb; out->n_records = g->nrec;
+  return 0;
+}
+
+int check_gram_len(greb_engine* e, const std::string& who, const greb_gram* g, size_t len) {
+  if (len < 1) return fail(e, GREB_E_INVALID, who + ": len = 0");
+  if (!g->scale.empty() && len != (size_t)g->nx * g->ny)
+    return fail(e, GREB_E_INVALID, who + ": len = " + std::to_string(len) + ", but the plan has a scale map of ny * nx = " +
+                                       std::to_string((size_t)g->nx * g->ny) + " elements");
+  return 0;
+}
+} // namespace
+
+extern "C" {
+
+int greb_gram_create(int nx, int ny, int n_members, int n_records, const int32_t* block, int n_blocks, const int32_t* use,
+                     const int32_t* control, const float* scale, greb_gram** out) {
+  if (!out) return fail(nullptr, GREB_E_INVALID, "gram_create: `out` is NULL");
+  *out = nullptr;
+  if (int rc = check_grid("gram_create", nx, ny)) return rc;
+  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "gram_create: n_members = " + std::to_string(n_members));
+  if (n_records < 1) return fail(nullptr, GREB_E_INVALID, "gram_create: n_records = " + std::to_string(n_records));
+  if (n_blocks < 1 || n_blocks > kGramMaxBlocks)
+    return fail(nullptr, GREB_E_INVALID, "gram_create: n_blocks = " + std::to_string(n_blocks) + " (1 ... " +
+                                             std::to_string(kGramMaxBlocks) + ")");
+  if (!block) return fail(nullptr, GREB_E_INVALID, "gram_create: `block` is NULL");
+  std::vector<int> count((size_t)n_blocks, 0);
+  for (int r = 0; r < n_records; ++r) {
+    if (block[r] < -1 || block[r] >= n_blocks)
+      return fail(nullptr, GREB_E_INVALID, "gram_create: record " + std::to_string(r) + ": block = " + std::to_string(block[r]) +
+                                               " (-1 = none, or 0 ... " + std::to_string(n_blocks - 1) + ")");
+    if (block[r] >= 0) ++count[(size_t)block[r]];
+  }
+  for (int b = 0; b < n_blocks; ++b)
+    if (count[(size_t)b] == 0) return fail(nullptr, GREB_E_INVALID, "gram_create: block " + std::to_string(b) + " is empty");
+  int n_used = 0;
+  for (int m = 0; m < n_members; ++m) {
+    if (control && (control[m] < -1 || control[m] >= n_members))
+      return fail(nullptr, GREB_E_INVALID, "gram_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
+                                               " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
+    if (use && !use[m]) continue;
+    if (control && control[m] < 0)
+      return fail(nullptr, GREB_E_INVALID, "gram_create: member " + std::to_string(m) +
+                                               " is used but has no control (control = -1) while a control map is given");
+    ++n_used;
+  }
+  if (n_used == 0) return fail(nullptr, GREB_E_INVALID, "gram_create: no used member (`use` is zero everywhere)");
+  if (n_used > kGramMaxUsed)
+    return fail(nullptr, GREB_E_UNSUPPORTED, "gram_create: " + std::to_string(n_used) + " used members (at most " +
+                                                 std::to_string(kGramMaxUsed) + ")");
+  const size_t np = (size_t)nx * ny;
+  for (size_t i = 0; scale && i < np; ++i)
+    if (!(scale[i] >= 0.f && std::isfinite(scale[i]))) { // (a NaN fails the comparison)
+      char buf[160];
+      std::snprintf(buf, sizeof(buf), "gram_create: scale %g at row %zu, column %zu is negative or not finite", (double)scale[i],
+                    i / (size_t)nx, i % (size_t)nx);
+      return fail(nullptr, GREB_E_INVALID, buf);
+    }
+  greb_gram* g = new (std::nothrow) greb_gram();
+  if (!g) return fail(nullptr, GREB_E_INVALID, "out of host memory");
+  g->nx = nx; g->ny = ny; g->nm = n_members; g->nrec = n_records; g->nb = n_blocks; g->has_control = control != nullptr;
+  for (int m = 0; m < n_members; ++m) { // ascending member index
+    if (use && !use[m]) continue;
+    g->member.push_back(m);
+    if (control) g->control.push_back(control[m]);
+  }
+  g->offs.assign((size_t)n_blocks + 1, 0);
+  for (int b = 0; b < n_blocks; ++b) {
+    for (int r = 0; r < n_records; ++r) // ascending record inside the block
+      if (block[r] == b) g->record.push_back(r);
+    g->offs[(size_t)b + 1] = (int)g->record.size();
+  }
+  if (scale) g->scale.assign(scale, scale + np);
+  *out = g;
+  return 0;
+}
+
+int greb_gram_destroy(greb_gram* g) {
+  delete g; // (PerDevice waits for each device before its tables go)
+  return 0;
+}
+
+int greb_gram_reduce_dev(greb_gram* g, int device, const float* x_dev, size_t len, double* G_dev, void* stream) {
+  if (!g) return fail(nullptr, GREB_E_INVALID, "gram_reduce_dev: no plan (greb_gram is NULL)");
+  if (!x_dev) return fail(nullptr, GREB_E_INVALID, "gram_reduce_dev: x_dev is NULL");
+  if (int rc = check_aligned("gram_reduce_dev", x_dev, "x_dev")) return rc;
+  if (!G_dev) return fail(nullptr, GREB_E_INVALID, "gram_reduce_dev: G_dev is NULL");
+  if (reinterpret_cast<uintptr_t>(G_dev) & 7) return fail(nullptr, GREB_E_INVALID, "gram_reduce_dev: G_dev is not 8-byte aligned");
+  if (int rc = check_gram_len(nullptr, "gram_reduce_dev", g, len)) return rc;
+  if (int rc = use_device("gram_reduce_dev: ", device)) return rc;
+  GramTables t{};
+  if (int rc = gram_on_device(g, device, &t)) return rc;
+  HIP_TRY(nullptr, launch_gram(x_dev, len, t, G_dev, (hipStream_t)stream));
+  return 0;
+}
+
+} // extern "C"
+
+namespace {
+int run_gram(const std::string& who, Records src, greb_engine* e, int years, const float* co2_ppm, greb_gram* g, double* G,
+             float* yearly) {
+  // argument errors first, before anything touches a device: the plan, the output, then the engine
+  if (!g) return fail(e, GREB_E_INVALID, who + ": no plan (greb_gram is NULL)");
+  if (years < 1) return fail(e, GREB_E_INVALID, who + ": years = " + std::to_string(years));
+  if (g->nrec != 12 * src.nv)
+    return fail(e, GREB_E_INVALID, who + ": the plan is for n_records = " + std::to_string(g->nrec) + ", a model year of this run has 12 * " +
+                                       std::to_string(src.nv) + " = " + std::to_string(12 * src.nv));
+  if (!G) return fail(e, GREB_E_INVALID, who + ": `G` is NULL");
+  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, who + ": bad argument (engine or co2_ppm)");
+  if (int rc = check_engine(e, who, g->nx, g->ny, g->nm)) return rc;
+  const size_t len = (size_t)e->np, out = g->matrix(); // doubles of a year's matrices
+  GramTables t{};
+  // A unit is a year's matrices, made in output slot y & 1 of e->gram_out.  Nothing on the device grows with `years`
+  // (besides the yearly scalars).
+  auto slot = [&](int u) { return e->gram_out + (size_t)(u & 1) * out; };
+  RunSink sink;
+  sink.prepare = [&]() -> int {
+    if (e->gram_out_cap < 2 * out) {
+      if (e->gram_out) HIP_TRY(e, hipFree(e->gram_out));
+      e->gram_out = nullptr; e->gram_out_cap = 0;
+      HIP_TRY(e, dev_alloc(&e->gram_out, 2 * out));
+      e->gram_out_cap = 2 * out;
+    }
+    if (int rc = src.prepare(e)) return rc;
+    return gram_on_device(g, e->device, &t);
+  };
+  sink.year = [&](const YearCalls& run, int y) -> int {
+    const float* mon = nullptr;
+    if (int rc = src.integrate(e, run, y, &mon)) return rc;
+    if (int rc = run.writing(y)) return rc; // (here, not before the year: only the reduction writes the slot)
+    HIP_TRY(e, launch_gram(mon, len, t, slot(y), e->stream));
+    return run.complete(y);
+  };
+  sink.deliver = [&](int y, int sl) -> int {
+    HIP_TRY(e, hipMemcpyAsync(G + (size_t)y * out, slot(sl), out * sizeof(double), hipMemcpyDeviceToHost, e->copy_stream));
+    return 0;
+  };
+  return run_years(e, years, co2_ppm, yearly, sink);
+}
+} // namespace
+
+extern "C" {
+
+int greb_engine_run_gram(greb_engine* e, int years, const float* co2_ppm, greb_gram* g, double* G, float* yearly) {
+  return run_gram("run_gram", Records{}, e, years, co2_ppm, g, G, yearly);
+}
+
+int greb_engine_run_budget_gram(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_gram* g,
+                                double* G, float* yearly) {
+  Records src;
+  if (int rc = src.init(e, "run_budget_gram", true, combo, n_out)) return rc;
+  return run_gram("run_budget_gram", src, e, years, co2_ppm, g, G, yearly);
 }
 
 } // extern "C"

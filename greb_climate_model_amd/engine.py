@@ -48,6 +48,7 @@ def lib() -> C.CDLL:
         abi.ens_prototypes(L)
         abi.lin_prototypes(L)
         abi.budget_prototypes(L)
+        abi.gram_prototypes(L)
         _lib = L
     return _lib
 
@@ -70,7 +71,8 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_forcing_record_bytes", "greb_forcing_record_field_name", "greb_engine_get_forcing_record",
            "greb_forcing_record_field_static", "greb_forcing_record_static_floats",
            "greb_diag_create_vars", "greb_clim_create_vars", "greb_budget_combine_dev", "greb_engine_run_budget_diag",
-           "greb_engine_run_budget_clim", "greb_engine_run_budget_ens", "greb_engine_run_budget_lin"]
+           "greb_engine_run_budget_clim", "greb_engine_run_budget_ens", "greb_engine_run_budget_lin",
+           "greb_gram_create", "greb_gram_destroy", "greb_gram_reduce_dev", "greb_engine_run_gram", "greb_engine_run_budget_gram"]
 
 
 def _check(rc: int, h=None):
@@ -268,7 +270,7 @@ class Engine:
         return monthly, budget, yearly
 
     def _reduced(self, name: str, records, co2, plan, *args):
-        """Call the reduced run `name` ("diag", "clim", "ens", "lin") over `records`: "state" -- the year's five state
+        """Call the reduced run `name` ("diag", "clim", "ens", "lin", "gram") over `records`: "state" -- the year's five state
         records (greb_engine_run_<name>) --, "budget" -- its thirteen flux terms -- or a budget.Combo -- sums of them
         (greb_engine_run_budget_<name>).  `args`: what follows the plan in the C call."""
         from . import budget
@@ -345,6 +347,18 @@ class Engine:
         self._reduced("lin", records, co2, plan, None if coef is None else abi.fptr(coef), None if rss is None else abi.fptr(rss),
                       abi.fptr(yearly))
         return lin.Result(coef, rss, yearly, names)
+
+    def run_gram(self, years: int, co2_ppm, plan, records="state"):
+        """The scenario run of run() that hands back only the Gram matrices of `plan` (gram.Plan) across the members: per
+        year and block of records G[a][c] = sum v_a v_c in float64, made on the device year by year (greb_engine_run_gram).
+        Returns a gram.Result: G [years][n_blocks][U][U].  State, clock and yearly are those of run() over the same years.
+        records: as in run_diag; the plan's n_records must be 12 times that variable count."""
+        from . import budget, gram
+        co2, yearly = self._run_arrays(years, co2_ppm)
+        names = budget.record_names(records)
+        G = np.empty((years, plan.nb, plan.U, plan.U), np.float64)
+        self._reduced("gram", records, co2, plan, G.ctypes.data_as(C.POINTER(C.c_double)), abi.fptr(yearly))
+        return gram.Result(G, yearly, names)
 
     def state(self, member: int = 0) -> np.ndarray:
         s = np.empty((5, self.ny, self.nx), np.float32)

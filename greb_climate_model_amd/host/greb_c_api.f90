@@ -201,6 +201,50 @@ module greb_c_api
        real(c_float), intent(in) :: co2_ppm(*)
        real(c_float), intent(out) :: yearly(*)
      end function
+     ! covariance output (greb_gram.hip): a plan = grid, member count, n_records (12 * 5 for a model year), block(n_records)
+     ! (0-based, -1 = the record enters no matrix), n_blocks, use(n_members) (c_null_ptr: all), control(n_members) (0-based;
+     ! c_null_ptr: no control map) and scale(nx,ny) (float; c_null_ptr: none)
+     integer(c_int) function greb_gram_create(nx, ny, n_members, n_records, block, n_blocks, use, control, scale, plan) &
+          bind(C, name="greb_gram_create")
+       import :: c_int, c_int32_t, c_ptr
+       integer(c_int), value :: nx, ny, n_members, n_records, n_blocks
+       integer(c_int32_t), intent(in) :: block(*)
+       type(c_ptr), value :: use, control, scale
+       type(c_ptr), intent(out) :: plan
+     end function
+     integer(c_int) function greb_gram_destroy(plan) bind(C, name="greb_gram_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan
+     end function
+     ! device pointers (c_ptr): x_dev(len,n_records,n_members) -> G_dev(U,U,n_blocks) in double, U = the used members;
+     ! launches on `stream`, no synchronisation
+     integer(c_int) function greb_gram_reduce_dev(plan, device, x_dev, len, G_dev, stream) &
+          bind(C, name="greb_gram_reduce_dev")
+       import :: c_int, c_ptr, c_size_t
+       type(c_ptr), value :: plan, x_dev, G_dev, stream
+       integer(c_int), value :: device
+       integer(c_size_t), value :: len
+     end function
+     ! greb_engine_run that delivers only the plan's Gram matrices of every year's monthly records: G(U,U,n_blocks,years)
+     integer(c_int) function greb_engine_run_gram(eng, years, co2_ppm, plan, G, yearly) &
+          bind(C, name="greb_engine_run_gram")
+       import :: c_int, c_ptr, c_float, c_double
+       type(c_ptr), value :: eng, plan
+       integer(c_int), value :: years
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_double), intent(out) :: G(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
+     ! ... of the year's budget records: the 13 flux terms (combo = c_null_ptr) or the n_out rows of combo(13,n_out)
+     integer(c_int) function greb_engine_run_budget_gram(eng, years, co2_ppm, combo, n_out, plan, G, yearly) &
+          bind(C, name="greb_engine_run_budget_gram")
+       import :: c_int, c_ptr, c_float, c_double
+       type(c_ptr), value :: eng, combo, plan
+       integer(c_int), value :: years, n_out
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_double), intent(out) :: G(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
      ! greb_engine_run that also delivers the monthly means of the 13 flux terms of the update (GREB_B_* of greb_engine.h):
      ! budget(nx,ny,13,12,years,n_members); monthly as in greb_engine_run, or c_null_ptr for a budget-only run
      integer(c_int) function greb_engine_run_budget(eng, years, co2_ppm, monthly, budget, yearly, run_flags) &

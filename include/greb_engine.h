@@ -438,6 +438,58 @@ int greb_engine_run_budget_ens(greb_engine* e, int years, const float* co2_ppm, 
 int greb_engine_run_budget_lin(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_lin* l,
                                float* coef, float* rss, float* yearly);
 
+/* ---- covariance output: member-by-member Gram matrices, made on the device ------------------------
+ * greb_lin reduces the members by contrasts the caller already knows.  Which contrasts are worth looking at -- the leading
+ * modes of an ensemble's spread -- and how far each member's pattern lies from every other's both come from the Gram
+ * matrix across the members, G[a][c] = sum_i v_a[i] v_c[i]: its eigenvectors are weight rows for greb_lin, and
+ * G[a][a] + G[c][c] - 2 G[a][c] is the squared distance of two members.  It is the one reduction whose input is the whole
+ * member x space x time volume and whose output is small.  A plan holds the grid and n_members; n_records, the records of
+ * one member in a call (12 * n_vars for a model year); block[n_records] in -1 ... n_blocks-1 (-1: the record enters no
+ * matrix); optionally use[n_members] (as greb_lin; U = the number of used members), control[n_members] (as greb_ens and
+ * greb_lin; control[m] = m is legal and gives a row and a column of zeros) and scale[ny][nx] (fp32, finite, >= 0: e.g. the
+ * square root of the cell area).  For record r, element i < len and used member m the sample is
+ *   d = x[m][r][i]                          without a control map
+ *   d = x[m][r][i] - x[control[m]][r][i]    with one, as ONE fp32 subtraction
+ *   v = d  without `scale`,  v = fl32(scale[i] * d)  with it: one fp32 multiply (len must then be ny * nx)
+ * and the matrices are formed in fp64, a and c counting the USED members in ascending member index:
+ *   per record   P[r][a][c] = sum_i (double)v_a[i] * (double)v_c[i]   over ascending i, from +0.0, one add per element
+ *   per block    G[b][a][c] = sum_{r: block[r] = b} P[r][a][c]        over ascending r, from +0.0
+ * The product of two fp32 values is exact in fp64, so a fused multiply-add and a multiply followed by an add give the same
+ * bits: either may be used.  What the definition forbids is reassociating the adds (no fast-math).  The output is fp64,
+ * G[n_blocks][U][U], the full symmetric matrix; G[a][c] and G[c][a] carry identical bits.  (fp64 on purpose: centring
+ * H G H and distances cancel 4-5 digits at climate magnitudes.)  Every output element has one owner (no atomics): results
+ * are deterministic, a block's numbers depend neither on the other blocks nor on unused members, and a member with
+ * use[m] = 0 that is no used member's control is never read. */
+#define GREB_GRAM_MAX_BLOCKS 16
+#define GREB_GRAM_MAX_USED   1024
+typedef struct greb_gram greb_gram;
+/* A plan.  Host work only, validated without touching a device.  GREB_E_INVALID with a message that names the offender
+ * (greb_engine_last_error(NULL)): a grid greb_diag_create does not take, n_members < 1, n_records < 1, n_blocks outside
+ * 1 ... 16, `block` NULL, a block index out of range (the message names the record), an empty block, a control index out
+ * of range, a used member whose control is -1 while a control map is given, no used member, a scale that is negative or
+ * not finite (the message names row and column).  GREB_E_UNSUPPORTED: more than GREB_GRAM_MAX_USED used members.  A plan
+ * serves any number of calls and engines; its calls on one device share a scratch array (listed records x U x U doubles,
+ * made with the first call there) and must not run side by side on different streams. */
+int greb_gram_create(int nx, int ny, int n_members, int n_records, const int32_t* block, int n_blocks, const int32_t* use,
+                     const int32_t* control, const float* scale, greb_gram** out);
+int greb_gram_destroy(greb_gram* g); /* waits for the device before it frees the tables */
+/* x_dev[n_members][n_records][len] on HIP device `device` (16-byte aligned; len is arbitrary without `scale`; the products
+ * of greb_clim_finish_dev are valid input, e.g. seasons with n_records = 5 * n_vars) -> G_dev[n_blocks][U][U] doubles.
+ * Launches on `stream` (a hipStream_t, may be NULL) and does not synchronise.  Arguments are checked before any device
+ * query; without a device: GREB_E_NOGPU (no CPU path). */
+int greb_gram_reduce_dev(greb_gram* g, int device, const float* x_dev, size_t len, double* G_dev, void* stream);
+/* greb_engine_run that delivers ONLY the plan's matrices of each model year's monthly records, to host memory:
+ *   G  [years][n_blocks][U][U] doubles
+ * The plan must have n_records = 12 * 5; one made for another grid, member count or record count, or a NULL `G`, is
+ * GREB_E_INVALID, decided before any device work.  Each year is integrated into one of the engine's two one-year staging
+ * slots and reduced there into one of two device output slots, which leaves on the copy stream while the following year
+ * integrates.  Device memory does not grow with `years` (the yearly scalars aside).  co2_ppm, yearly, the model clock, the
+ * state the engine is left in and the kernels that integrate are those of greb_engine_run over the same years, bit for bit. */
+int greb_engine_run_gram(greb_engine* e, int years, const float* co2_ppm, greb_gram* g, double* G, float* yearly);
+/* ... over the year's BUDGET records, as greb_engine_run_budget_lin: the plan must have n_records = 12 * V. */
+int greb_engine_run_budget_gram(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_gram* g,
+                                double* G, float* yearly);
+
 /* ---- per-member forcing: regional and seasonal CO2, insolation tables and scale --------------------
  * Members of one engine may differ in the forcing itself, not only in the CO2 level: CO2 raised in one hemisphere, over
  * land or ocean only or in one half of the year, a changed solar constant, a changed latitudinal or seasonal distribution
