@@ -932,6 +932,10 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
   int cur = 0;
   const unsigned xsw = EXP ? member_switches(a, m) : 0u;
   const int nsub = (EXP && (xsw & kXNoCirc)) ? 0 : a.nsub;
+  // vapour diffused but not advected (orig :560-564) -- unless its transport is off altogether (:554-555 come first): the
+  // increment is then dropped in the point physics, and the sub-steps run as they do without the switch, so that Tair, which
+  // shares the FAST loop with q, has the bits it has under NO_VAPOR_TRANSPORT alone (Circ::substeps on the two loops)
+  const bool q_dif_only = EXP && (xsw & kXQDiffOnly) && !(xsw & kXNoQTransport);
   // the flux-phase CO2 (:104) may be the member's own; read here, so that the step loop reads nothing new
   const float co2_flux = FLUX ? (a.co2_flux_m ? a.co2_flux_m[m] : a.co2_flux) : 0.f;
   __syncthreads();
@@ -965,9 +969,9 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 
     // ---- circulation of Tair and q: 24 sub-steps (:543-550)
 #ifdef GREB_TUNING
-    circ.substeps(lds, cur, nsub, 0, EXP && (xsw & kXQDiffOnly), stamp, &st_busy);
+    circ.substeps(lds, cur, nsub, 0, q_dif_only, stamp, &st_busy);
 #else
-    circ.substeps(lds, cur, nsub, 0, EXP && (xsw & kXQDiffOnly));
+    circ.substeps(lds, cur, nsub, 0, q_dif_only);
 #endif
     cur ^= nsub & 1;
     GREB_STAMP(t_c);

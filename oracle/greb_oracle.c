@@ -37,7 +37,8 @@ struct greb_oracle {
   long it_scnr; /* steps done in the scenario so far */
   float year;   /* src/greb.f90:227,233 (implicitly typed REAL) */
   oracle_grid g;
-  int log_exp; /* greb.original.model.f90:60; 10 = complete model = src/greb.f90 */
+  int log_exp; /* greb.original.model.f90:60; 10 = complete model = src/greb.f90.  Kept as a record only: */
+  unsigned xsw; /* every physics branch reads one GREB_X_* bit of this word (oracle_log_exp_switches, oracle_set_switches) */
   int scenario; /* 1 inside the original's scenario loop (SST+1 applies there only, :224-226) */
   /* scratch */
   float *scr;
@@ -146,7 +147,7 @@ greb_oracle* oracle_create(const greb_params* p, int nx, int ny, const greb_fiel
     o->To[i] = o->toclim2d[i];     o->q[i] = o->qclim[last + i];
   }
   o->mon = 1; o->it_scnr = 0; o->year = (float)p->year0; /* :227 */
-  o->log_exp = 10; o->scenario = 1;
+  o->log_exp = 10; o->xsw = 0u; o->scenario = 1;
   return o;
 }
 
@@ -410,7 +411,7 @@ void oracle_swradiation(const greb_oracle* o, int ityr, const float* Ts, float* 
           a_surf = p->a_no_ice + p->da_ice * (1.f - (T - p->To_ice1) / (p->To_ice2 - p->To_ice1));
       }
       if (o->glacier[i] > 0.5f) a_surf = p->a_no_ice + p->da_ice; /* :395 */
-      if (o->log_exp <= 5) a_surf = p->a_no_ice;                  /* greb.original.model.f90:394 */
+      if (o->xsw & GREB_X_NO_ICE) a_surf = p->a_no_ice;           /* greb.original.model.f90:394 */
       albedo[i] = a_surf + a_atmos - a_surf * a_atmos;            /* :398 */
       sw[i] = sol[k] * (1.f - albedo[i]);                         /* :400 */
     }
@@ -429,13 +430,13 @@ void oracle_lwradiation(const greb_oracle* o, int ityr, const float* Ts, const f
     const float ez = expf(-o->z_topo[i] / p->z_air);
     const float e_co2 = ez * co2;              /* :420 */
     float e_vapor = ez * p->r_qviwv * q[i]; /* :421 */
-    if (o->log_exp == 11) e_vapor = ez * p->r_qviwv * o->qclim[off + i]; /* greb.original.model.f90:423 */
+    if (o->xsw & GREB_X_LW_LINEAR_VAPOR) e_vapor = ez * p->r_qviwv * o->qclim[off + i]; /* greb.original.model.f90:423 */
     const float e_cloud = o->cldclim[off + i]; /* :422 */
     float e = pe[3] * logf(pe[0] * e_co2 + pe[1] * e_vapor + pe[2]) + pe[6]
               + pe[4] * logf(pe[0] * e_co2 + pe[2])
               + pe[5] * logf(pe[1] * e_vapor + pe[2]); /* :425-427 */
     e = (pe[7] - e_cloud) / pe[8] * (e - pe[9]) + pe[9]; /* :428 */
-    if (o->log_exp == 11) e = e + 0.022f / (0.15f * 24.f) * p->r_qviwv * (q[i] - o->qclim[off + i]); /* orig :430 */
+    if (o->xsw & GREB_X_LW_LINEAR_VAPOR) e = e + 0.022f / (0.15f * 24.f) * p->r_qviwv * (q[i] - o->qclim[off + i]); /* orig :430 */
     em[i] = e;
     LWsurf[i] = -p->sig * pow4(Ts[i]);                                   /* :430 */
     const float dTrad = -0.16f * o->tclim[off + i] - 5.f;                /* :176 */
@@ -449,7 +450,7 @@ void oracle_hydro(const greb_oracle* o, int ityr, const float* Ts, const float* 
                   float* Qlat_air, float* dq_eva, float* dq_rain) {
   const greb_params* p = &o->p;
   const size_t off = (size_t)(ityr - 1) * o->np;
-  if (o->log_exp <= 6 || o->log_exp == 13 || o->log_exp == 15) { /* greb.original.model.f90:452-453 */
+  if (o->xsw & GREB_X_NO_HYDRO) { /* greb.original.model.f90:452-453 */
     for (int i = 0; i < o->np; ++i) Qlat[i] = Qlat_air[i] = dq_eva[i] = dq_rain[i] = 0.f;
     return;
   }
@@ -480,7 +481,7 @@ void oracle_seaice(greb_oracle* o, int ityr, const float* Ts) {
         o->cap_surf[i] = o->cap_land + (o->cap_ocean * mld[i] - o->cap_land)
                                            / (p->To_ice2 - p->To_ice1) * (T - p->To_ice1);
     }
-    if (o->log_exp <= 5) { /* greb.original.model.f90:492-495 */
+    if (o->xsw & GREB_X_NO_ICE) { /* greb.original.model.f90:492-495 */
       if (o->z_topo[i] > 0.f) o->cap_surf[i] = o->cap_land;
       if (o->z_topo[i] < 0.f) o->cap_surf[i] = o->cap_ocean * mld[i];
     }
@@ -495,7 +496,7 @@ void oracle_deep_ocean(const greb_oracle* o, int ityr, const float* Ts, const fl
   const float* mld = o->mldclim + (size_t)(ityr - 1) * o->np;
   const float* mldm = o->mldclim + (size_t)(ityr > 1 ? ityr - 2 : NT - 1) * o->np; /* :507-508 */
   const float dt = (float)p->dt;
-  if (o->log_exp <= 9 || o->log_exp == 11 || (o->log_exp >= 14 && o->log_exp <= 16)) { /* orig :513-515 */
+  if (o->xsw & GREB_X_NO_DEEP_OCEAN) { /* orig :513-515 */
     for (int i = 0; i < o->np; ++i) dT_ocean[i] = dTo[i] = 0.f;
     return;
   }
@@ -536,12 +537,13 @@ static void tendencies(greb_oracle* o, int ityr, float co2, const tend_t* t) {
   oracle_lwradiation(o, ityr, o->Ts, o->Ta, o->q, co2, t->LW_surf, t->LWair_up, t->LWair_down, t->em); /* :293 */
   for (int i = 0; i < o->np; ++i) t->Q_sens[i] = o->p.ct_sens * (o->Ta[i] - o->Ts[i]);    /* :295 */
   oracle_hydro(o, ityr, o->Ts, o->q, t->Q_lat, t->Q_lat_air, t->dq_eva, t->dq_rain);     /* :297 */
-  /* greb.original.model.f90:553-571.  Where the original returns before assigning dX_crcl (log_exp <= 4; the
+  /* greb.original.model.f90:553-571, one switch bit per condition; the original's if / else-if order is the precedence
+   * NO_CIRCULATION > NO_VAPOR_TRANSPORT > VAPOR_DIFFUSION_ONLY.  Where the original returns before assigning dX_crcl (log_exp <= 4; the
    * vapour call at 7 and 16) its intent(out) result is undefined; defined here as no transport (0). */
-  if (o->log_exp <= 4) memset(t->dTa_crcl, 0, sizeof(float) * o->np);
+  if (o->xsw & GREB_X_NO_CIRCULATION) memset(t->dTa_crcl, 0, sizeof(float) * o->np);
   else oracle_circulation(o, ityr, o->Ta, t->dTa_crcl, o->wz_air);                        /* :301 */
-  if (o->log_exp <= 4 || o->log_exp == 7 || o->log_exp == 16) memset(t->dq_crcl, 0, sizeof(float) * o->np);
-  else if (o->log_exp == 8) oracle_diffusion_only(o, o->q, t->dq_crcl, o->wz_vapor);     /* orig :560-564 */
+  if (o->xsw & (GREB_X_NO_CIRCULATION | GREB_X_NO_VAPOR_TRANSPORT)) memset(t->dq_crcl, 0, sizeof(float) * o->np);
+  else if (o->xsw & GREB_X_VAPOR_DIFFUSION_ONLY) oracle_diffusion_only(o, o->q, t->dq_crcl, o->wz_vapor);     /* orig :560-564 */
   else oracle_circulation(o, ityr, o->q, t->dq_crcl, o->wz_vapor);                        /* :303 */
   oracle_deep_ocean(o, ityr, o->Ts, o->To, t->dT_ocean, t->dTo);                          /* :306 */
 }
@@ -640,7 +642,7 @@ void oracle_run(greb_oracle* o, int years, const float* co2_ppm, float* monthly,
     const int jday = (int)(((it - 1) / 2) % 365) + 1; /* :251 */
     const int ityr = (int)((it - 1) % NT) + 1;        /* :252 */
     const size_t off = (size_t)(ityr - 1) * np;
-    if (o->scenario && o->log_exp >= 14 && o->log_exp <= 16) {
+    if (o->scenario && (o->xsw & GREB_X_SST_PLUS1)) {
       /* sens. exp. SST+1, greb.original.model.f90:226 (CO2 = CO2_ctrl: the caller's series).  The statement sits
        * BEFORE time_loop updates the module variable ityr (:247), so it reads the climatology slice of the
        * PREVIOUS step -- slice 730 at it = 1, left there by the preceding phase. */
@@ -673,12 +675,32 @@ void oracle_run(greb_oracle* o, int years, const float* co2_ppm, float* monthly,
  * log_exp sensitivity experiments of the upstream model variant.
  * All citations in this block are into /root/reference/src/greb.original.model.f90.
  * ---------------------------------------------------------------------------------------- */
+/* Which process each log_exp value switches off: the original's own conditions, one GREB_X_* bit each.  The table
+ * repeats greb_log_exp_switches of the engine (the oracle links nothing of the product). */
+unsigned oracle_log_exp_switches(int le) {
+  unsigned x = 0;
+  if (le <= 5) x |= GREB_X_NO_ICE;                                              /* :394, :492-495 */
+  if (le <= 6 || le == 13 || le == 15) x |= GREB_X_NO_HYDRO;                    /* :452-453 */
+  if (le <= 9 || le == 11 || (le >= 14 && le <= 16)) x |= GREB_X_NO_DEEP_OCEAN; /* :513-515 */
+  if (le == 11) x |= GREB_X_LW_LINEAR_VAPOR;                                    /* :423, :430 */
+  if (le <= 4) x |= GREB_X_NO_CIRCULATION;                                      /* :553 */
+  if (le == 7 || le == 16) x |= GREB_X_NO_VAPOR_TRANSPORT;                      /* :554-555 */
+  if (le == 8) x |= GREB_X_VAPOR_DIFFUSION_ONLY;                                /* :560 */
+  if (le >= 14 && le <= 16) x |= GREB_X_SST_PLUS1;                              /* :226 */
+  return x;
+}
+
+/* An arbitrary combination of the process switches: sets the word and touches nothing else (no input field, no state,
+ * not log_exp), so it may be called at any point -- before the flux-correction year, or between it and the run. */
+void oracle_set_switches(greb_oracle* o, unsigned xsw) { o->xsw = xsw & 0xffu; }
+
 /* greb_model preamble :162-197: boundary-data changes of the experiment, then the derived fields that are
  * computed after them (cap_surf, initial q, wz_*).  z_ocean (:155-160) and Toclim (shell) keep their values
  * from the unmodified data.  Call once, right after oracle_create. */
 void oracle_set_log_exp(greb_oracle* o, int log_exp) {
   const size_t np = (size_t)o->np, n3 = np * NT;
   o->log_exp = log_exp;
+  o->xsw = oracle_log_exp_switches(log_exp);
   if (log_exp == 1) for (size_t i = 0; i < np; ++i) if (o->z_topo[i] > 1.f) o->z_topo[i] = 1.0f; /* :162 */
   if (log_exp <= 2) for (size_t i = 0; i < n3; ++i) o->cldclim[i] = 0.7f;                          /* :163 */
   if (log_exp <= 3) for (size_t i = 0; i < n3; ++i) o->qclim[i] = 0.0052f;                         /* :164 */

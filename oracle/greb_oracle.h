@@ -67,6 +67,13 @@ void oracle_run(greb_oracle* o, int years, const float* co2_ppm, float* monthly,
  * log_exp 10 (default) is the complete model == src/greb.f90.  Where the original reads an unassigned
  * intent(out) circulation increment (log_exp <= 4; vapour at 7 and 16) the oracle defines it as 0. */
 void oracle_set_log_exp(greb_oracle* o, int log_exp);                   /* once, right after oracle_create */
+/* The process half of an experiment as a word of GREB_X_* bits (include/greb_engine.h): every physics branch of the oracle
+ * tests one bit of it.  oracle_create leaves 0 (the complete model); oracle_set_log_exp derives it from log_exp through
+ * oracle_log_exp_switches (the table of greb_log_exp_switches, repeated); oracle_set_switches sets ANY of the 256 words
+ * and changes nothing else, at any point between the phases.  Transport precedence, as the original's if / else-if:
+ * NO_CIRCULATION > NO_VAPOR_TRANSPORT > VAPOR_DIFFUSION_ONLY.  SST_PLUS1 acts only in a run begun as a scenario. */
+unsigned oracle_log_exp_switches(int log_exp);
+void oracle_set_switches(greb_oracle* o, unsigned xsw);
 void oracle_begin_run(greb_oracle* o, const float* state4, float year_start, int is_scenario); /* control / scenario loop start */
 float oracle_co2_level(int log_exp, float year);
 void oracle_set_co2_flux(greb_oracle* o, float co2); /* CO2_ctrl, :178-179 */

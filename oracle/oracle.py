@@ -165,6 +165,17 @@ class Oracle:
     def set_log_exp(self, log_exp: int):
         self.lib.oracle_set_log_exp(self.h, int(log_exp))
 
+    def log_exp_switches(self, log_exp: int) -> int:
+        """The GREB_X_* word of experiment `log_exp` (the oracle's own repeat of greb_log_exp_switches)."""
+        self.lib.oracle_log_exp_switches.restype = C.c_uint
+        return int(self.lib.oracle_log_exp_switches(int(log_exp)))
+
+    def set_switches(self, word: int):
+        """Any of the 256 switch words; sets nothing else (callable between flux_correction and run)."""
+        if word & ~0xff:
+            raise ValueError(f"unknown switch bits in {word:#x}")
+        self.lib.oracle_set_switches(self.h, C.c_uint(int(word)))
+
     def begin_run(self, state4=None, year_start: float = 1940.0, scenario: bool = True):
         s4 = None if state4 is None else np.ascontiguousarray(state4, np.float32)
         self.lib.oracle_begin_run(self.h, None if s4 is None else fp(s4), C.c_float(year_start), int(scenario))

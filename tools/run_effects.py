@@ -14,8 +14,10 @@ the same years, forms the same numbers on the host with lin.reference and checks
 Engine.run and Engine.run_ens (GREB_S_MEAN of all members) in the same process, the three legs alternating.
 --bits MASK: the factorial of the switches in MASK only (default 0xff, all eight).  The 32 members that combine
 GREB_X_LW_LINEAR_VAPOR and GREB_X_NO_CIRCULATION with the hydrology left on run away in the second scenario year at
-2 x CO2 (NaN in their records, from Engine.run as from here), and a contrast over all members is NaN wherever one of its
-members is: `non_finite_values` counts them, and --bits 0xf7 (without the linearised vapour feedback: 128 members, 29
+2 x CO2 (NaN in their records, from Engine.run as from here).  That is the model's behaviour under LW_LINEAR_VAPOR without
+circulation and with hydrology, not the port's: the oracle, asked for the same switch word, is finite in year 1 and non-finite
+from year 2 as well (tests/test_switch_words_cpu.py, tests/test_gpu_switch_words.py).  A contrast over all members is NaN
+wherever one of its members is: `non_finite_values` counts them, and --bits 0xf7 (without the linearised vapour feedback: 128 members, 29
 terms) gives finite effects everywhere.  Where records are NaN the comparison of --compare asks for NaN on both sides
 (an operation that makes a NaN gives it another sign bit on the host than on the device), for equal bits elsewhere.
 --kernel-timing times, on a year of synthetic records of the same ensemble, the two launches of this plan beside
