@@ -143,6 +143,17 @@ int greb_member_deal_cover(int strict, int* counts) {
   return 0;
 }
 
+int greb_member_lds_table(int strict, int* records, int capacity) {
+  if (capacity < 0 || (capacity > 0 && !records)) return fail(nullptr, GREB_E_INVALID, "member_lds_table: bad argument");
+  return member_lds_table(strict != 0, records, capacity);
+}
+
+int greb_member_lds_map(int* words8) {
+  if (!words8) return fail(nullptr, GREB_E_INVALID, "member_lds_map: bad argument");
+  member_lds_map(words8);
+  return 0;
+}
+
 int greb_substep_launch_order(const greb_params* p, int nx, int ny, int n_members, const float* kappa, int* field, int* k0,
                               int* k1, int capacity) {
   if (!p || !grid_ok(nx, ny) || n_members < 1 || capacity < 0 || (capacity > 0 && (!field || !k0 || !k1)))

@@ -195,6 +195,10 @@ auto pick_variant(bool strict, unsigned v) { return pick_variant<Family>(strict,
 bool member_layout_supported(const RowTables& tab, int nx, int ny);
 // how often the member kernel's static deal computes each row-quad of the 96x48 grid: counts[48 * 24]
 void member_deal_cover(bool strict, int* counts);
+// the LDS accesses of the bulk waves in one sub-step (greb_member.hip): records of 7 ints, at most `capacity` written;
+// returns the number of records there are
+int member_lds_table(bool strict, int* out, int capacity);
+void member_lds_map(int* words8);
 hipError_t launch_member_kernel(const MemberArgs& a, int n_members, bool strict, hipStream_t s);
 // the forcing record (kFrBytes at `rec`) of the set whose thirteen device arrays `b` names (greb_member.hip)
 hipError_t launch_pack_forcing(const BoundarySet& b, float* rec, hipStream_t s);

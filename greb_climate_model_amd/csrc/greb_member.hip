@@ -28,7 +28,9 @@
 //   (rows 1-9, 38-46: sub-cycled formulas, one sweep) and the "full" family (rows 10-37).  A PASS is 64 tasks of
 //   one kind, one per lane; 3 passes of sub row-pairs, 3 of full row-pairs, 1 + 4.5 of single rows, in both arithmetic
 //   modes; dealt statically to the seven (STRICT: six) bulk waves (see "The schedule") with each lane's task addresses
-//   computed once per circulation call.
+//   computed once per circulation call.  Which (row, quad) a lane of a pass holds follows the LDS's lane groups -- for a
+//   ds_read_b128 the 16 lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32, not 16 consecutive lanes --
+//   so that the reads of a group fall on different banks (see RS and task_rowquad).
 //   polar rows 0 / 47 (8 dependent Jacobi sweeps per diffusion call, src/greb.f90:656-717): FAST -- ONE wave, each
 //   DPP row of 16 lanes x 6 longitudes one (pole, tracer) chain, neighbours by row rotates (quad_chain_substep);
 //   STRICT -- one wave per pole, 48 lanes x 2 longitudes x (Tair,q), neighbours by ds_bpermute (chain_substep).
@@ -45,12 +47,20 @@ namespace greb {
 constexpr int NX = 96, NY = 48, NQ = 24, NP = 4608;
 constexpr int kThreads = 512;
 // floats per interleaved row: 2*NX = 192 data + 16 of padding, i.e. a row stride of 52 sixteen-byte slots = 4 mod 16.
-// A ds_read_b128 is served in groups of 16 lanes that must hit 16 different slot classes (slot mod 16) to take one
-// LDS cycle.  With the unpadded stride (48 slots = 0 mod 16) every row started in the same class and the lanes of a
-// pass, which span two to three rows, collided two-way on every read (42 % of the LDS cycles of the round-1 kernel
-// were bank conflicts); with 4 mod 16, rows two apart -- the neighbouring row pairs of a pass -- are offset by 8
-// classes and the 16 lanes of every group fall on distinct classes.  (The 9.6 KB this costs are those of the polar
-// chains' former Jacobi row buffers plus the slack: the chains exchange their halos by ds_bpermute now.)
+// A ds_read_b128 is served in four groups of 16 lanes, which are NOT consecutive lanes: {0-3, 12-15, 20-27},
+// {4-11, 16-19, 28-31} and the same two + 32; a ds_write_b128 in eight groups of 8 consecutive lanes.  The bank of a
+// dword is its address mod 64 (stores: mod 32), so the 16 lanes of a read group take one LDS cycle when their slots fall
+// into 16 different slot classes (slot mod 16), the 8 of a store group when theirs differ mod 8; every further slot of a
+// class costs the group a cycle.  With the unpadded stride (48 slots = 0 mod 16) every row started in the same class
+// (42 % of the LDS cycles of the round-1 kernel were bank conflicts); with 4 mod 16, rows 2 mod 4 apart are offset by 8
+// classes, and 8 consecutive quads of one row and of the other fill the 16 classes.  What the layout guarantees today
+// (task_rowquad deals the lanes of a pass to these groups; tools/lds_conflicts.py counts it from the kernel's own
+// tables, tests/test_member_lds_model_cpu.py holds it): every ds_read_b128 of X and W in the sub-step loop -- column,
+// left and right quads, the seam between quads 23 and 0 included -- and every store is conflict-free; of the wind reads
+// (WX, WY: row stride 24 slots = 8 mod 16, no padding) those of a third of the read groups are 2-way: 1 760 modelled
+// cycles per sub-step against 1 716 conflict-free, where the row-major enumeration took 2 080.  (The 9.6 KB the padding
+// costs are those of the polar chains' former Jacobi row buffers plus the slack: the chains exchange their halos by
+// ds_bpermute now.)
 constexpr int RS = 2 * NX + 16;
 // LDS map, in floats
 // X buffers and W carry one all-zero GUARD row below row 0 and above row NY-1: the rows k-2 .. k+2 of any bulk
@@ -318,6 +328,12 @@ struct Pass { int kind, index; };
 //     S0+F0 S2+F1 T1+F3 T2+H+F2 | S1    T0    C     F4      4 664
 //     S0    S2+F1 T1+F3 T2+H+F2 | S1    T0    C     F0+F4   4 889
 //     S0+F0 S2+F1 T1+F3+F2 T2+H | S1    T0    C     F4      5 089
+// With the tasks dealt to the LDS's lane groups (task_rowquad; profiles/r08_member_lds_groups_stamps.txt) every pass got
+// shorter and the busiest waves of the four SIMDs moved from 4 221 4 315 4 109 3 931 to 4 128 4 040 4 044 3 900; the table stays:
+//     S0+F0 S2+F1 T1+F3 T2+H    | S1    T0    C     F2+F4   4 428   <- the table below (busy 3 417 3 492 2 941 3 191 | 4 128 4 040 4 044 3 900)
+//     S0+F0 S2+F1 T1+F3 T2+F2   | S1    T0    C     H+F4    4 449
+//     S0+F0 S2+F1 T1+F3 T2+H+F2 | S1    T0    C     F4      4 515
+//     S0    S2+F1 T1+F3 T2+H+F2 | S1    T0    C     F0+F4   4 710
 __host__ __device__ constexpr Pass deal_fast(int wave, int i) {
   constexpr Pass none{kNone, 0};
 #if defined(GREB_TUNING) && defined(GREB_DEAL_FAST) // tools/deal_search.py: a deal given on the compiler command line
@@ -364,25 +380,77 @@ __host__ __device__ constexpr bool is_polar_wave(int wave) { return STRICT ? (wa
 // the first row and the quad of task t (= 64 * pass index + lane) of a kind; valid = 0: no such task
 struct RowQuad { int k, q, valid; };
 __host__ __device__ constexpr int task_rows(int kind) { return kind == kST || kind == kFT ? 2 : (kind == kS1 || kind == kF1 ? 1 : 0); }
-__host__ __device__ constexpr RowQuad task_rowquad(int kind, int t) {
-  int k = 1, q = 0, valid = 0;
-  const int r = t / NQ;
-  q = t % NQ;
-  // row order: consecutive r of a pass sit two rows (= 8 slot classes) apart wherever the rows allow it
-  if (kind == kST) { valid = r < 8; k = r < 4 ? 1 + 2 * r : (r == 4 ? 41 : (r == 5 ? 39 : (r == 6 ? 45 : 43))); }
-  else if (kind == kFT) { valid = r < 8; k = 10 + 2 * r; }
-  else if (kind == kS1) { valid = r < 2; k = r == 0 ? 9 : 38; if (r == 1) q = (q + 4) % NQ; }
-  else if (kind == kF1) { valid = r < 12; k = r < 6 ? 26 + 2 * r : 27 + 2 * (r - 6); }
-  if (!valid) { k = 1; q = 0; }
-  return RowQuad{k, q, valid};
+__host__ __device__ constexpr int kind_tasks(int kind) {
+  return kind == kST || kind == kFT ? 8 * NQ : (kind == kS1 ? 2 * NQ : (kind == kF1 ? 12 * NQ : 0));
 }
-
+// The enumeration follows the lane groups of the LDS (see RS).  A SEGMENT is 8 cyclically consecutive quads of a row, from
+// quad q0 on: 8 slot classes in a row, shifted as a whole by the reads of the left / right quads unless the shift crosses
+// the seam between quads 23 and 0 (24 = 8 mod 16 moves the quads beyond the seam by 8 classes).  A row is cut at
+// q0 = rot, rot + 8, rot + 16 with rot = 1 (even rows) or 5 (odd rows): only the third segment holds the seam, and every
+// segment starts in slot class 1 mod 8 (a pair task's second row: 5 mod 8).  A read group of 16 lanes holds two segments
+// whose classes are 8 apart:
+//   the first two segments of ONE row -- conflict-free in the column, left, right and wind reads;
+//   the third segments of two rows that are 2 mod 4 apart (same q0, so the seam shifts both alike) -- conflict-free in the
+//   X and W reads; in WX / WY (row stride 24 slots = 8 mod 16) these two rows start in the same class, a 2-way conflict
+//   on 2 of a row task's reads in a third of the groups, which is what tools/lds_conflicts.py still counts.
+// The 32 lanes of a half wave are the chunks c = 0 .. 7 of 4 lanes; read group 0 is {c0, c3, c5, c6}, read group 1
+// {c1, c2, c4, c7} (the parity of c's bits), a store group two neighbouring chunks.  Chunk c holds the quads 4 (c & 1) ..
+// + 3 of segment (c >> 1) & 1 of its read group, so a store group is the first half of one segment and the second half of
+// another: 8 different classes mod 8.
+// The rows of a kind in pairs 2 mod 4 apart: groups 3p, 3p + 1 are the two rows' own, 3p + 2 their third segments.
+// S1 (rows 9 and 38, 1 mod 4 apart): the two third segments have a read group each, in lanes 32 .. 47.
+struct Segment { int k, q0; };
+__host__ __device__ constexpr int seg_rot(int k) { return 1 + 4 * (k & 1); }
+__host__ __device__ constexpr Segment task_segment(int kind, int group, int member) {
+  if (kind == kS1) {
+    const int k = group == 0 || group == 3 ? 38 : 9;
+    return Segment{k, seg_rot(k) + (group >= 2 ? 16 : 8 * member)};
+  }
+  const int p = group / 3, g = group % 3;
+  int a = 1;
+  if (kind == kST) a = p < 2 ? 1 + 4 * p : 31 + 4 * p;             // (1,3) (5,7) (39,41) (43,45)
+  else if (kind == kFT) a = 10 + 4 * p;                            // (10,12) .. (22,24)
+  else if (kind == kF1) a = 26 + 4 * (p >> 1) + (p & 1);           // (26,28) (27,29) (30,32) .. (35,37)
+  const int k = g == 0 ? a : (g == 1 ? a + 2 : a + 2 * member);
+  return Segment{k, seg_rot(k) + (g == 2 ? 16 : 8 * member)};
+}
 // number of passes of a kind, and of tasks of one of its passes: 64 = every lane has one
 __host__ __device__ constexpr int kind_passes(int kind) { return kind == kST || kind == kFT ? 3 : (kind == kS1 ? 1 : (kind == kF1 ? 5 : 0)); }
 __host__ __device__ constexpr int pass_tasks(int kind, int index) {
-  const int total = kind == kST || kind == kFT ? 8 * NQ : (kind == kS1 ? 2 * NQ : (kind == kF1 ? 12 * NQ : 0));
-  const int left = total - 64 * index;
+  const int left = kind_tasks(kind) - 64 * index;
   return left >= 64 ? 64 : (left > 0 ? left : 0);
+}
+// The eight segments of a pass, a byte each for the row and for q0: segment s = 4 (half wave) + 2 (read group) + member.
+// make_tasks gets them as two 64-bit literals and a lane finds its own with a shift: the enumeration costs the once-per-step
+// setup no more instructions than the division by 24 of the row-major one did.
+struct PassSegments { unsigned long long k, q0; };
+__host__ __device__ constexpr PassSegments pass_segments(int kind, int index) {
+  PassSegments p{0, 0};
+  for (int s = 0; s < 8; ++s) {
+    const int group = 4 * index + (s >> 1);
+    const Segment g = 32 * (group >> 1) < kind_tasks(kind) ? task_segment(kind, group, s & 1) : Segment{1, 0};
+    p.k |= (unsigned long long)g.k << (8 * s);
+    p.q0 |= (unsigned long long)g.q0 << (8 * s);
+  }
+  return p;
+}
+// (the task of lane 0 .. 63, whether or not a short pass has one for it)
+__host__ __device__ constexpr RowQuad lane_rowquad(const PassSegments& p, int lane) {
+  const int s = ((lane >> 5) << 2) | ((((lane >> 2) ^ (lane >> 3) ^ (lane >> 4)) & 1) << 1) | ((lane >> 3) & 1);
+  const int k = (int)(p.k >> (8 * s)) & 255, q = ((int)(p.q0 >> (8 * s)) & 255) + (lane & 7);
+  return RowQuad{k, q >= NQ ? q - NQ : q, 1};
+}
+__host__ __device__ constexpr RowQuad task_rowquad(int kind, int t) {
+  if (t < 0 || t >= kind_tasks(kind)) return RowQuad{1, 0, 0};
+#if defined(GREB_TUNING) && defined(GREB_TASKS_ROW_MAJOR) // tools/lds_conflicts.py: the row-major enumeration this one replaced
+  const int r = t / NQ, q = t % NQ;
+  if (kind == kST) return RowQuad{r < 4 ? 1 + 2 * r : (r == 4 ? 41 : (r == 5 ? 39 : (r == 6 ? 45 : 43))), q, 1};
+  if (kind == kFT) return RowQuad{10 + 2 * r, q, 1};
+  if (kind == kS1) return RowQuad{r == 0 ? 9 : 38, r == 0 ? q : (q + 4) % NQ, 1};
+  return RowQuad{r < 6 ? 26 + 2 * r : 27 + 2 * (r - 6), q, 1};
+#else
+  return lane_rowquad(pass_segments(kind, t / 64), t % 64);
+#endif
 }
 
 // How often the deal computes each row-quad: every lane's task of every dealt pass, counted by the rows it writes.
@@ -424,23 +492,90 @@ void member_deal_cover(bool strict, int* counts) {
   for (int i = 0; i < NY * NQ; ++i) counts[i] = strict ? cs.n[i] : cf.n[i];
 }
 
+// the addresses of a task (make_tasks, and the table below)
+__host__ __device__ constexpr TaskAddr task_addr(const RowQuad& rq) {
+  const int k = rq.k, q = rq.q;
+  return TaskAddr{k * RS + 4 * q, k * RS + 4 * (q == 0 ? NQ - 1 : q - 1), k * RS + 4 * (q == NQ - 1 ? 0 : q + 1),
+                  rq.valid ? (k | (q << 8)) : -1};
+}
+
+// The LDS traffic of the bulk waves in one sub-step, for tools/lds_conflicts.py (greb_member_lds_table): one record of
+// kLdsRecInts ints per lane of every LDS instruction of every dealt pass -- wave, the wave's pass slot, the instruction's
+// number within the pass, lane, kind of access (kLds*), bytes per lane, float offset into the workgroup's LDS or -1 for a
+// lane without a task.  The offsets are those of row_task / row_task2 reading buffer 0 and storing to buffer 1, from the
+// deal, the enumeration and the LDS map above; the chain wave(s) of the polar rows are not in it.
+enum { kLdsCol = 0, kLdsSide = 1, kLdsWind = 2, kLdsStore = 3, kLdsConst = 4, kLdsRecInts = 7 };
+// ... and the map they point into: the row stride and where X[0], X[1], W (each with its two guard rows), WX, WY and the
+// row constants begin and the last ends, in floats
+void member_lds_map(int* words8) {
+  const int m[8] = {RS, 0, XB, 2 * XB, kOffWX, kOffWY, kOffRowK, kLdsFloats};
+  for (int i = 0; i < 8; ++i) words8[i] = m[i];
+}
+int member_lds_table(bool strict, int* out, int capacity) {
+  int n = 0;
+  for (int w = 0; w < 8; ++w)
+    for (int i = 0; i < 3; ++i) {
+      const Pass p = strict ? deal_strict(w, i) : deal_fast(w, i);
+      const int rows = task_rows(p.kind);
+      if (rows == 0) continue;
+      int instr = 0;
+      // one instruction: lane -> ta.c / ta.l / ta.r (which = 0 / 1 / 2) + off, or a wind / constant address of row k + j
+      auto emit = [&](int kind, int bytes, int base, int which, int off, int j) {
+        for (int lane = 0; lane < 64; ++lane, ++n) {
+          if (n >= capacity) continue;
+          const RowQuad rq = task_rowquad(p.kind, 64 * p.index + lane);
+          const TaskAddr ta = task_addr(rq);
+          const int k = (ta.kq & 255) + j, q = ta.kq >> 8;
+          int a = base + off + (which == 0 ? ta.c : (which == 1 ? ta.l : ta.r));
+          if (kind == kLdsWind) a = base + k * NX + 4 * q;
+          if (kind == kLdsConst) a = base + k * kRowKWords + off;
+          const int rec[kLdsRecInts] = {w, i, instr, lane, kind, bytes, rq.valid ? a : -1};
+          for (int x = 0; x < kLdsRecInts; ++x) out[(size_t)n * kLdsRecInts + x] = rec[x];
+        }
+        ++instr;
+      };
+      auto pairquad = [&](int kind, int base, int which, int off) { // ld8p / st8p: two 16-byte accesses
+        emit(kind, 16, base, which, off, 0);
+        emit(kind, 16, base, which, off + kHalfRow, 0);
+      };
+      for (int base : {kOffX, kOffW}) // the column: rows k-2 .. k+2 (two stacked rows: .. k+3)
+        for (int j = -2; j <= 1 + rows; ++j) pairquad(kLdsCol, base, 0, j * RS);
+      for (int j = 0; j < rows; ++j) {
+        for (int base : {kOffX, kOffW}) { pairquad(kLdsSide, base, 1, j * RS); pairquad(kLdsSide, base, 2, j * RS); }
+        emit(kLdsWind, 16, kOffWX, 0, 0, j);
+        emit(kLdsWind, 16, kOffWY, 0, 0, j);
+        if (strict) { emit(kLdsConst, 16, kOffRowK, 0, 0, j); emit(kLdsConst, 16, kOffRowK, 0, 4, j); } // row_consts
+        else emit(kLdsConst, 4, kOffRowK, 0, kRowKCsDif, j);                                             // task_consts
+        pairquad(kLdsStore, kOffX + XB, 0, j * RS);
+      }
+    }
+  return n;
+}
+
 // once per launch; the asm makes the values opaque, so the compiler keeps them instead of re-deriving them from
 // the lane id inside the sub-step loop
-template <bool STRICT>
-__device__ __forceinline__ BulkTasks make_tasks(int wave, int lane) {
+template <bool STRICT, int WAVE>
+__device__ __forceinline__ BulkTasks make_tasks(int lane) {
+  __builtin_assume(lane >= 0 && lane < 64);
   BulkTasks b;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const RowQuad rq = task_rowquad(deal<STRICT>(wave, i).kind, deal<STRICT>(wave, i).index * 64 + lane);
-    const int k = rq.k, q = rq.q, valid = rq.valid;
-    TaskAddr a;
-    a.c = k * RS + 4 * q;
-    a.l = k * RS + 4 * (q == 0 ? NQ - 1 : q - 1);
-    a.r = k * RS + 4 * (q == NQ - 1 ? 0 : q + 1);
-    a.kq = valid ? (k | (q << 8)) : -1;
+  static_for<3>([&](auto I) {
+    constexpr int i = I;
+    constexpr Pass p = deal<STRICT>(WAVE, i);
+#if defined(GREB_TUNING) && defined(GREB_TASKS_ROW_MAJOR)
+    const RowQuad rq = task_rowquad(p.kind, p.index * 64 + lane);
+#else
+    constexpr PassSegments ps = pass_segments(p.kind, p.index);
+    constexpr int ntask = pass_tasks(p.kind, p.index);
+    RowQuad rq{1, 0, 0};
+    if constexpr (ntask > 0) {
+      rq = lane_rowquad(ps, lane);
+      if (ntask < 64 && lane >= ntask) rq = RowQuad{1, 0, 0};
+    }
+#endif
+    TaskAddr a = task_addr(rq);
     asm volatile("" : "+v"(a.c), "+v"(a.l), "+v"(a.r), "+v"(a.kq));
     b.t[i] = a;
-  }
+  });
   return b;
 }
 
@@ -795,7 +930,7 @@ struct Circ {
     BulkTasks tasks;
     BulkSigns signs;
     QuadChain quad;
-    if constexpr (!kPolar) tasks = make_tasks<STRICT>(WAVE, lane);
+    if constexpr (!kPolar) tasks = make_tasks<STRICT, WAVE>(lane);
     else if constexpr (!STRICT) quad_chain_setup(lds, cur, lane, calm_q, quad);
     if constexpr (!kPolar && !STRICT) make_signs<WAVE>(lds, tasks, signs);
     // FAST bulk waves: dif_ccy, the one row constant that is the same in every row, as a scalar for the whole call

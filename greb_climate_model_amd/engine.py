@@ -62,7 +62,7 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_substep_launch_order", "greb_circulation_launch_plan", "greb_engine_describe",
            "greb_engine_create_members", "greb_engine_set_member_experiments", "greb_diag_create", "greb_diag_destroy",
            "greb_diag_reduce_dev", "greb_engine_run_diag", "greb_engine_run_budget", "greb_budget_name",
-           "greb_member_deal_cover", "greb_engine_set_forcing_tables", "greb_engine_set_member_forcing",
+           "greb_member_deal_cover", "greb_member_lds_table", "greb_member_lds_map", "greb_engine_set_forcing_tables", "greb_engine_set_member_forcing",
            "greb_engine_add_boundary_set", "greb_engine_set_member_boundary", "greb_step_variant", "greb_step_variants",
            "greb_clim_create", "greb_clim_destroy", "greb_clim_add_year_dev", "greb_clim_finish_dev", "greb_engine_run_clim",
            "greb_ens_create", "greb_ens_destroy", "greb_ens_reduce_dev", "greb_engine_run_ens",
@@ -544,6 +544,29 @@ def member_deal_cover(strict=False):
     (48, 24) (include/greb_engine.h: greb_member_deal_cover)."""
     out = np.zeros((48, 24), np.int32)
     _check(lib().greb_member_deal_cover(int(bool(strict)), out.ctypes.data_as(C.POINTER(C.c_int))))
+    return out
+
+
+LDS_KINDS = ("column", "side", "wind", "store", "const")
+
+
+def member_lds_map():
+    """greb_member_lds_map as a dict: RS (row stride) and the float offsets at which X0, X1, W, WX, WY, ROWK begin; END."""
+    w = (C.c_int * 8)()
+    _check(lib().greb_member_lds_map(w))
+    return dict(zip(("RS", "X0", "X1", "W", "WX", "WY", "ROWK", "END"), (int(x) for x in w)))
+
+
+def member_lds_table(strict=False):
+    """Host-only diagnostic: the LDS accesses of the bulk waves in one sub-step of the fused 96x48 member kernel, int array
+    (n, 7): wave, pass slot, instruction, lane, kind (index into LDS_KINDS), bytes per lane, float offset or -1
+    (include/greb_engine.h: greb_member_lds_table); member_lds_map() says where the arrays lie."""
+    f = lib().greb_member_lds_table
+    n = f(int(bool(strict)), None, 0)
+    if n < 0:
+        _check(n)
+    out = np.zeros((n, 7), np.int32)
+    assert f(int(bool(strict)), out.ctypes.data_as(C.POINTER(C.c_int)), n) == n
     return out
 
 

@@ -660,6 +660,19 @@ int greb_circulation_launch_plan(const greb_params* p, int nx, int ny, int n_mem
  * Returns 0, < 0 on a bad argument. */
 int greb_member_deal_cover(int strict, int* counts);
 
+/* Diagnostic, host only (no GPU call): the LDS accesses of one circulation sub-step of the fused 96x48 member kernel's bulk
+ * waves, FAST (strict = 0) or STRICT, made from the kernel's own deal, task enumeration and LDS map (tools/lds_conflicts.py
+ * applies the LDS's lane groups and bank rule to them).  One record of 7 ints per lane of every LDS instruction of every
+ * dealt pass: wave, pass slot of the wave, number of the instruction within the pass, lane, kind (0 column read, 1 left /
+ * right quad read, 2 wind read, 3 store, 4 row-constant read), bytes per lane, float offset into the workgroup's LDS
+ * (-1: the lane has no task in this pass).  The wave(s) of the polar rows are not listed.  At most `capacity` records are
+ * written (records may be NULL with capacity 0); returns the number of records there are, or < 0 on a bad argument. */
+int greb_member_lds_table(int strict, int* records, int capacity);
+/* The LDS map those offsets point into, 8 ints in floats: the stride of a row of X and W; where X[0], X[1] and W begin (each
+ * 50 rows: 48 and a zero guard row on either side), where the winds WX and WY (48 x 96 each) and the row constants begin,
+ * and where the last ends (the kernel's LDS size).  Returns 0, < 0 on a bad argument. */
+int greb_member_lds_map(int* words8);
+
 /* ---- forcing records (diagnostic) -------------------------------------------------------------------
  * The FAST fused 96x48 member kernel reads the boundary data of the point physics from one packed, read-only record per
  * boundary set, made on the device when the set's data is uploaded, in two parts: the static fields [row 0..47][field][96]
