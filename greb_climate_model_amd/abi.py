@@ -163,6 +163,32 @@ def gram_prototypes(lib) -> None:
         f.restype = C.c_int
 
 
+T_FIRST, T_LAST, T_STAY, T_COUNT, T_PEAK, T_FRACTION = 1, 2, 4, 8, 16, 32  # crossing products, GREB_T_* of include/greb_engine.h
+CROSS_MAX_EVENTS = 16  # GREB_CROSS_MAX_EVENTS
+
+
+class GrebCrossEvent(C.Structure):
+    """struct greb_cross_event: variable, selector (0 ... 11 a month, 12 ... 16 DJF MAM JJA SON ANN), member minus control,
+    direction (+1: q >= thr hits, -1: q <= thr) and threshold."""
+    _fields_ = [("var", C.c_int32), ("sel", C.c_int32), ("rel", C.c_int32), ("dir", C.c_int32), ("thr", C.c_float)]
+
+
+def cross_prototypes(lib) -> None:
+    """The argument types of greb_cross_* and of the two runs that deliver crossing maps (int32 and float arrays)."""
+    i32p, vp = C.POINTER(C.c_int32), C.c_void_p
+    maps = [i32p, i32p, i32p, i32p, c_float_p, i32p]  # first, last, stay, count, peak, peak_year
+    lib.greb_cross_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GrebCrossEvent), C.c_int, i32p, i32p, C.c_int,
+                                      C.c_uint, C.POINTER(vp)]
+    lib.greb_cross_destroy.argtypes = [vp]
+    lib.greb_cross_add_year_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
+    lib.greb_cross_finish_dev.argtypes = [vp, C.c_int, C.c_int] + [vp] * 7
+    lib.greb_engine_run_cross.argtypes = [vp, C.c_int, c_float_p, vp] + maps + [c_float_p, c_float_p]
+    lib.greb_engine_run_budget_cross.argtypes = [vp, C.c_int, c_float_p, c_float_p, C.c_int, vp] + maps + [c_float_p, c_float_p]
+    for f in (lib.greb_cross_create, lib.greb_cross_destroy, lib.greb_cross_add_year_dev, lib.greb_cross_finish_dev,
+              lib.greb_engine_run_cross, lib.greb_engine_run_budget_cross):
+        f.restype = C.c_int
+
+
 MAX_RECORD_VARS = 16  # GREB_MAX_RECORD_VARS: variables per month of the records a diag or clim plan reduces
 
 

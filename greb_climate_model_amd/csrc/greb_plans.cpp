@@ -1,7 +1,8 @@
-// greb_plans.cpp -- the output plans (greb_diag, greb_clim, greb_ens, greb_lin, greb_gram): their _dev entry points and their scenario-run sinks.
+// greb_plans.cpp -- the output plans (greb_diag, greb_clim, greb_ens, greb_lin, greb_gram, greb_cross): their _dev entry points and their scenario-run sinks.
 // A plan is host data only; what it needs on a device is made the first time it works there (PerDevice).
 #include "greb_host.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <new>
@@ -11,12 +12,14 @@
 #include "greb_ens.h"
 #include "greb_lin.h"
 #include "greb_gram.h"
+#include "greb_cross.h"
 #include "greb_fluxes.h"
 
 using namespace greb;
 using namespace greb::host;
 
 static_assert(kGramMaxUsed == GREB_GRAM_MAX_USED && kGramMaxBlocks == GREB_GRAM_MAX_BLOCKS, "greb_gram.h mirrors include/greb_engine.h");
+static_assert(kCrossMaxEvents == GREB_CROSS_MAX_EVENTS && sizeof(greb_cross_event) == 20, "greb_cross.h mirrors include/greb_engine.h");
 static_assert(kFluxTerms == GREB_NBUDGET && kFluxMaxOut == GREB_MAX_RECORD_VARS, "greb_fluxes.h mirrors include/greb_engine.h");
 
 namespace {
@@ -1189,6 +1192,292 @@ int greb_engine_run_budget_gram(greb_engine* e, int years, const float* co2_ppm,
   Records src;
   if (int rc = src.init(e, "run_budget_gram", true, combo, n_out)) return rc;
   return run_gram("run_budget_gram", src, e, years, co2_ppm, g, G, yearly);
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- crossing output (greb_cross.hip)
+// Grid, member count, variable count, the events in the caller's order and as the update kernel walks them (CrossTable:
+// sorted by variable, then selector), each member's control, the group lists (group g is member[offs[g] ... offs[g + 1]) in
+// ascending member index) and the products.  Per device: the state words the products need, the hit bytes and the two
+// output slots of FRACTION, and the lists' copy (one allocation: control, offs, member).  `added` counts the years since the
+// last finish: one period is followed at a time, on one device.
+struct greb_cross {
+  int nx = 0, ny = 0, nm = 0, nv = 0, ne = 0, ng = 0;
+  unsigned what = 0;
+  CrossTable table{};
+  std::vector<int> control, offs, member;
+  int added = 0, added_device = -1;
+  struct Dev { DevBuf<int> first, last, last_miss, count, peak_year, lists; DevBuf<float> peak, frac_out; DevBuf<unsigned char> hit; };
+  PerDevice<Dev> devs;
+  size_t np() const { return (size_t)nx * ny; }
+  size_t elems() const { return (size_t)nm * ne * np(); }    // one state word, one map
+  size_t fraction() const { return (size_t)ng * ne * np(); } // floats of a year's FRACTION
+};
+
+namespace {
+constexpr unsigned kCrossAll = GREB_T_FIRST | GREB_T_LAST | GREB_T_STAY | GREB_T_COUNT | GREB_T_PEAK | GREB_T_FRACTION;
+
+int cross_on_device(greb_cross* c, int device, greb_cross::Dev** out) {
+  return c->devs.get(device, [c](greb_cross::Dev& n) -> int {
+    const size_t el = c->elems();
+    if (c->what & GREB_T_FIRST) HIP_TRY(nullptr, n.first.alloc(el));
+    if (c->what & GREB_T_LAST) HIP_TRY(nullptr, n.last.alloc(el));
+    if (c->what & GREB_T_STAY) HIP_TRY(nullptr, n.last_miss.alloc(el));
+    if (c->what & GREB_T_COUNT) HIP_TRY(nullptr, n.count.alloc(el));
+    if (c->what & GREB_T_PEAK) { HIP_TRY(nullptr, n.peak.alloc(el)); HIP_TRY(nullptr, n.peak_year.alloc(el)); }
+    if (c->what & GREB_T_FRACTION) { HIP_TRY(nullptr, n.hit.alloc(el)); HIP_TRY(nullptr, n.frac_out.alloc(2 * c->fraction())); }
+    std::vector<int> lists(c->control);
+    lists.insert(lists.end(), c->offs.begin(), c->offs.end());
+    lists.insert(lists.end(), c->member.begin(), c->member.end());
+    if (!lists.empty()) HIP_TRY(nullptr, n.lists.upload(lists.data(), lists.size()));
+    return 0;
+  }, out);
+}
+const int* cross_control(const greb_cross* c, const greb_cross::Dev* dv) { return c->control.empty() ? nullptr : dv->lists.get(); }
+const int* cross_offs(const greb_cross* c, const greb_cross::Dev* dv) { return dv->lists.get() + c->control.size(); }
+
+CrossState cross_state(const greb_cross::Dev* dv) {
+  return CrossState{dv->first.get(), dv->last.get(), dv->last_miss.get(), dv->count.get(), dv->peak_year.get(), dv->peak.get(), dv->hit.get()};
+}
+
+// year k of x into the state and, with FRACTION, the year's exceedance probabilities into `fraction`
+int cross_launch_year(greb_engine* e, const greb_cross* c, const greb_cross::Dev* dv, const float* x, int k, float* fraction,
+                      hipStream_t stream) {
+  CrossUpdateArgs a{};
+  a.x = x; a.control = cross_control(c, dv); a.st = cross_state(dv); a.np = c->np();
+  a.n_members = c->nm; a.n_vars = c->nv; a.n_events = c->ne; a.k = k; a.t = c->table;
+  HIP_TRY(e, launch_cross_update(a, stream));
+  if (c->what & GREB_T_FRACTION)
+    HIP_TRY(e, launch_cross_fraction(dv->hit.get(), cross_offs(c, dv), cross_offs(c, dv) + c->offs.size(), c->ng, c->nm, c->ne, c->np(),
+                                     fraction, stream));
+  return 0;
+}
+
+// the six maps: their parameters' names, what selects each, and whether the caller gave every selected one
+const char* const kCrossOutNames[6] = {"first", "last", "stay", "count", "peak", "peak_year"};
+const char* const kCrossFlagNames[6] = {"GREB_T_FIRST", "GREB_T_LAST", "GREB_T_STAY", "GREB_T_COUNT", "GREB_T_PEAK", "GREB_T_PEAK"};
+const unsigned kCrossFlags[6] = {GREB_T_FIRST, GREB_T_LAST, GREB_T_STAY, GREB_T_COUNT, GREB_T_PEAK, GREB_T_PEAK};
+int check_cross_maps(greb_engine* e, const std::string& who, const greb_cross* c, void* p[6], const char* suffix, bool aligned) {
+  for (int i = 0; i < 6; ++i) {
+    if (!(c->what & kCrossFlags[i])) { p[i] = nullptr; continue; }
+    if (!p[i]) return fail(e, GREB_E_INVALID, who + ": " + kCrossFlagNames[i] + " selected but `" + kCrossOutNames[i] + suffix + "` is NULL");
+    if (aligned) if (int rc = check_aligned(who, p[i], std::string(kCrossOutNames[i]) + suffix)) return rc;
+  }
+  return 0;
+}
+} // namespace
+
+extern "C" {
+
+int greb_cross_create(int nx, int ny, int n_members, int n_vars, const greb_cross_event* events, int n_events, const int32_t* control,
+                      const int32_t* group, int n_groups, unsigned what, greb_cross** out) {
+  if (!out) return fail(nullptr, GREB_E_INVALID, "cross_create: `out` is NULL");
+  *out = nullptr;
+  if (int rc = check_grid("cross_create", nx, ny)) return rc;
+  if (int rc = check_n_vars("cross_create", n_vars)) return rc;
+  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "cross_create: n_members = " + std::to_string(n_members));
+  if (int rc = check_what(nullptr, "cross_create", what, kCrossAll)) return rc;
+  if (n_events < 1 || n_events > GREB_CROSS_MAX_EVENTS || !events)
+    return fail(nullptr, GREB_E_INVALID, "cross_create: n_events = " + std::to_string(n_events) + (events ? "" : " and `events` NULL") +
+                                             " (1 ... " + std::to_string(GREB_CROSS_MAX_EVENTS) + ")");
+  for (int i = 0; i < n_events; ++i) {
+    const greb_cross_event& ev = events[i];
+    const std::string who = "cross_create: event " + std::to_string(i) + ": ";
+    if (ev.var < 0 || ev.var >= n_vars)
+      return fail(nullptr, GREB_E_INVALID, who + "var = " + std::to_string(ev.var) + " (0 ... " + std::to_string(n_vars - 1) + ")");
+    if (ev.sel < 0 || ev.sel >= kCrossSelectors)
+      return fail(nullptr, GREB_E_INVALID, who + "sel = " + std::to_string(ev.sel) + " (0 ... 11: a month; 12 ... 16: DJF, MAM, JJA, SON, ANN)");
+    if (ev.rel != 0 && ev.rel != 1) return fail(nullptr, GREB_E_INVALID, who + "rel = " + std::to_string(ev.rel) + " (0 or 1)");
+    if (ev.rel && !control) return fail(nullptr, GREB_E_INVALID, who + "rel = 1 (member minus its control) but `control` is NULL");
+    if (ev.dir != 1 && ev.dir != -1) return fail(nullptr, GREB_E_INVALID, who + "dir = " + std::to_string(ev.dir) + " (+1: q >= thr, -1: q <= thr)");
+    if (!std::isfinite(ev.thr)) {
+      char buf[64];
+      std::snprintf(buf, sizeof(buf), "thr = %g is not finite", (double)ev.thr);
+      return fail(nullptr, GREB_E_INVALID, who + buf);
+    }
+  }
+  if (control)
+    for (int m = 0; m < n_members; ++m)
+      if (control[m] < -1 || control[m] >= n_members)
+        return fail(nullptr, GREB_E_INVALID, "cross_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
+                                                 " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
+  if ((what & GREB_T_FRACTION) && !group)
+    return fail(nullptr, GREB_E_INVALID, "cross_create: GREB_T_FRACTION selected but `group` is NULL (it is the share of a group's members)");
+  std::vector<int> count;
+  if (group) {
+    if (n_groups < 1 || n_groups > GREB_ENS_MAX_GROUPS)
+      return fail(nullptr, GREB_E_INVALID, "cross_create: n_groups = " + std::to_string(n_groups) + " (1 ... " +
+                                               std::to_string(GREB_ENS_MAX_GROUPS) + ")");
+    count.assign((size_t)n_groups, 0);
+    for (int m = 0; m < n_members; ++m) {
+      if (group[m] < -1 || group[m] >= n_groups)
+        return fail(nullptr, GREB_E_INVALID, "cross_create: member " + std::to_string(m) + ": group = " + std::to_string(group[m]) +
+                                                 " (-1 = none, or 0 ... " + std::to_string(n_groups - 1) + ")");
+      if (group[m] >= 0) ++count[(size_t)group[m]];
+    }
+    for (int g = 0; g < n_groups; ++g)
+      if (count[(size_t)g] == 0) return fail(nullptr, GREB_E_INVALID, "cross_create: group " + std::to_string(g) + " is empty");
+  }
+  greb_cross* c = new (std::nothrow) greb_cross();
+  if (!c) return fail(nullptr, GREB_E_INVALID, "out of host memory");
+  c->nx = nx; c->ny = ny; c->nm = n_members; c->nv = n_vars; c->ne = n_events; c->what = what;
+  if (control) c->control.assign(control, control + n_members);
+  if (group) {
+    c->ng = n_groups;
+    c->offs.assign((size_t)n_groups + 1, 0);
+    for (int g = 0; g < n_groups; ++g) c->offs[(size_t)g + 1] = c->offs[(size_t)g] + count[(size_t)g];
+    c->member.resize((size_t)c->offs[(size_t)n_groups]);
+    std::vector<int> at(c->offs.begin(), c->offs.end() - 1);
+    for (int m = 0; m < n_members; ++m) // ascending member index inside every group
+      if (group[m] >= 0) c->member[(size_t)at[(size_t)group[m]]++] = m;
+  }
+  // the events by variable, then selector (the caller's order among equals); what each variable's events read
+  std::vector<int> order((size_t)n_events);
+  for (int i = 0; i < n_events; ++i) order[(size_t)i] = i;
+  std::stable_sort(order.begin(), order.end(), [events](int a, int b) {
+    return events[a].var != events[b].var ? events[a].var < events[b].var : events[a].sel < events[b].sel;
+  });
+  CrossTable& t = c->table;
+  int v = -1;
+  for (int i = 0; i < n_events; ++i) {
+    const greb_cross_event& ev = events[order[(size_t)i]];
+    t.ev[i] = CrossTable::Ev{ev.sel, ev.rel, ev.dir, ev.thr, order[(size_t)i]};
+    if (v < 0 || t.var[v] != ev.var) { ++v; t.var[v] = ev.var; t.vstart[v] = i; }
+    static constexpr int kSeasonMonths[5] = {0x803, 0x01c, 0x0e0, 0x700, 0xfff}; // DJF MAM JJA SON ANN, bit mo
+    const int months = ev.sel < 12 ? 1 << ev.sel : kSeasonMonths[ev.sel - 12];
+    t.months[v] |= months;
+    if (ev.rel) { t.ctl_months[v] |= months; t.rel_sels[v] |= 1 << ev.sel; }
+  }
+  t.n_vars_used = v + 1;
+  t.vstart[t.n_vars_used] = n_events;
+  *out = c;
+  return 0;
+}
+
+int greb_cross_destroy(greb_cross* c) {
+  delete c; // (PerDevice waits for each device before its state goes)
+  return 0;
+}
+
+int greb_cross_add_year_dev(greb_cross* c, int device, const float* x_dev, int k, float* fraction_dev, void* stream) {
+  if (!c) return fail(nullptr, GREB_E_INVALID, "cross_add_year_dev: no plan (greb_cross is NULL)");
+  if (!x_dev) return fail(nullptr, GREB_E_INVALID, "cross_add_year_dev: x_dev is NULL");
+  if (int rc = check_aligned("cross_add_year_dev", x_dev, "x_dev")) return rc;
+  if (c->what & GREB_T_FRACTION) {
+    if (!fraction_dev) return fail(nullptr, GREB_E_INVALID, "cross_add_year_dev: GREB_T_FRACTION selected but `fraction_dev` is NULL");
+    if (int rc = check_aligned("cross_add_year_dev", fraction_dev, "fraction_dev")) return rc;
+  }
+  if (k != c->added)
+    return fail(nullptr, GREB_E_INVALID, "cross_add_year_dev: k = " + std::to_string(k) + ", but " + std::to_string(c->added) +
+                                             " years were added since the last finish (years go in ascending order, k = 0 first)");
+  if (k > 0 && device != c->added_device)
+    return fail(nullptr, GREB_E_INVALID, "cross_add_year_dev: device " + std::to_string(device) + ", but this period's state is on device " +
+                                             std::to_string(c->added_device));
+  if (int rc = use_device("cross_add_year_dev: ", device)) return rc;
+  greb_cross::Dev* dv = nullptr;
+  if (int rc = cross_on_device(c, device, &dv)) return rc;
+  if (int rc = cross_launch_year(nullptr, c, dv, x_dev, k, fraction_dev, (hipStream_t)stream)) return rc;
+  c->added = k + 1; c->added_device = device;
+  return 0;
+}
+
+int greb_cross_finish_dev(greb_cross* c, int device, int n_years, int32_t* first_dev, int32_t* last_dev, int32_t* stay_dev,
+                          int32_t* count_dev, float* peak_dev, int32_t* peak_year_dev, void* stream) {
+  if (!c) return fail(nullptr, GREB_E_INVALID, "cross_finish_dev: no plan (greb_cross is NULL)");
+  void* out[6] = {first_dev, last_dev, stay_dev, count_dev, peak_dev, peak_year_dev};
+  if (int rc = check_cross_maps(nullptr, "cross_finish_dev", c, out, "_dev", true)) return rc;
+  if (n_years != c->added || n_years < 1)
+    return fail(nullptr, GREB_E_INVALID, "cross_finish_dev: n_years = " + std::to_string(n_years) + ", but " + std::to_string(c->added) +
+                                             " years were added since the last finish");
+  if (device != c->added_device)
+    return fail(nullptr, GREB_E_INVALID, "cross_finish_dev: device " + std::to_string(device) + ", but this period's state is on device " +
+                                             std::to_string(c->added_device));
+  if (int rc = use_device("cross_finish_dev: ", device)) return rc;
+  greb_cross::Dev* dv = nullptr;
+  if (int rc = cross_on_device(c, device, &dv)) return rc;
+  CrossFinishArgs a{};
+  a.st = cross_state(dv); a.n = c->elems(); a.n_years = n_years;
+  a.first = (int32_t*)out[0]; a.last = (int32_t*)out[1]; a.stay = (int32_t*)out[2]; a.count = (int32_t*)out[3];
+  a.peak = (float*)out[4]; a.peak_year = (int32_t*)out[5];
+  if (c->what & ~GREB_T_FRACTION) HIP_TRY(nullptr, launch_cross_finish(a, (hipStream_t)stream));
+  c->added = 0; c->added_device = -1;
+  return 0;
+}
+
+} // extern "C"
+
+namespace {
+int run_cross(const std::string& who, Records src, greb_engine* e, int years, const float* co2_ppm, greb_cross* c, int32_t* first,
+              int32_t* last, int32_t* stay, int32_t* count, float* peak, int32_t* peak_year, float* fraction, float* yearly) {
+  // argument errors first, before anything touches a device: the plan, the outputs, then the engine
+  if (!c) return fail(e, GREB_E_INVALID, who + ": no plan (greb_cross is NULL)");
+  if (int rc = src.check_plan(e, who, c->nv)) return rc;
+  if (years < 1) return fail(e, GREB_E_INVALID, who + ": years = " + std::to_string(years));
+  void* host[6] = {first, last, stay, count, peak, peak_year};
+  if (int rc = check_cross_maps(e, who, c, host, "", false)) return rc;
+  const bool frac = (c->what & GREB_T_FRACTION) != 0;
+  if (frac && !fraction) return fail(e, GREB_E_INVALID, who + ": GREB_T_FRACTION selected but `fraction` is NULL");
+  if (c->added != 0)
+    return fail(e, GREB_E_INVALID, who + ": the plan holds " + std::to_string(c->added) + " years of an unfinished period");
+  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, who + ": bad argument (engine or co2_ppm)");
+  if (int rc = check_engine(e, who, c->nx, c->ny, c->nm)) return rc;
+  const size_t el = c->elems(), fr = c->fraction();
+  greb_cross::Dev* dv = nullptr;
+  // The state follows every year where the year was integrated.  A unit is a year's FRACTION, made in output slot y & 1 of
+  // the plan's frac_out; without FRACTION nothing leaves before the end, and the run makes no copy stream and no events.
+  // Nothing on the device grows with `years` (besides the yearly scalars).
+  auto slot = [&](int u) { return dv->frac_out.get() + (size_t)(u & 1) * fr; };
+  RunSink sink;
+  sink.prepare = [&]() -> int {
+    if (int rc = ensure(e, &e->monthly_dev, &e->monthly_cap, 2 * year_records(e))) return rc; // the staging slots
+    if (int rc = src.prepare(e)) return rc;
+    return cross_on_device(c, e->device, &dv);
+  };
+  sink.year = [&](const YearCalls& run, int y) -> int {
+    const float* mon = nullptr;
+    if (int rc = src.integrate(e, run, y, &mon)) return rc;
+    if (frac) if (int rc = run.writing(y)) return rc; // (here, not before the year: only the fraction pass writes the slot)
+    if (int rc = cross_launch_year(e, c, dv, mon, y, frac ? slot(y) : nullptr, e->stream)) return rc;
+    return frac ? run.complete(y) : 0;
+  };
+  if (frac)
+    sink.deliver = [&](int y, int sl) -> int {
+      HIP_TRY(e, hipMemcpyAsync(fraction + (size_t)y * fr, slot(sl), fr * sizeof(float), hipMemcpyDeviceToHost, e->copy_stream));
+      return 0;
+    };
+  // The maps, once, after the last year.  All but STAY are the state words themselves and leave from where they lie; STAY
+  // is made IN PLACE over last_miss (element by element; the period is over, and the next year 0 stores the state anew).
+  sink.finish = [&]() -> int {
+    const CrossState st = cross_state(dv);
+    if (host[2]) {
+      CrossFinishArgs a{};
+      a.st = st; a.n = el; a.n_years = years; a.stay = st.last_miss;
+      HIP_TRY(e, launch_cross_finish(a, e->stream));
+      HIP_TRY(e, hipStreamSynchronize(e->stream));
+    }
+    const void* from[6] = {st.first, st.last, st.last_miss, st.count, st.peak, st.peak_year};
+    for (int i = 0; i < 6; ++i)
+      if (host[i]) HIP_TRY(e, hipMemcpy(host[i], from[i], el * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+  };
+  return run_years(e, years, co2_ppm, yearly, sink);
+}
+} // namespace
+
+extern "C" {
+
+int greb_engine_run_cross(greb_engine* e, int years, const float* co2_ppm, greb_cross* c, int32_t* first, int32_t* last, int32_t* stay,
+                          int32_t* count, float* peak, int32_t* peak_year, float* fraction, float* yearly) {
+  return run_cross("run_cross", Records{}, e, years, co2_ppm, c, first, last, stay, count, peak, peak_year, fraction, yearly);
+}
+
+int greb_engine_run_budget_cross(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_cross* c,
+                                 int32_t* first, int32_t* last, int32_t* stay, int32_t* count, float* peak, int32_t* peak_year,
+                                 float* fraction, float* yearly) {
+  Records src;
+  if (int rc = src.init(e, "run_budget_cross", true, combo, n_out)) return rc;
+  return run_cross("run_budget_cross", src, e, years, co2_ppm, c, first, last, stay, count, peak, peak_year, fraction, yearly);
 }
 
 } // extern "C"

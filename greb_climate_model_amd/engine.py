@@ -49,6 +49,7 @@ def lib() -> C.CDLL:
         abi.lin_prototypes(L)
         abi.budget_prototypes(L)
         abi.gram_prototypes(L)
+        abi.cross_prototypes(L)
         _lib = L
     return _lib
 
@@ -72,7 +73,9 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_forcing_record_field_static", "greb_forcing_record_static_floats",
            "greb_diag_create_vars", "greb_clim_create_vars", "greb_budget_combine_dev", "greb_engine_run_budget_diag",
            "greb_engine_run_budget_clim", "greb_engine_run_budget_ens", "greb_engine_run_budget_lin",
-           "greb_gram_create", "greb_gram_destroy", "greb_gram_reduce_dev", "greb_engine_run_gram", "greb_engine_run_budget_gram"]
+           "greb_gram_create", "greb_gram_destroy", "greb_gram_reduce_dev", "greb_engine_run_gram", "greb_engine_run_budget_gram",
+           "greb_cross_create", "greb_cross_destroy", "greb_cross_add_year_dev", "greb_cross_finish_dev", "greb_engine_run_cross",
+           "greb_engine_run_budget_cross"]
 
 
 def _check(rc: int, h=None):
@@ -270,7 +273,7 @@ class Engine:
         return monthly, budget, yearly
 
     def _reduced(self, name: str, records, co2, plan, *args):
-        """Call the reduced run `name` ("diag", "clim", "ens", "lin", "gram") over `records`: "state" -- the year's five state
+        """Call the reduced run `name` ("diag", "clim", "ens", "lin", "gram", "cross") over `records`: "state" -- the year's five state
         records (greb_engine_run_<name>) --, "budget" -- its thirteen flux terms -- or a budget.Combo -- sums of them
         (greb_engine_run_budget_<name>).  `args`: what follows the plan in the C call."""
         from . import budget
@@ -359,6 +362,24 @@ class Engine:
         G = np.empty((years, plan.nb, plan.U, plan.U), np.float64)
         self._reduced("gram", records, co2, plan, G.ctypes.data_as(C.POINTER(C.c_double)), abi.fptr(yearly))
         return gram.Result(G, yearly, names)
+
+    def run_cross(self, years: int, co2_ppm, plan, records="state"):
+        """The scenario run of run() that hands back only the crossing products of `plan` (cross.Plan): per member, event and
+        point the first and the last year that hits the event's threshold, the year from which it holds to the end, the
+        number of years that hit, the peak and its year, and per year the share of each group's members that hit -- made on
+        the device year by year (greb_engine_run_cross).  Years are 0-based within this call (cross.as_year turns them into
+        calendar years).  Returns a cross.Result: the maps [n_members][n_events][ny][nx], fraction
+        [years][n_groups][n_events][ny][nx] (a product the plan does not select is None).  State, clock and yearly are those
+        of run() over the same years.  records: as in run_diag; the plan's n_vars must be that variable count."""
+        from . import budget, cross
+        co2, yearly = self._run_arrays(years, co2_ppm)
+        names = budget.record_names(records)
+        out = cross.empty_products(plan, years)
+        i32 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+        f32 = lambda a: None if a is None else abi.fptr(a)
+        self._reduced("cross", records, co2, plan, i32(out[0]), i32(out[1]), i32(out[2]), i32(out[3]), f32(out[4]), i32(out[5]),
+                      f32(out[6]), abi.fptr(yearly))
+        return cross.Result(*out, yearly, names)
 
     def state(self, member: int = 0) -> np.ndarray:
         s = np.empty((5, self.ny, self.nx), np.float32)

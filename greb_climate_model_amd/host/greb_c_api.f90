@@ -29,6 +29,13 @@ module greb_c_api
      type(c_ptr) :: z_topo, glacier, sw_solar, tclim, qclim, uclim, vclim, mldclim, cldclim, swetclim
   end type greb_fields
 
+  ! an event of the crossing output (greb_cross_create): variable (0-based), selector (0 ... 11 a month, 12 ... 16 DJF MAM JJA
+  ! SON ANN), rel (1: member minus its control), dir (+1: q >= thr hits, -1: q <= thr), threshold
+  type, bind(C) :: greb_cross_event
+     integer(c_int32_t) :: var, sel, rel, dir
+     real(c_float) :: thr
+  end type greb_cross_event
+
   interface
      subroutine greb_params_default(p) bind(C, name="greb_params_default")
        import :: greb_params
@@ -243,6 +250,57 @@ module greb_c_api
        integer(c_int), value :: years, n_out
        real(c_float), intent(in) :: co2_ppm(*)
        real(c_double), intent(out) :: G(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
+     ! crossing output (greb_cross.hip): a plan = grid, member count, variables per month, events(n_events), control(n_members)
+     ! (0-based; c_null_ptr: no control map), group(n_members) (0-based, -1 = in none; c_null_ptr: no group map), n_groups and
+     ! the products `what` (GREB_T_* of greb_engine.h)
+     integer(c_int) function greb_cross_create(nx, ny, n_members, n_vars, events, n_events, control, group, n_groups, what, plan) &
+          bind(C, name="greb_cross_create")
+       import :: c_int, c_ptr, greb_cross_event
+       integer(c_int), value :: nx, ny, n_members, n_vars, n_events, n_groups, what
+       type(greb_cross_event), intent(in) :: events(*)
+       type(c_ptr), value :: control, group
+       type(c_ptr), intent(out) :: plan
+     end function
+     integer(c_int) function greb_cross_destroy(plan) bind(C, name="greb_cross_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan
+     end function
+     ! device pointers (c_ptr): year k (0-based since the last finish) x_dev(nx,ny,n_vars,12,n_members) into the state, and
+     ! with GREB_T_FRACTION that year's fraction_dev(nx,ny,n_events,n_groups); launches on `stream`, no synchronisation
+     integer(c_int) function greb_cross_add_year_dev(plan, device, x_dev, k, fraction_dev, stream) &
+          bind(C, name="greb_cross_add_year_dev")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan, x_dev, fraction_dev, stream
+       integer(c_int), value :: device, k
+     end function
+     ! the maps of the n_years years added, each (nx,ny,n_events,n_members): int32 but peak_dev (float); c_null_ptr where
+     ! the plan does not select a product
+     integer(c_int) function greb_cross_finish_dev(plan, device, n_years, first_dev, last_dev, stay_dev, count_dev, peak_dev, &
+          peak_year_dev, stream) bind(C, name="greb_cross_finish_dev")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan, first_dev, last_dev, stay_dev, count_dev, peak_dev, peak_year_dev, stream
+       integer(c_int), value :: device, n_years
+     end function
+     ! greb_engine_run that delivers only the plan's crossing products: the maps (nx,ny,n_events,n_members) -- first, last,
+     ! stay, count, peak_year int32, peak float -- and fraction(nx,ny,n_events,n_groups,years); host arrays passed as
+     ! c_loc(...), c_null_ptr where the plan does not select a product; years are 0-based, -1 = never
+     integer(c_int) function greb_engine_run_cross(eng, years, co2_ppm, plan, first, last, stay, count, peak, peak_year, &
+          fraction, yearly) bind(C, name="greb_engine_run_cross")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, plan, first, last, stay, count, peak, peak_year, fraction
+       integer(c_int), value :: years
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
+     ! ... of the year's budget records: the 13 flux terms (combo = c_null_ptr) or the n_out rows of combo(13,n_out)
+     integer(c_int) function greb_engine_run_budget_cross(eng, years, co2_ppm, combo, n_out, plan, first, last, stay, count, &
+          peak, peak_year, fraction, yearly) bind(C, name="greb_engine_run_budget_cross")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, combo, plan, first, last, stay, count, peak, peak_year, fraction
+       integer(c_int), value :: years, n_out
+       real(c_float), intent(in) :: co2_ppm(*)
        real(c_float), intent(out) :: yearly(*)
      end function
      ! greb_engine_run that also delivers the monthly means of the 13 flux terms of the update (GREB_B_* of greb_engine.h):

@@ -490,6 +490,102 @@ int greb_engine_run_gram(greb_engine* e, int years, const float* co2_ppm, greb_g
 int greb_engine_run_budget_gram(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_gram* g,
                                 double* G, float* yearly);
 
+/* ---- crossing output: when members pass thresholds, made on the device ------------------------------
+ * greb_clim reduces the time axis linearly.  WHEN a member's annual-mean warming passes 2 K, whether it stays there, in
+ * which year September's albedo first falls below 0.4, in what share of an ensemble that has happened by year y: a
+ * threshold is not linear in the record, so neither the multi-year means of greb_clim nor the quantiles of greb_ens give
+ * it (a mean crossing is not the years crossing, a quantile crossing is not a member crossing).  A plan holds the grid,
+ * n_members, n_vars (1 ... GREB_MAX_RECORD_VARS), optionally control[n_members] (-1 ... n_members-1) and group[n_members]
+ * (-1 ... n_groups-1, as greb_ens), the products `what` and 1 ... GREB_CROSS_MAX_EVENTS events:
+ *   var  0 ... n_vars-1
+ *   sel  0 ... 11 a calendar month; 12 ... 16 DJF, MAM, JJA, SON, ANN, the seasons of greb_clim (DJF = Dec, Jan, Feb of the
+ *        SAME model year)
+ *   rel  0, or 1: the member minus its control (needs a control map)
+ *   dir  +1: a hit is q >= thr;  -1: a hit is q <= thr
+ *   thr  a finite fp32
+ * The year's quantity q of member m, event e, point i comes from one model year x[m][12][n_vars][ny][nx]:
+ *   month selector   a = x[m][sel][var][i], the fp32 record itself
+ *   season selector  acc = 0.0; acc = acc + jday_mon[mo] * (double)x[m][mo][var][i] over the season's months in calendar
+ *                    order; a = (float)(acc / the season's days) -- greb_clim's seasons applied to one year, the same day
+ *                    counts and divisors, no fused multiply-add: a has the bits of a one-year GREB_C_SEASONS
+ *   rel = 0          q = a
+ *   rel = 1          q = a - a_ctl as ONE fp32 subtraction (the greb_ens convention), a_ctl the same expression for
+ *                    control[m]; a member with control[m] = -1 has q = a QUIET NaN; control[m] = m is legal and gives +0
+ * A NaN never hits.  Over the years k = 0 ... n-1 added since the last finish, per (member, event, point):
+ *   first       -1, then the first k that hits            last       -1, then the latest k that hits
+ *   last_miss   -1, then the latest k that does not hit   count      the number of hits
+ *   peak, peak_year   q of year 0 and 0; afterwards replaced by (q, k) when q > peak (dir = +1; q < peak for dir = -1) or when
+ *                     peak is NaN and q is not: strict, so a tie keeps the earlier year
+ * Year k = 0 STORES the state (no clearing pass); a plan serves any number of periods one after the other.  Products, each
+ * [member][event][ny][nx] in the caller's event order:
+ *   GREB_T_FIRST     int32  first                       GREB_T_LAST   int32  last
+ *   GREB_T_STAY      int32  last_miss + 1 if that is <= n-1, else -1: the year from which the event holds to the end (0: always)
+ *   GREB_T_COUNT     int32  count                       GREB_T_PEAK   fp32 peak and int32 peak_year: two arrays
+ *   GREB_T_FRACTION  fp32 [year][group][event][ny][nx], per YEAR: (float)((double)c / (double)n_g), c the number of the
+ *                    group's n_g members that hit in that year, counted in ascending member index: the group's exceedance
+ *                    probability.  Needs a group map.
+ * Years are 0-based within the call.  Every element has one owner (no atomics): results are deterministic and a member's
+ * numbers do not depend on the batch it is in.
+ * Device memory, per device on first use: only the state words the selected products need, 4 bytes each per (member,
+ * event, point) -- FIRST, LAST, STAY, COUNT one word, PEAK two; all five: 24 bytes, i.e. 906 MB for 512 members x 16 events
+ * at 96 x 48, 57 MB per event.  FRACTION adds one hit byte per (member, event, point) and two output slots of
+ * [group][event][ny][nx].  Nothing grows with the number of years. */
+#define GREB_T_FIRST    1u
+#define GREB_T_LAST     2u
+#define GREB_T_STAY     4u
+#define GREB_T_COUNT    8u
+#define GREB_T_PEAK     16u
+#define GREB_T_FRACTION 32u
+#define GREB_CROSS_MAX_EVENTS 16
+#define GREB_CROSS_DJF 12 /* selectors behind the twelve months */
+#define GREB_CROSS_MAM 13
+#define GREB_CROSS_JJA 14
+#define GREB_CROSS_SON 15
+#define GREB_CROSS_ANN 16
+typedef struct greb_cross_event {
+  int32_t var, sel, rel, dir;
+  float thr;
+} greb_cross_event;
+typedef struct greb_cross greb_cross;
+/* A plan.  Host data only, validated without touching a device.  GREB_E_INVALID with a message that names the offender --
+ * field, event index or member (greb_engine_last_error(NULL)): a grid greb_diag_create does not take, n_members < 1, n_vars
+ * out of range, `what` zero or with unknown bits, n_events outside 1 ... 16 or `events` NULL, an event's var or sel out of
+ * range, rel not 0 or 1 or rel = 1 without `control`, dir not +1 or -1, thr not finite, a control index out of range,
+ * GREB_T_FRACTION without `group`; with `group`: n_groups outside 1 ... GREB_ENS_MAX_GROUPS, a group index out of range, an
+ * empty group.  control and group may be NULL (n_groups is then not read). */
+int greb_cross_create(int nx, int ny, int n_members, int n_vars, const greb_cross_event* events, int n_events,
+                      const int32_t* control, const int32_t* group, int n_groups, unsigned what, greb_cross** out);
+int greb_cross_destroy(greb_cross* c); /* waits for the device before it frees the state */
+/* Year k (0-based) of the current period, one model year x_dev[n_members][12][n_vars][ny][nx] on HIP device `device` (16-byte
+ * aligned), into the state; with GREB_T_FRACTION also that year's fraction_dev[n_groups][n_events][ny][nx] (16-byte aligned;
+ * NULL is GREB_E_INVALID then, and the pointer is ignored otherwise).  k must be the number of years added since the last
+ * finish.  Launches on `stream` (a hipStream_t, may be NULL) and does not synchronise; the calls of one period must be
+ * ordered among themselves. */
+int greb_cross_add_year_dev(greb_cross* c, int device, const float* x_dev, int k, float* fraction_dev, void* stream);
+/* The maps of the n_years years added since the last finish (n_years must be that number) to device memory,
+ * [n_members][n_events][ny][nx] each, 16-byte aligned.  A pointer whose product the plan does not select is ignored and
+ * may be NULL; a selected product with a NULL pointer is GREB_E_INVALID (GREB_T_PEAK needs both peak_dev and
+ * peak_year_dev).  Both _dev calls check their arguments before any device query; without a device they are GREB_E_NOGPU
+ * (no CPU path). */
+int greb_cross_finish_dev(greb_cross* c, int device, int n_years, int32_t* first_dev, int32_t* last_dev, int32_t* stay_dev,
+                          int32_t* count_dev, float* peak_dev, int32_t* peak_year_dev, void* stream);
+/* greb_engine_run that delivers ONLY the plan's products over the `years` years of this call (k = the year of the call),
+ * to host memory: the maps [n_members][n_events][ny][nx], fraction [years][n_groups][n_events][ny][nx] (unselected products
+ * as above).  The plan must have n_vars = 5; one made for another grid, member count or variable count, a selected
+ * product with a NULL pointer or a plan with an unfinished period is GREB_E_INVALID, decided before any device work; a
+ * refused call leaves the engine usable.  Each year is integrated into one of the engine's two one-year staging slots and
+ * the state updated behind it on the same stream; a year's FRACTION is made in one of two device output slots and leaves
+ * on the copy stream while the following year integrates; the maps are written once after the last year.  Without
+ * GREB_T_FRACTION the run makes no copy stream and no events.  Device memory does not grow with `years` (the yearly
+ * scalars aside).  co2_ppm, yearly, the model clock, the state the engine is left in and the kernels that integrate are
+ * those of greb_engine_run over the same years, bit for bit. */
+int greb_engine_run_cross(greb_engine* e, int years, const float* co2_ppm, greb_cross* c, int32_t* first, int32_t* last,
+                          int32_t* stay, int32_t* count, float* peak, int32_t* peak_year, float* fraction, float* yearly);
+/* ... over the year's BUDGET records, as greb_engine_run_budget_clim: the plan must have n_vars = V. */
+int greb_engine_run_budget_cross(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_cross* c,
+                                 int32_t* first, int32_t* last, int32_t* stay, int32_t* count, float* peak, int32_t* peak_year,
+                                 float* fraction, float* yearly);
+
 /* ---- per-member forcing: regional and seasonal CO2, insolation tables and scale --------------------
  * Members of one engine may differ in the forcing itself, not only in the CO2 level: CO2 raised in one hemisphere, over
  * land or ocean only or in one half of the year, a changed solar constant, a changed latitudinal or seasonal distribution
