@@ -189,6 +189,36 @@ def cross_prototypes(lib) -> None:
         f.restype = C.c_int
 
 
+R_SLOPE, R_INTERCEPT, R_R2, R_INDEX = 1, 2, 4, 8  # regression products, GREB_R_* of include/greb_engine.h
+REG_MAX_INDICES, REG_MAX_TERMS, REG_MAX_MEMBERS = 8, 16, 65535  # GREB_REG_MAX_INDICES, GREB_REG_MAX_TERMS, GREB_REG_MAX_MEMBERS
+
+
+class GrebRegIndex(C.Structure):
+    """struct greb_reg_index: variable, selector and member minus control as in GrebCrossEvent, and the region (0: the globe)."""
+    _fields_ = [("var", C.c_int32), ("sel", C.c_int32), ("rel", C.c_int32), ("region", C.c_int32)]
+
+
+class GrebRegTerm(C.Structure):
+    """struct greb_reg_term: variable, selector, member minus control, and the index it is regressed on."""
+    _fields_ = [("var", C.c_int32), ("sel", C.c_int32), ("rel", C.c_int32), ("index", C.c_int32)]
+
+
+def reg_prototypes(lib) -> None:
+    """The argument types of greb_reg_* and of the two runs that deliver regression maps."""
+    i32p, vp = C.POINTER(C.c_int32), C.c_void_p
+    out = [c_float_p] * 5  # slope, intercept, r2, index, yearly
+    lib.greb_reg_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, i32p, C.POINTER(GrebRegIndex), C.c_int,
+                                    C.POINTER(GrebRegTerm), C.c_int, C.c_uint, C.POINTER(vp)]
+    lib.greb_reg_destroy.argtypes = [vp]
+    lib.greb_reg_add_year_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
+    lib.greb_reg_finish_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.greb_engine_run_reg.argtypes = [vp, C.c_int, c_float_p, vp] + out
+    lib.greb_engine_run_budget_reg.argtypes = [vp, C.c_int, c_float_p, c_float_p, C.c_int, vp] + out
+    for f in (lib.greb_reg_create, lib.greb_reg_destroy, lib.greb_reg_add_year_dev, lib.greb_reg_finish_dev, lib.greb_engine_run_reg,
+              lib.greb_engine_run_budget_reg):
+        f.restype = C.c_int
+
+
 MAX_RECORD_VARS = 16  # GREB_MAX_RECORD_VARS: variables per month of the records a diag or clim plan reduces
 
 

@@ -25,39 +25,16 @@
 // the same IEEE operations; it is seasons_of of greb_clim.hip applied to one year): this file is built with
 // -ffp-contract=off (build.py: EXTRA_FLAGS), so that no multiply is fused into the add that follows it.
 #include "greb_cross.h"
+#include "greb_season.h"
 
 namespace greb {
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
+using season::f4;
+using season::kMonths;
+using season::months_of;
+using season::quantity; // (greb_season.h: one statement of the yearly quantity for greb_cross and greb_reg)
 typedef int i4 __attribute__((ext_vector_type(4)));
-
-constexpr int kMonths = 12;
-
-// the quantity of selector s (a compile-time constant after unrolling) from the twelve months of one variable
-__device__ inline f4 quantity(int s, const f4 (&x)[kMonths]) {
-  if (s < kMonths) return x[s];
-  constexpr double days[kMonths] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31}; // JDAY_MON, src/greb.f90:42
-  constexpr int first[5] = {11, 2, 5, 8, 0}, count[5] = {3, 3, 3, 3, 12};
-  constexpr double total[5] = {90, 92, 92, 91, 365};
-  const int q = s - kMonths;
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int j = 0; j < count[q]; ++j) {
-    const int mo = (first[q] + j) % kMonths;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = acc[e] + days[mo] * (double)x[mo][e];
-  }
-  f4 a;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) a[e] = (float)(acc[e] / total[q]);
-  return a;
-}
-
-// the months selector s reads
-__host__ __device__ constexpr int months_of(int s) {
-  return s < kMonths ? 1 << s : s == 12 ? 0x803 : s == 13 ? 0x01c : s == 14 ? 0x0e0 : s == 15 ? 0x700 : 0xfff;
-}
 
 // one event's state words of one quad: g = the quad's index in [member][event][np / 4]
 template <bool FIRST>

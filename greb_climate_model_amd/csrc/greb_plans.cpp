@@ -1,4 +1,4 @@
-// greb_plans.cpp -- the output plans (greb_diag, greb_clim, greb_ens, greb_lin, greb_gram, greb_cross): their _dev entry points and their scenario-run sinks.
+// greb_plans.cpp -- the output plans (greb_diag, greb_clim, greb_ens, greb_lin, greb_gram, greb_cross, greb_reg): their _dev entry points and their scenario-run sinks.
 // A plan is host data only; what it needs on a device is made the first time it works there (PerDevice).
 #include "greb_host.h"
 
@@ -13,6 +13,7 @@
 #include "greb_lin.h"
 #include "greb_gram.h"
 #include "greb_cross.h"
+#include "greb_reg.h"
 #include "greb_fluxes.h"
 
 using namespace greb;
@@ -20,6 +21,9 @@ using namespace greb::host;
 
 static_assert(kGramMaxUsed == GREB_GRAM_MAX_USED && kGramMaxBlocks == GREB_GRAM_MAX_BLOCKS, "greb_gram.h mirrors include/greb_engine.h");
 static_assert(kCrossMaxEvents == GREB_CROSS_MAX_EVENTS && sizeof(greb_cross_event) == 20, "greb_cross.h mirrors include/greb_engine.h");
+static_assert(kRegMaxTerms == GREB_REG_MAX_TERMS && kRegMaxIndices == GREB_REG_MAX_INDICES && sizeof(greb_reg_index) == 16 &&
+                  sizeof(greb_reg_term) == 16 && kRegSelectors == kCrossSelectors && kRegMaxMembers == GREB_REG_MAX_MEMBERS,
+              "greb_reg.h mirrors include/greb_engine.h");
 static_assert(kFluxTerms == GREB_NBUDGET && kFluxMaxOut == GREB_MAX_RECORD_VARS, "greb_fluxes.h mirrors include/greb_engine.h");
 
 namespace {
@@ -247,32 +251,27 @@ DiagArgs diag_args(const greb_diag* d, const greb_diag::Dev* dv, const float* mo
   a.regions = regions; a.regions_stride = regions_stride; a.zonal = zonal; a.annual = annual;
   return a;
 }
-} // namespace
 
-extern "C" {
-
-int greb_diag_create(int nx, int ny, const float* region_w, int n_regions, greb_diag** out) {
-  return greb_diag_create_vars(nx, ny, region_w, n_regions, kStateVars, out);
-}
-
-int greb_diag_create_vars(int nx, int ny, const float* region_w, int n_regions, int n_vars, greb_diag** out) {
-  if (!out) return fail(nullptr, GREB_E_INVALID, "diag_create: `out` is NULL");
+// The plan of greb_diag_create_vars for whoever makes one (`who`: "diag_create", or "reg_create" for the regional means a
+// regression plan takes its indices from): the checks, the combined weights and the reciprocals of their sums.
+int make_diag(const std::string& who, int nx, int ny, const float* region_w, int n_regions, int n_vars, greb_diag** out) {
+  if (!out) return fail(nullptr, GREB_E_INVALID, who + ": `out` is NULL");
   *out = nullptr;
-  if (int rc = check_grid("diag_create", nx, ny)) return rc;
-  if (int rc = check_n_vars("diag_create", n_vars)) return rc;
+  if (int rc = check_grid(who, nx, ny)) return rc;
+  if (int rc = check_n_vars(who, n_vars)) return rc;
   if (n_regions < 0 || n_regions > kDiagMaxRegions)
-    return fail(nullptr, GREB_E_INVALID, "diag_create: n_regions = " + std::to_string(n_regions) + " (0 ... " +
+    return fail(nullptr, GREB_E_INVALID, who + ": n_regions = " + std::to_string(n_regions) + " (0 ... " +
                                              std::to_string(kDiagMaxRegions) + "; the globe is region 0 on top of them)");
-  if (n_regions > 0 && !region_w) return fail(nullptr, GREB_E_INVALID, "diag_create: region_w is NULL with n_regions > 0");
+  if (n_regions > 0 && !region_w) return fail(nullptr, GREB_E_INVALID, who + ": region_w is NULL with n_regions > 0");
   const size_t np = (size_t)nx * ny;
   for (int k = 0; k < n_regions; ++k)
     for (size_t i = 0; i < np; ++i) {
       const float v = region_w[(size_t)k * np + i];
       if (!(v >= 0.f && v <= 1.f)) { // (a NaN fails both comparisons)
         char buf[160];
-        std::snprintf(buf, sizeof(buf), "diag_create: region %d: weight %g at row %zu, column %zu is not in [0, 1]", k + 1,
-                      (double)v, i / (size_t)nx, i % (size_t)nx);
-        return fail(nullptr, GREB_E_INVALID, buf);
+        std::snprintf(buf, sizeof(buf), ": region %d: weight %g at row %zu, column %zu is not in [0, 1]", k + 1, (double)v,
+                      i / (size_t)nx, i % (size_t)nx);
+        return fail(nullptr, GREB_E_INVALID, who + buf);
       }
     }
   greb_diag* d = new (std::nothrow) greb_diag();
@@ -294,12 +293,23 @@ int greb_diag_create_vars(int nx, int ny, const float* region_w, int n_regions, 
     }
     if (!(sum > 0.0)) {
       delete d;
-      return fail(nullptr, GREB_E_INVALID, "diag_create: region " + std::to_string(r) + " has zero weight everywhere");
+      return fail(nullptr, GREB_E_INVALID, who + ": region " + std::to_string(r) + " has zero weight everywhere");
     }
     d->inv_sum[(size_t)r] = 1.0 / sum;
   }
   *out = d;
   return 0;
+}
+} // namespace
+
+extern "C" {
+
+int greb_diag_create(int nx, int ny, const float* region_w, int n_regions, greb_diag** out) {
+  return make_diag("diag_create", nx, ny, region_w, n_regions, kStateVars, out);
+}
+
+int greb_diag_create_vars(int nx, int ny, const float* region_w, int n_regions, int n_vars, greb_diag** out) {
+  return make_diag("diag_create", nx, ny, region_w, n_regions, n_vars, out);
 }
 
 int greb_diag_destroy(greb_diag* d) {
@@ -1478,6 +1488,304 @@ int greb_engine_run_budget_cross(greb_engine* e, int years, const float* co2_ppm
   Records src;
   if (int rc = src.init(e, "run_budget_cross", true, combo, n_out)) return rc;
   return run_cross("run_budget_cross", src, e, years, co2_ppm, c, first, last, stay, count, peak, peak_year, fraction, yearly);
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- regression output (greb_reg.hip)
+// Grid, member count, variable count, a diag plan over the caller's region weights (made by make_diag: the regional means
+// the indices are taken from have the bits a greb_diag plan over the same weights returns), the indices in the caller's
+// order, the terms in the caller's order (index_of) and as the update kernel walks them (RegTable: sorted by variable, then
+// selector), each member's control and the products.  Per device: the term state, the index state, one year's regional
+// means, the control's copy; for greb_engine_run_reg the map the products leave through and the INDEX series.  `added`
+// counts the years since the last finish: one period is followed at a time, on one device.
+struct greb_reg {
+  int nx = 0, ny = 0, nm = 0, nv = 0, nt = 0, ni = 0;
+  unsigned what = 0;
+  greb_diag* diag = nullptr;
+  RegTable table{};
+  RegIndexTable itable{};
+  int index_of[kRegMaxTerms] = {};
+  std::vector<int> control;
+  int added = 0, added_device = -1;
+  struct Dev {
+    DevBuf<float> y0, g0, regions, out, series;
+    DevBuf<double> sy, sgy, syy, G, sg, sgg;
+    DevBuf<int> control;
+    size_t series_cap = 0;
+  };
+  PerDevice<Dev> devs;
+  size_t np() const { return (size_t)nx * ny; }
+  size_t elems() const { return (size_t)nm * nt * np(); } // one state word, one map
+  size_t regions() const { return (size_t)nm * kDiagMonths * nv * diag->nr; }
+  ~greb_reg() { delete diag; }
+};
+
+namespace {
+constexpr unsigned kRegMaps = GREB_R_SLOPE | GREB_R_INTERCEPT | GREB_R_R2;
+constexpr unsigned kRegAll = kRegMaps | GREB_R_INDEX;
+
+int reg_on_device(greb_reg* r, int device, greb_reg::Dev** out) {
+  return r->devs.get(device, [r](greb_reg::Dev& n) -> int {
+    const size_t el = r->elems(), ix = (size_t)r->nm * r->ni;
+    HIP_TRY(nullptr, n.y0.alloc(el)); HIP_TRY(nullptr, n.sy.alloc(el)); HIP_TRY(nullptr, n.sgy.alloc(el));
+    if (r->what & GREB_R_R2) HIP_TRY(nullptr, n.syy.alloc(el));
+    HIP_TRY(nullptr, n.g0.alloc(ix)); HIP_TRY(nullptr, n.G.alloc(ix)); HIP_TRY(nullptr, n.sg.alloc(ix)); HIP_TRY(nullptr, n.sgg.alloc(ix));
+    HIP_TRY(nullptr, n.regions.alloc(r->regions()));
+    if (!r->control.empty()) HIP_TRY(nullptr, n.control.upload(r->control.data(), r->control.size()));
+    return 0;
+  }, out);
+}
+
+RegState reg_state(const greb_reg::Dev* dv) { return RegState{dv->y0.get(), dv->sy.get(), dv->sgy.get(), dv->syy.get()}; }
+RegIndexState reg_index_state(const greb_reg::Dev* dv) { return RegIndexState{dv->g0.get(), dv->G.get(), dv->sg.get(), dv->sgg.get()}; }
+
+// year k of x: its regional means, the indices from them (member m's g to index + m * index_stride where `index` is
+// given), then the terms' sums
+int reg_launch_year(greb_engine* e, greb_reg* r, int device, const greb_reg::Dev* dv, const float* x, int k, float* index,
+                    size_t index_stride, hipStream_t stream) {
+  greb_diag::Dev* ddv = nullptr;
+  if (int rc = diag_on_device(r->diag, device, r->nm, true, &ddv)) return rc;
+  const DiagArgs d = diag_args(r->diag, ddv, x, dv->regions.get(), (size_t)kDiagMonths * r->nv * r->diag->nr, nullptr, nullptr);
+  HIP_TRY(e, launch_diag_year(d, r->nm, stream));
+  RegIndexArgs ia{};
+  ia.regions = dv->regions.get(); ia.control = dv->control.get(); ia.ix = reg_index_state(dv);
+  ia.n_members = r->nm; ia.n_vars = r->nv; ia.nr = r->diag->nr; ia.n_indices = r->ni; ia.k = k;
+  ia.index = index; ia.index_stride = index_stride; ia.t = r->itable;
+  HIP_TRY(e, launch_reg_index(ia, stream));
+  RegUpdateArgs a{};
+  a.x = x; a.control = dv->control.get(); a.st = reg_state(dv); a.G = dv->G.get(); a.np = r->np();
+  a.n_members = r->nm; a.n_vars = r->nv; a.n_terms = r->nt; a.n_indices = r->ni; a.k = k; a.t = r->table;
+  HIP_TRY(e, launch_reg_update(a, stream));
+  return 0;
+}
+
+RegFinishArgs reg_finish_args(const greb_reg* r, const greb_reg::Dev* dv, int n_years, float* slope, float* intercept, float* r2) {
+  RegFinishArgs a{};
+  a.st = reg_state(dv); a.ix = reg_index_state(dv); a.np = r->np();
+  a.n_members = r->nm; a.n_terms = r->nt; a.n_indices = r->ni; a.n_years = n_years;
+  for (int t = 0; t < r->nt; ++t) a.index_of[t] = r->index_of[t];
+  a.slope = slope; a.intercept = intercept; a.r2 = r2;
+  return a;
+}
+
+// the three maps: their parameters' names, what selects each, and whether the caller gave every selected one
+const char* const kRegOutNames[3] = {"slope", "intercept", "r2"};
+const char* const kRegFlagNames[3] = {"GREB_R_SLOPE", "GREB_R_INTERCEPT", "GREB_R_R2"};
+const unsigned kRegFlags[3] = {GREB_R_SLOPE, GREB_R_INTERCEPT, GREB_R_R2};
+int check_reg_maps(greb_engine* e, const std::string& who, const greb_reg* r, float* p[3], const char* suffix, bool aligned) {
+  for (int i = 0; i < 3; ++i) {
+    if (!(r->what & kRegFlags[i])) { p[i] = nullptr; continue; }
+    if (!p[i]) return fail(e, GREB_E_INVALID, who + ": " + kRegFlagNames[i] + " selected but `" + kRegOutNames[i] + suffix + "` is NULL");
+    if (aligned) if (int rc = check_aligned(who, p[i], std::string(kRegOutNames[i]) + suffix)) return rc;
+  }
+  return 0;
+}
+
+const char* const kSelRange = " (0 ... 11: a month; 12 ... 16: DJF, MAM, JJA, SON, ANN)";
+} // namespace
+
+extern "C" {
+
+int greb_reg_create(int nx, int ny, int n_members, int n_vars, const float* region_w, int n_regions, const int32_t* control,
+                    const greb_reg_index* indices, int n_indices, const greb_reg_term* terms, int n_terms, unsigned what,
+                    greb_reg** out) {
+  if (!out) return fail(nullptr, GREB_E_INVALID, "reg_create: `out` is NULL");
+  *out = nullptr;
+  if (int rc = check_grid("reg_create", nx, ny)) return rc;
+  if (int rc = check_n_vars("reg_create", n_vars)) return rc;
+  if (n_members < 1 || n_members > GREB_REG_MAX_MEMBERS) // (the member is a grid dimension of the update and finish kernels)
+    return fail(nullptr, GREB_E_INVALID, "reg_create: n_members = " + std::to_string(n_members) + " (1 ... " +
+                                             std::to_string(GREB_REG_MAX_MEMBERS) + ")");
+  if (int rc = check_what(nullptr, "reg_create", what, kRegAll)) return rc;
+  if (n_indices < 1 || n_indices > GREB_REG_MAX_INDICES || !indices)
+    return fail(nullptr, GREB_E_INVALID, "reg_create: n_indices = " + std::to_string(n_indices) + (indices ? "" : " and `indices` NULL") +
+                                             " (1 ... " + std::to_string(GREB_REG_MAX_INDICES) + ")");
+  if (n_terms < 1 || n_terms > GREB_REG_MAX_TERMS || !terms)
+    return fail(nullptr, GREB_E_INVALID, "reg_create: n_terms = " + std::to_string(n_terms) + (terms ? "" : " and `terms` NULL") +
+                                             " (1 ... " + std::to_string(GREB_REG_MAX_TERMS) + ")");
+  if (n_regions < 0 || n_regions > kDiagMaxRegions) // (make_diag says the same; here before an index's region is held against it)
+    return fail(nullptr, GREB_E_INVALID, "reg_create: n_regions = " + std::to_string(n_regions) + " (0 ... " +
+                                             std::to_string(kDiagMaxRegions) + "; the globe is region 0 on top of them)");
+  for (int j = 0; j < n_indices; ++j) {
+    const greb_reg_index& ix = indices[j];
+    const std::string who = "reg_create: index " + std::to_string(j) + ": ";
+    if (ix.var < 0 || ix.var >= n_vars)
+      return fail(nullptr, GREB_E_INVALID, who + "var = " + std::to_string(ix.var) + " (0 ... " + std::to_string(n_vars - 1) + ")");
+    if (ix.sel < 0 || ix.sel >= kRegSelectors) return fail(nullptr, GREB_E_INVALID, who + "sel = " + std::to_string(ix.sel) + kSelRange);
+    if (ix.rel != 0 && ix.rel != 1) return fail(nullptr, GREB_E_INVALID, who + "rel = " + std::to_string(ix.rel) + " (0 or 1)");
+    if (ix.region < 0 || ix.region > n_regions)
+      return fail(nullptr, GREB_E_INVALID, who + "region = " + std::to_string(ix.region) + " (0: the globe, ... " + std::to_string(n_regions) + ")");
+  }
+  for (int t = 0; t < n_terms; ++t) {
+    const greb_reg_term& tm = terms[t];
+    const std::string who = "reg_create: term " + std::to_string(t) + ": ";
+    if (tm.var < 0 || tm.var >= n_vars)
+      return fail(nullptr, GREB_E_INVALID, who + "var = " + std::to_string(tm.var) + " (0 ... " + std::to_string(n_vars - 1) + ")");
+    if (tm.sel < 0 || tm.sel >= kRegSelectors) return fail(nullptr, GREB_E_INVALID, who + "sel = " + std::to_string(tm.sel) + kSelRange);
+    if (tm.rel != 0 && tm.rel != 1) return fail(nullptr, GREB_E_INVALID, who + "rel = " + std::to_string(tm.rel) + " (0 or 1)");
+    if (tm.index < 0 || tm.index >= n_indices)
+      return fail(nullptr, GREB_E_INVALID, who + "index = " + std::to_string(tm.index) + " (0 ... " + std::to_string(n_indices - 1) + ")");
+    if (tm.rel && !control) return fail(nullptr, GREB_E_INVALID, who + "rel = 1 (member minus its control) but `control` is NULL");
+    if (indices[tm.index].rel && !control)
+      return fail(nullptr, GREB_E_INVALID, who + "its index " + std::to_string(tm.index) + " has rel = 1 (member minus its control) but `control` is NULL");
+  }
+  for (int j = 0; j < n_indices; ++j) // (one that no term names)
+    if (indices[j].rel && !control)
+      return fail(nullptr, GREB_E_INVALID, "reg_create: index " + std::to_string(j) + ": rel = 1 (member minus its control) but `control` is NULL");
+  if (control)
+    for (int m = 0; m < n_members; ++m)
+      if (control[m] < -1 || control[m] >= n_members)
+        return fail(nullptr, GREB_E_INVALID, "reg_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
+                                                 " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
+  greb_diag* diag = nullptr;
+  if (int rc = make_diag("reg_create", nx, ny, region_w, n_regions, n_vars, &diag)) return rc; // the weights
+  greb_reg* r = new (std::nothrow) greb_reg();
+  if (!r) { delete diag; return fail(nullptr, GREB_E_INVALID, "out of host memory"); }
+  r->nx = nx; r->ny = ny; r->nm = n_members; r->nv = n_vars; r->nt = n_terms; r->ni = n_indices; r->what = what; r->diag = diag;
+  if (control) r->control.assign(control, control + n_members);
+  for (int j = 0; j < n_indices; ++j) r->itable.ix[j] = RegIndexTable::Ix{indices[j].var, indices[j].sel, indices[j].rel, indices[j].region};
+  // the terms by variable, then selector (the caller's order among equals); what each variable's terms read
+  std::vector<int> order((size_t)n_terms);
+  for (int i = 0; i < n_terms; ++i) order[(size_t)i] = i;
+  std::stable_sort(order.begin(), order.end(), [terms](int a, int b) {
+    return terms[a].var != terms[b].var ? terms[a].var < terms[b].var : terms[a].sel < terms[b].sel;
+  });
+  RegTable& t = r->table;
+  int v = -1;
+  for (int i = 0; i < n_terms; ++i) {
+    const greb_reg_term& tm = terms[order[(size_t)i]];
+    r->index_of[i] = terms[i].index;
+    t.term[i] = RegTable::Term{tm.sel, tm.rel, tm.index, order[(size_t)i]};
+    if (v < 0 || t.var[v] != tm.var) { ++v; t.var[v] = tm.var; t.vstart[v] = i; }
+    static constexpr int kSeasonMonths[5] = {0x803, 0x01c, 0x0e0, 0x700, 0xfff}; // DJF MAM JJA SON ANN, bit mo
+    const int months = tm.sel < 12 ? 1 << tm.sel : kSeasonMonths[tm.sel - 12];
+    t.months[v] |= months;
+    if (tm.rel) { t.ctl_months[v] |= months; t.rel_sels[v] |= 1 << tm.sel; }
+  }
+  t.n_vars_used = v + 1;
+  t.vstart[t.n_vars_used] = n_terms;
+  *out = r;
+  return 0;
+}
+
+int greb_reg_destroy(greb_reg* r) {
+  delete r; // (PerDevice waits for each device before its state goes)
+  return 0;
+}
+
+int greb_reg_add_year_dev(greb_reg* r, int device, const float* x_dev, int k, float* index_dev, void* stream) {
+  if (!r) return fail(nullptr, GREB_E_INVALID, "reg_add_year_dev: no plan (greb_reg is NULL)");
+  if (!x_dev) return fail(nullptr, GREB_E_INVALID, "reg_add_year_dev: x_dev is NULL");
+  if (int rc = check_aligned("reg_add_year_dev", x_dev, "x_dev")) return rc;
+  if ((r->what & GREB_R_INDEX) && !index_dev)
+    return fail(nullptr, GREB_E_INVALID, "reg_add_year_dev: GREB_R_INDEX selected but `index_dev` is NULL");
+  if (k != r->added)
+    return fail(nullptr, GREB_E_INVALID, "reg_add_year_dev: k = " + std::to_string(k) + ", but " + std::to_string(r->added) +
+                                             " years were added since the last finish (years go in ascending order, k = 0 first)");
+  if (k > 0 && device != r->added_device)
+    return fail(nullptr, GREB_E_INVALID, "reg_add_year_dev: device " + std::to_string(device) + ", but this period's state is on device " +
+                                             std::to_string(r->added_device));
+  if (int rc = use_device("reg_add_year_dev: ", device)) return rc;
+  greb_reg::Dev* dv = nullptr;
+  if (int rc = reg_on_device(r, device, &dv)) return rc;
+  if (int rc = reg_launch_year(nullptr, r, device, dv, x_dev, k, (r->what & GREB_R_INDEX) ? index_dev : nullptr, (size_t)r->ni,
+                               (hipStream_t)stream))
+    return rc;
+  r->added = k + 1; r->added_device = device;
+  return 0;
+}
+
+int greb_reg_finish_dev(greb_reg* r, int device, int n_years, float* slope_dev, float* intercept_dev, float* r2_dev, void* stream) {
+  if (!r) return fail(nullptr, GREB_E_INVALID, "reg_finish_dev: no plan (greb_reg is NULL)");
+  float* out[3] = {slope_dev, intercept_dev, r2_dev};
+  if (int rc = check_reg_maps(nullptr, "reg_finish_dev", r, out, "_dev", true)) return rc;
+  if (n_years != r->added || n_years < 1)
+    return fail(nullptr, GREB_E_INVALID, "reg_finish_dev: n_years = " + std::to_string(n_years) + ", but " + std::to_string(r->added) +
+                                             " years were added since the last finish");
+  if (device != r->added_device)
+    return fail(nullptr, GREB_E_INVALID, "reg_finish_dev: device " + std::to_string(device) + ", but this period's state is on device " +
+                                             std::to_string(r->added_device));
+  if (int rc = use_device("reg_finish_dev: ", device)) return rc;
+  greb_reg::Dev* dv = nullptr;
+  if (int rc = reg_on_device(r, device, &dv)) return rc;
+  HIP_TRY(nullptr, launch_reg_finish(reg_finish_args(r, dv, n_years, out[0], out[1], out[2]), (hipStream_t)stream));
+  r->added = 0; r->added_device = -1;
+  return 0;
+}
+
+} // extern "C"
+
+namespace {
+int run_reg(const std::string& who, Records src, greb_engine* e, int years, const float* co2_ppm, greb_reg* r, float* slope,
+            float* intercept, float* r2, float* index, float* yearly) {
+  // argument errors first, before anything touches a device: the plan, the outputs, then the engine
+  if (!r) return fail(e, GREB_E_INVALID, who + ": no plan (greb_reg is NULL)");
+  if (int rc = src.check_plan(e, who, r->nv)) return rc;
+  if (years < 1) return fail(e, GREB_E_INVALID, who + ": years = " + std::to_string(years));
+  float* host[3] = {slope, intercept, r2};
+  if (int rc = check_reg_maps(e, who, r, host, "", false)) return rc;
+  const bool series = (r->what & GREB_R_INDEX) != 0;
+  if (series && !index) return fail(e, GREB_E_INVALID, who + ": GREB_R_INDEX selected but `index` is NULL");
+  if (r->added != 0)
+    return fail(e, GREB_E_INVALID, who + ": the plan holds " + std::to_string(r->added) + " years of an unfinished period");
+  if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, who + ": bad argument (engine or co2_ppm)");
+  if (int rc = check_engine(e, who, r->nx, r->ny, r->nm)) return rc;
+  const size_t el = r->elems(), ser = (size_t)r->nm * years * r->ni;
+  greb_reg::Dev* dv = nullptr;
+  // The state follows every year where the year was integrated; nothing leaves before the end, so the run makes no copy
+  // stream and no events.  The INDEX series [member][years][index] is the only thing that grows with `years`.
+  RunSink sink;
+  sink.prepare = [&]() -> int {
+    if (int rc = ensure(e, &e->monthly_dev, &e->monthly_cap, 2 * year_records(e))) return rc; // the staging slots
+    if (int rc = src.prepare(e)) return rc;
+    if (int rc = reg_on_device(r, e->device, &dv)) return rc;
+    if ((r->what & kRegMaps) && !dv->out) HIP_TRY(e, dv->out.alloc(el));
+    if (series && dv->series_cap < ser) {
+      if (dv->series) HIP_TRY(e, hipDeviceSynchronize());
+      dv->series_cap = 0;
+      HIP_TRY(e, dv->series.alloc(ser));
+      dv->series_cap = ser;
+    }
+    return 0;
+  };
+  sink.year = [&](const YearCalls& run, int y) -> int {
+    const float* mon = nullptr;
+    if (int rc = src.integrate(e, run, y, &mon)) return rc;
+    return reg_launch_year(e, r, e->device, dv, mon, y, series ? dv->series.get() + (size_t)y * r->ni : nullptr, (size_t)years * r->ni,
+                           e->stream);
+  };
+  // The maps, once, after the last year: each selected one is made in the plan's output map and leaves from there.
+  sink.finish = [&]() -> int {
+    for (int i = 0; i < 3; ++i) {
+      if (!host[i]) continue;
+      float* o = dv->out.get();
+      HIP_TRY(e, launch_reg_finish(reg_finish_args(r, dv, years, i == 0 ? o : nullptr, i == 1 ? o : nullptr, i == 2 ? o : nullptr), e->stream));
+      HIP_TRY(e, hipStreamSynchronize(e->stream));
+      HIP_TRY(e, hipMemcpy(host[i], o, el * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    if (series) {
+      HIP_TRY(e, hipStreamSynchronize(e->stream)); // (the index kernels of the last year)
+      HIP_TRY(e, hipMemcpy(index, dv->series.get(), ser * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return 0;
+  };
+  return run_years(e, years, co2_ppm, yearly, sink);
+}
+} // namespace
+
+extern "C" {
+
+int greb_engine_run_reg(greb_engine* e, int years, const float* co2_ppm, greb_reg* r, float* slope, float* intercept, float* r2,
+                        float* index, float* yearly) {
+  return run_reg("run_reg", Records{}, e, years, co2_ppm, r, slope, intercept, r2, index, yearly);
+}
+
+int greb_engine_run_budget_reg(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_reg* r,
+                               float* slope, float* intercept, float* r2, float* index, float* yearly) {
+  Records src;
+  if (int rc = src.init(e, "run_budget_reg", true, combo, n_out)) return rc;
+  return run_reg("run_budget_reg", src, e, years, co2_ppm, r, slope, intercept, r2, index, yearly);
 }
 
 } // extern "C"

@@ -50,6 +50,7 @@ def lib() -> C.CDLL:
         abi.budget_prototypes(L)
         abi.gram_prototypes(L)
         abi.cross_prototypes(L)
+        abi.reg_prototypes(L)
         _lib = L
     return _lib
 
@@ -75,7 +76,9 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_engine_run_budget_clim", "greb_engine_run_budget_ens", "greb_engine_run_budget_lin",
            "greb_gram_create", "greb_gram_destroy", "greb_gram_reduce_dev", "greb_engine_run_gram", "greb_engine_run_budget_gram",
            "greb_cross_create", "greb_cross_destroy", "greb_cross_add_year_dev", "greb_cross_finish_dev", "greb_engine_run_cross",
-           "greb_engine_run_budget_cross"]
+           "greb_engine_run_budget_cross",
+           "greb_reg_create", "greb_reg_destroy", "greb_reg_add_year_dev", "greb_reg_finish_dev", "greb_engine_run_reg",
+           "greb_engine_run_budget_reg"]
 
 
 def _check(rc: int, h=None):
@@ -273,7 +276,7 @@ class Engine:
         return monthly, budget, yearly
 
     def _reduced(self, name: str, records, co2, plan, *args):
-        """Call the reduced run `name` ("diag", "clim", "ens", "lin", "gram", "cross") over `records`: "state" -- the year's five state
+        """Call the reduced run `name` ("diag", "clim", "ens", "lin", "gram", "cross", "reg") over `records`: "state" -- the year's five state
         records (greb_engine_run_<name>) --, "budget" -- its thirteen flux terms -- or a budget.Combo -- sums of them
         (greb_engine_run_budget_<name>).  `args`: what follows the plan in the C call."""
         from . import budget
@@ -380,6 +383,21 @@ class Engine:
         self._reduced("cross", records, co2, plan, i32(out[0]), i32(out[1]), i32(out[2]), i32(out[3]), f32(out[4]), i32(out[5]),
                       f32(out[6]), abi.fptr(yearly))
         return cross.Result(*out, yearly, names)
+
+    def run_reg(self, years: int, co2_ppm, plan, records="state"):
+        """The scenario run of run() that hands back only the regression products of `plan` (regress.Plan): per member, term
+        and point the slope, the intercept and R2 of the least-squares line of the term's yearly quantity on the member's own
+        yearly index -- a regional mean of its records, e.g. its annual global-mean warming -- and the index series itself,
+        made on the device year by year (greb_engine_run_reg).  Returns a regress.Result: the maps
+        [n_members][n_terms][ny][nx], index [n_members][years][n_indices] (a product the plan does not select is None).  State,
+        clock and yearly are those of run() over the same years.  records: as in run_diag; the plan's n_vars must be that
+        variable count."""
+        from . import budget, regress
+        co2, yearly = self._run_arrays(years, co2_ppm)
+        names = budget.record_names(records)
+        out = regress.empty_products(plan, years)
+        self._reduced("reg", records, co2, plan, *[None if a is None else abi.fptr(a) for a in out], abi.fptr(yearly))
+        return regress.Result(*out, yearly, names)
 
     def state(self, member: int = 0) -> np.ndarray:
         s = np.empty((5, self.ny, self.nx), np.float32)

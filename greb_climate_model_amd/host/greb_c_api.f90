@@ -36,6 +36,15 @@ module greb_c_api
      real(c_float) :: thr
   end type greb_cross_event
 
+  ! an index and a term of the regression output (greb_reg_create): variable (0-based), selector and rel as in
+  ! greb_cross_event; an index is the mean over `region` (0: the globe), a term names the index it is regressed on (0-based)
+  type, bind(C) :: greb_reg_index
+     integer(c_int32_t) :: var, sel, rel, region
+  end type greb_reg_index
+  type, bind(C) :: greb_reg_term
+     integer(c_int32_t) :: var, sel, rel, index
+  end type greb_reg_term
+
   interface
      subroutine greb_params_default(p) bind(C, name="greb_params_default")
        import :: greb_params
@@ -299,6 +308,56 @@ module greb_c_api
           peak, peak_year, fraction, yearly) bind(C, name="greb_engine_run_budget_cross")
        import :: c_int, c_ptr, c_float
        type(c_ptr), value :: eng, combo, plan, first, last, stay, count, peak, peak_year, fraction
+       integer(c_int), value :: years, n_out
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
+     ! regression output (greb_reg.hip): a plan = grid, member count, variables per month, region_w(nx,ny,n_regions) as
+     ! greb_diag_create takes it (c_null_ptr with n_regions = 0), control(n_members) (0-based; c_null_ptr: no control map),
+     ! indices(n_indices), terms(n_terms) and the products `what` (GREB_R_* of greb_engine.h)
+     integer(c_int) function greb_reg_create(nx, ny, n_members, n_vars, region_w, n_regions, control, indices, n_indices, terms, &
+          n_terms, what, plan) bind(C, name="greb_reg_create")
+       import :: c_int, c_ptr, greb_reg_index, greb_reg_term
+       integer(c_int), value :: nx, ny, n_members, n_vars, n_regions, n_indices, n_terms, what
+       type(c_ptr), value :: region_w, control
+       type(greb_reg_index), intent(in) :: indices(*)
+       type(greb_reg_term), intent(in) :: terms(*)
+       type(c_ptr), intent(out) :: plan
+     end function
+     integer(c_int) function greb_reg_destroy(plan) bind(C, name="greb_reg_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan
+     end function
+     ! device pointers (c_ptr): year k (0-based since the last finish) x_dev(nx,ny,n_vars,12,n_members) into the state, and
+     ! with GREB_R_INDEX that year's index_dev(n_indices,n_members); launches on `stream`, no synchronisation
+     integer(c_int) function greb_reg_add_year_dev(plan, device, x_dev, k, index_dev, stream) bind(C, name="greb_reg_add_year_dev")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan, x_dev, index_dev, stream
+       integer(c_int), value :: device, k
+     end function
+     ! the maps of the n_years years added, each float (nx,ny,n_terms,n_members); c_null_ptr where the plan does not select
+     ! a product
+     integer(c_int) function greb_reg_finish_dev(plan, device, n_years, slope_dev, intercept_dev, r2_dev, stream) &
+          bind(C, name="greb_reg_finish_dev")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan, slope_dev, intercept_dev, r2_dev, stream
+       integer(c_int), value :: device, n_years
+     end function
+     ! greb_engine_run that delivers only the plan's regression products: the float maps (nx,ny,n_terms,n_members) and
+     ! index(n_indices,years,n_members); host arrays passed as c_loc(...), c_null_ptr where the plan does not select a product
+     integer(c_int) function greb_engine_run_reg(eng, years, co2_ppm, plan, slope, intercept, r2, index, yearly) &
+          bind(C, name="greb_engine_run_reg")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, plan, slope, intercept, r2, index
+       integer(c_int), value :: years
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
+     ! ... of the year's budget records: the 13 flux terms (combo = c_null_ptr) or the n_out rows of combo(13,n_out)
+     integer(c_int) function greb_engine_run_budget_reg(eng, years, co2_ppm, combo, n_out, plan, slope, intercept, r2, index, &
+          yearly) bind(C, name="greb_engine_run_budget_reg")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, combo, plan, slope, intercept, r2, index
        integer(c_int), value :: years, n_out
        real(c_float), intent(in) :: co2_ppm(*)
        real(c_float), intent(out) :: yearly(*)

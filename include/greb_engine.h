@@ -586,6 +586,95 @@ int greb_engine_run_budget_cross(greb_engine* e, int years, const float* co2_ppm
                                  int32_t* first, int32_t* last, int32_t* stay, int32_t* count, float* peak, int32_t* peak_year,
                                  float* fraction, float* yearly);
 
+/* ---- regression output: each member's records per unit of its own index, made on the device -----------
+ * The other plans reduce along space, time, the members, into the fluxes and at thresholds; none relates a record to a
+ * scalar the run itself produces.  The local change per degree of the member's OWN global-mean warming (pattern scaling),
+ * polar amplification, albedo or humidity per degree: the regressor is known only once the year has been reduced in
+ * space, so sum g*y over the years is not a function of any sums the other plans keep (greb_clim's TREND regresses on
+ * the year number).  A plan holds the grid, n_members, n_vars (1 ... GREB_MAX_RECORD_VARS), the region weights
+ * region_w[n_regions][ny][nx] as greb_diag_create takes them (region 0 is the globe), optionally control[n_members]
+ * (-1 ... n_members-1), the products `what`, 1 ... GREB_REG_MAX_INDICES indices {var, sel, rel, region} and
+ * 1 ... GREB_REG_MAX_TERMS terms {var, sel, rel, index}; var, sel and rel mean what they mean in greb_cross_event.
+ * THE ORDER OF OPERATIONS IS THE DEFINITION:
+ *   term quantity  y of year k, member m, point i: exactly greb_cross's quantity q of (var, sel, rel) -- a month selector
+ *                  gives the fp32 record itself, a season selector the fp64 day-weighted sum in calendar order divided by
+ *                  the season's days and rounded to fp32, rel = 1 ONE fp32 subtraction of the control's same expression,
+ *                  a quiet NaN for a member without a control.
+ *   index          g of year k, member m: r[mo] = the fp32 GREB_D_REGIONS value of (m, mo, var, region) under the plan's
+ *                  weights, made by the device code of greb_diag_reduce_dev (the bits a greb_diag plan over the same
+ *                  weights returns); a = r[sel] for a month selector, the season formula above applied to the twelve r
+ *                  for a season selector; g = a for rel = 0, g = a - a_ctl as ONE fp32 subtraction for rel = 1 (a quiet
+ *                  NaN without a control).
+ *   state          fp64 sums of values centred on year 0.  Year k = 0 STORES y0 = y (fp32) and Sy = Sgy = Syy = 0 per
+ *                  (member, term, point), g0 = g (fp32) and Sg = Sgg = 0 per (member, index): no clearing pass, a plan
+ *                  serves period after period.  For k >= 1, G = (double)g - (double)g0, Y = (double)y - (double)y0 and
+ *                    Sg = Sg + G    Sgg = Sgg + G*G    Sy = Sy + Y    Sgy = Sgy + G*Y    Syy = Syy + Y*Y
+ *                  each one multiply, then one add, never fused.  A NaN propagates.  Centring makes a constant series
+ *                  give exact zeros and loses nothing to the 288 K offset.
+ *   finish         over n years, every step a separate fp64 operation:
+ *                    Sxx = Sgg - Sg*Sg/n    Sxy = Sgy - Sg*Sy/n    Syc = Syy - Sy*Sy/n    b = Sxy/Sxx
+ * Products, each rounded to fp32 once:
+ *   GREB_R_SLOPE      [member][term][ny][nx]  (float)b
+ *   GREB_R_INTERCEPT  [member][term][ny][nx]  (float)(((double)y0 + Sy/n) - b*((double)g0 + Sg/n))
+ *   GREB_R_R2         [member][term][ny][nx]  (float)((Sxy*Sxy)/(Sxx*Syc))
+ *   GREB_R_INDEX      per year [n_members][n_indices], the fp32 g; greb_engine_run_reg delivers [n_members][years][n_indices]
+ * All three maps are a quiet NaN where n < 2 or Sxx is not > 0; R2 also where Syc is not > 0.  (No square root: its bits
+ * would be the one thing numpy and the device might not share.)  Every element has one owner (no atomics): results are
+ * deterministic and a member's numbers do not depend on the batch it is in.
+ * Device memory, per device on first use: 20 bytes per (member, term, point) -- y0, Sy, Sgy -- and 8 more for Syy where
+ * GREB_R_R2 is selected (28: 1.06 GB for 512 members x 16 terms at 96 x 48), the regional means of one year
+ * [member][12][n_vars][1 + n_regions] with greb_diag's scratch, and 28 bytes per (member, index).  greb_engine_run_reg adds
+ * one map [member][term][ny][nx] of floats, through which the selected maps leave one after the other, and with
+ * GREB_R_INDEX the series [member][years][n_indices], the only thing that grows with the years. */
+#define GREB_R_SLOPE     1u
+#define GREB_R_INTERCEPT 2u
+#define GREB_R_R2        4u
+#define GREB_R_INDEX     8u
+#define GREB_REG_MAX_INDICES 8
+#define GREB_REG_MAX_TERMS   16
+#define GREB_REG_MAX_MEMBERS 65535
+typedef struct greb_reg_index {
+  int32_t var, sel, rel, region;
+} greb_reg_index;
+typedef struct greb_reg_term {
+  int32_t var, sel, rel, index;
+} greb_reg_term;
+typedef struct greb_reg greb_reg;
+/* A plan.  Host data only, validated without touching a device.  GREB_E_INVALID with a message that names the offender --
+ * field, index, term or member (greb_engine_last_error(NULL)): a grid greb_diag_create does not take, n_members outside
+ * 1 ... GREB_REG_MAX_MEMBERS, n_vars,
+ * n_regions, n_indices or n_terms out of range or their arrays NULL, `what` zero or with unknown bits, a region weight that
+ * is not finite or outside [0, 1] or a region of zero weight (as greb_diag_create), an index's var, sel or region or a
+ * term's var, sel or index out of range, rel not 0 or 1, rel = 1 without `control` -- of a term, of the index a term names,
+ * or of an index no term names --, a control index out of range.  control may be NULL. */
+int greb_reg_create(int nx, int ny, int n_members, int n_vars, const float* region_w, int n_regions, const int32_t* control,
+                    const greb_reg_index* indices, int n_indices, const greb_reg_term* terms, int n_terms, unsigned what,
+                    greb_reg** out);
+int greb_reg_destroy(greb_reg* r); /* waits for the device before it frees the state */
+/* Year k (0-based) of the current period, one model year x_dev[n_members][12][n_vars][ny][nx] on HIP device `device` (16-byte
+ * aligned), into the state; with GREB_R_INDEX also that year's index_dev[n_members][n_indices] (NULL is GREB_E_INVALID
+ * then, and the pointer is ignored otherwise).  k must be the number of years added since the last finish.  Launches on
+ * `stream` (a hipStream_t, may be NULL) and does not synchronise; the calls of one period must be ordered among themselves. */
+int greb_reg_add_year_dev(greb_reg* r, int device, const float* x_dev, int k, float* index_dev, void* stream);
+/* The maps of the n_years years added since the last finish (n_years must be that number) to device memory,
+ * [n_members][n_terms][ny][nx] each, 16-byte aligned.  A pointer whose product the plan does not select is ignored and
+ * may be NULL; a selected product with a NULL pointer is GREB_E_INVALID.  Both _dev calls check their arguments before
+ * any device query; without a device they are GREB_E_NOGPU (no CPU path). */
+int greb_reg_finish_dev(greb_reg* r, int device, int n_years, float* slope_dev, float* intercept_dev, float* r2_dev, void* stream);
+/* greb_engine_run that delivers ONLY the plan's products over the `years` years of this call, one period, to host memory:
+ * the maps [n_members][n_terms][ny][nx], index [n_members][years][n_indices] (unselected products as above).  The plan must
+ * have n_vars = 5; one made for another grid, member count or variable count, a selected product with a NULL pointer or
+ * a plan with an unfinished period is GREB_E_INVALID, decided before any device work; a refused call leaves the engine
+ * usable.  Each year is integrated into one of the engine's two one-year staging slots and reduced and added to the
+ * state behind it on the same stream; nothing leaves before the end, and the run makes no copy stream and no events.
+ * co2_ppm, yearly, the model clock, the state the engine is left in and the kernels that integrate are those of
+ * greb_engine_run over the same years, bit for bit. */
+int greb_engine_run_reg(greb_engine* e, int years, const float* co2_ppm, greb_reg* r, float* slope, float* intercept, float* r2,
+                        float* index, float* yearly);
+/* ... over the year's BUDGET records, as greb_engine_run_budget_clim: the plan must have n_vars = V. */
+int greb_engine_run_budget_reg(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_reg* r,
+                               float* slope, float* intercept, float* r2, float* index, float* yearly);
+
 /* ---- per-member forcing: regional and seasonal CO2, insolation tables and scale --------------------
  * Members of one engine may differ in the forcing itself, not only in the CO2 level: CO2 raised in one hemisphere, over
  * land or ocean only or in one half of the year, a changed solar constant, a changed latitudinal or seasonal distribution
