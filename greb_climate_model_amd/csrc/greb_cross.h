@@ -6,28 +6,22 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "greb_yearwalk.h"
+
 namespace greb {
 
 constexpr int kCrossThreads = 256;
 constexpr int kCrossMaxEvents = 16;
-constexpr int kCrossSelectors = 17; // 0 ... 11 the months, 12 ... 16 DJF MAM JJA SON ANN
 
-// The plan's events as the update kernel walks them: sorted by variable, then by selector.  The events of distinct
-// variable v are ev[vstart[v]] ... ev[vstart[v + 1] - 1].  Travels by value in the kernel arguments and is read through
-// the scalar cache.
-struct CrossTable {
-  struct Ev {
-    int sel, rel, dir; // selector, member minus control, +1: q >= thr hits, -1: q <= thr
-    float thr;
-    int out;           // the event's index in the caller's order: where its state and products lie
-  } ev[kCrossMaxEvents];
-  int n_vars_used;                 // distinct variables among the events
-  int var[kCrossMaxEvents];        // [n_vars_used] the variable
-  int vstart[kCrossMaxEvents + 1]; // [n_vars_used + 1]
-  int months[kCrossMaxEvents];     // [n_vars_used] bit mo: the variable's events need month mo of the member
-  int ctl_months[kCrossMaxEvents]; // ... of the member's control (the months of the `rel` events)
-  int rel_sels[kCrossMaxEvents];   // [n_vars_used] bit s: an event with selector s is `rel`
+// An event as the update kernel walks the plan's (greb_yearwalk.h: sorted by variable, then by selector).
+struct CrossEv {
+  int sel, rel, dir; // selector, member minus control, +1: q >= thr hits, -1: q <= thr
+  float thr;
+  int out;           // the event's index in the caller's order: where its state and products lie
 };
+using CrossTable = YearTable<CrossEv, kCrossMaxEvents>;
+// (the kernels' scalar loads address the table in the kernel arguments)
+static_assert(sizeof(CrossTable) == 648 && offsetof(CrossTable, vstart) == 388, "the layout greb_cross.hip was written to");
 
 // The state words, each [n_members][n_events][np] (null: the plan's products do not need it), and the hit bytes of the
 // current year, likewise (null without FRACTION).

@@ -6,16 +6,11 @@
 // follow the years: the first and the last year that hit, the last year that missed, the number of hits, the peak and
 // its year.
 //
-//   cross_update_kernel    grid (blocks of 256 point quads, member, distinct variable of the events).  A lane owns four
-//                          consecutive points.  It loads the months its variable's events need -- the month mask is
-//                          wave-uniform and decided by scalar branches -- as 16-byte vectors, the control's too where an
-//                          event is `rel`, so that every record byte is read once as the member's own data and at most
-//                          once as a control however many events share the variable.  Then it walks the variable's
-//                          events, which the host sorted by selector (a uniform loop over a table in the kernel
-//                          arguments, read through the scalar cache): the quantity of a selector is formed once, and
-//                          every event updates its state words [member][event][np] with 16-byte loads and stores, a
-//                          wavefront's access being one contiguous KiB.  Year k = 0 STORES the state: no clearing pass.
-//                          With FRACTION it also writes the year's hit bytes [member][event][np].
+//   cross_update_kernel    grid (blocks of 256 point quads, member, distinct variable of the events): year_walk of
+//                          greb_yearwalk.h, which loads the months the variable's events need once and forms each
+//                          selector's quantity once.  Every event updates its state words [member][event][np] with 16-byte
+//                          loads and stores, a wavefront's access being one contiguous KiB.  Year k = 0 STORES the state:
+//                          no clearing pass.  With FRACTION it also writes the year's hit bytes [member][event][np].
 //   cross_fraction_kernel  grid (blocks of point quads, group, event).  Adds the group's hit bytes in ascending member
 //                          index, four points per 32-bit load, and stores (float)((double)c / (double)n_g).
 //   cross_finish_kernel    the state words -> the selected maps; STAY = last_miss + 1 where that is a year of the period.
@@ -25,15 +20,11 @@
 // the same IEEE operations; it is seasons_of of greb_clim.hip applied to one year): this file is built with
 // -ffp-contract=off (build.py: EXTRA_FLAGS), so that no multiply is fused into the add that follows it.
 #include "greb_cross.h"
-#include "greb_season.h"
 
 namespace greb {
 namespace {
 
 using season::f4;
-using season::kMonths;
-using season::months_of;
-using season::quantity; // (greb_season.h: one statement of the yearly quantity for greb_cross and greb_reg)
 typedef int i4 __attribute__((ext_vector_type(4)));
 
 // one event's state words of one quad: g = the quad's index in [member][event][np / 4]
@@ -98,42 +89,9 @@ __device__ inline void update_event(const CrossState& st, size_t g, const f4 q, 
 
 template <bool FIRST>
 __global__ __launch_bounds__(kCrossThreads) void cross_update_kernel(CrossUpdateArgs a) {
-  const size_t gp = a.np >> 2, quad = (size_t)blockIdx.x * kCrossThreads + threadIdx.x;
-  if (quad >= gp) return;
-  const int m = (int)blockIdx.y, v = (int)blockIdx.z;
-  const int var = a.t.var[v], own = a.t.months[v], rel_sels = a.t.rel_sels[v];
-  const int c = a.control ? a.control[m] : -1;
-  const int ctl = c >= 0 ? a.t.ctl_months[v] : 0;
-  const size_t mon = (size_t)a.n_vars * gp; // quads of one month of one member
-  const f4* xm = reinterpret_cast<const f4*>(a.x) + ((size_t)m * kMonths * a.n_vars + var) * gp + quad;
-  const f4* xc = reinterpret_cast<const f4*>(a.x) + ((size_t)(c >= 0 ? c : 0) * kMonths * a.n_vars + var) * gp + quad;
-  f4 x[kMonths], y[kMonths];
-#pragma unroll
-  for (int mo = 0; mo < kMonths; ++mo) {
-    x[mo] = f4{0.f, 0.f, 0.f, 0.f};
-    if (own >> mo & 1) x[mo] = xm[mo * mon];
-  }
-#pragma unroll
-  for (int mo = 0; mo < kMonths; ++mo) {
-    y[mo] = f4{0.f, 0.f, 0.f, 0.f};
-    if (ctl >> mo & 1) y[mo] = xc[mo * mon];
-  }
-  const float nan = __builtin_nanf("");
-  const f4 nan4 = {nan, nan, nan, nan};
-  int i = a.t.vstart[v];
-  const int end = a.t.vstart[v + 1];
-#pragma unroll
-  for (int s = 0; s < kCrossSelectors; ++s) {
-    if (i >= end || a.t.ev[i].sel != s) continue; // (uniform)
-    const f4 own_a = quantity(s, x);
-    f4 rel_q = nan4; // a member without a control: a quiet NaN, which never hits
-    if ((rel_sels >> s & 1) && c >= 0) rel_q = own_a - quantity(s, y); // ONE fp32 subtraction
-    for (; i < end && a.t.ev[i].sel == s; ++i) {
-      const CrossTable::Ev ev = a.t.ev[i];
-      const size_t g = ((size_t)m * a.n_events + ev.out) * gp + quad;
-      update_event<FIRST>(a.st, g, ev.rel ? rel_q : own_a, ev.dir, ev.thr, a.k);
-    }
-  }
+  year_walk<kCrossThreads>(a.t, a.x, a.control, a.np, a.n_vars, a.n_events, [st = a.st, k = a.k](const CrossEv& ev, size_t g, const f4 q) {
+    update_event<FIRST>(st, g, q, ev.dir, ev.thr, k); // (a member without a control: a quiet NaN, which never hits)
+  });
 }
 
 __global__ __launch_bounds__(kCrossThreads) void cross_fraction_kernel(const unsigned* __restrict__ hit, const int* __restrict__ offs,
@@ -175,18 +133,9 @@ __global__ __launch_bounds__(kCrossThreads) void cross_finish_kernel(CrossFinish
 hipError_t launch_cross_update(const CrossUpdateArgs& a, hipStream_t s) {
   const CrossTable& t = a.t;
   if (!a.x || a.np < 4 || (a.np & 3) || a.n_members < 1 || a.n_vars < 1 || a.n_events < 1 || a.n_events > kCrossMaxEvents ||
-      a.k < 0 || t.n_vars_used < 1 || t.n_vars_used > a.n_events || t.vstart[0] != 0 || t.vstart[t.n_vars_used] != a.n_events ||
-      a.n_members > 65535 || (a.st.peak == nullptr) != (a.st.peak_year == nullptr))
+      a.k < 0 || a.n_members > 65535 || (a.st.peak == nullptr) != (a.st.peak_year == nullptr) ||
+      !year_table_ok(t, a.n_vars, a.n_events, a.control != nullptr))
     return hipErrorInvalidValue;
-  for (int v = 0; v < t.n_vars_used; ++v) { // what the kernel indexes with: nothing may point outside the records or the state
-    if (t.var[v] < 0 || t.var[v] >= a.n_vars || t.vstart[v + 1] <= t.vstart[v]) return hipErrorInvalidValue;
-    for (int i = t.vstart[v]; i < t.vstart[v + 1]; ++i) {
-      const CrossTable::Ev& ev = t.ev[i];
-      if (ev.sel < 0 || ev.sel >= kCrossSelectors || ev.out < 0 || ev.out >= a.n_events || (i > t.vstart[v] && ev.sel < t.ev[i - 1].sel) ||
-          (months_of(ev.sel) & ~t.months[v]) || (ev.rel && (!a.control || (months_of(ev.sel) & ~t.ctl_months[v]) || !(t.rel_sels[v] >> ev.sel & 1))))
-        return hipErrorInvalidValue;
-    }
-  }
   const size_t gp = a.np >> 2;
   const dim3 grid((unsigned)((gp + kCrossThreads - 1) / kCrossThreads), (unsigned)a.n_members, (unsigned)t.n_vars_used);
   if (a.k == 0) hipLaunchKernelGGL(cross_update_kernel<true>, grid, dim3(kCrossThreads), 0, s, a);

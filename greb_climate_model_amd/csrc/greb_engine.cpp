@@ -194,15 +194,6 @@ int greb::host::use_device(const char* who, int device) {
   return 0;
 }
 
-int greb::host::ensure(greb_engine* e, float** buf, size_t* cap, size_t n) {
-  if (*cap >= n) return 0;
-  if (*buf) HIP_TRY(e, hipFree(*buf));
-  *buf = nullptr; *cap = 0;
-  HIP_TRY(e, dev_alloc(buf, n));
-  *cap = n;
-  return 0;
-}
-
 // The wavefront slots of a device that one-launch circulation calls may fill, across the engines of this process.
 // Such a launch waits inside the kernel for its own tasks, so all of them must be resident at once; two engines driven
 // side by side (ensemble.run_beside: config 5's 62 + 2 members) share the device, and the sum of what they launch must fit.

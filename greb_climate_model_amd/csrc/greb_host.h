@@ -149,7 +149,16 @@ void adopt(T*& mine, DevBuf<T>& made) { if (mine) (void)hipFree(mine); mine = ma
 inline bool grid_ok(int nx, int ny) { return !(nx < 12 || (nx & 3) || ny < 5 || ny > kMaxNy); }
 // `device` exists and is current from here on; `who` ends in ": "
 int use_device(const char* who, int device);
-int ensure(greb_engine* e, float** buf, size_t* cap, size_t n);
+// *buf holds at least n elements: a larger array in place of a smaller one, whose contents go
+template <typename T>
+int ensure(greb_engine* e, T** buf, size_t* cap, size_t n) {
+  if (*cap >= n) return 0;
+  if (*buf) HIP_TRY(e, hipFree(*buf));
+  *buf = nullptr; *cap = 0;
+  HIP_TRY(e, dev_alloc(buf, n));
+  *cap = n;
+  return 0;
+}
 
 // ---- the engine's data and years (greb_engine.cpp)
 void compute_row_tables(const greb_params& p, float kappa, int nx, int ny, RowTables& g);

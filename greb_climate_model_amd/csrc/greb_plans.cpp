@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <initializer_list>
 #include <new>
 
 #include "greb_diag.h"
@@ -22,23 +23,24 @@ using namespace greb::host;
 static_assert(kGramMaxUsed == GREB_GRAM_MAX_USED && kGramMaxBlocks == GREB_GRAM_MAX_BLOCKS, "greb_gram.h mirrors include/greb_engine.h");
 static_assert(kCrossMaxEvents == GREB_CROSS_MAX_EVENTS && sizeof(greb_cross_event) == 20, "greb_cross.h mirrors include/greb_engine.h");
 static_assert(kRegMaxTerms == GREB_REG_MAX_TERMS && kRegMaxIndices == GREB_REG_MAX_INDICES && sizeof(greb_reg_index) == 16 &&
-                  sizeof(greb_reg_term) == 16 && kRegSelectors == kCrossSelectors && kRegMaxMembers == GREB_REG_MAX_MEMBERS,
+                  sizeof(greb_reg_term) == 16 && season::kSelectors == 17 && kRegMaxMembers == GREB_REG_MAX_MEMBERS,
               "greb_reg.h mirrors include/greb_engine.h");
 static_assert(kFluxTerms == GREB_NBUDGET && kFluxMaxOut == GREB_MAX_RECORD_VARS, "greb_fluxes.h mirrors include/greb_engine.h");
 
 namespace {
 constexpr int kStateVars = GREB_NVAR_OUT; // the variables of a year of state records
 
-int check_n_vars(const std::string& who, int n_vars) {
-  if (n_vars >= 1 && n_vars <= GREB_MAX_RECORD_VARS) return 0;
-  return fail(nullptr, GREB_E_INVALID, who + ": n_vars = " + std::to_string(n_vars) + " (1 ... " + std::to_string(GREB_MAX_RECORD_VARS) + ")");
+// a count `name` of the caller's is 1 ... max
+int check_count(greb_engine* e, const std::string& who, const char* name, int n, int max) {
+  if (n >= 1 && n <= max) return 0;
+  return fail(e, GREB_E_INVALID, who + ": " + name + " = " + std::to_string(n) + " (1 ... " + std::to_string(max) + ")");
 }
+int check_n_vars(const std::string& who, int n_vars) { return check_count(nullptr, who, "n_vars", n_vars, GREB_MAX_RECORD_VARS); }
 
 // combo[n_out][GREB_NBUDGET] checked and packed for the kernel arguments
 int make_combo(greb_engine* e, const std::string& who, const float* combo, int n_out, FluxCombo* out) {
   if (!combo) return fail(e, GREB_E_INVALID, who + ": `combo` is NULL");
-  if (n_out < 1 || n_out > GREB_MAX_RECORD_VARS)
-    return fail(e, GREB_E_INVALID, who + ": n_out = " + std::to_string(n_out) + " (1 ... " + std::to_string(GREB_MAX_RECORD_VARS) + ")");
+  if (int rc = check_count(e, who, "n_out", n_out, GREB_MAX_RECORD_VARS)) return rc;
   FluxCombo c{};
   c.n_out = n_out;
   for (int k = 0; k < n_out; ++k) {
@@ -167,30 +169,146 @@ int check_engine(greb_engine* e, const std::string& who, int nx, int ny, int nm)
   return 0;
 }
 
-// The five products of a climatology or an ensemble plan.  An output slot holds [row][record] of each selected product
-// in turn, 16-byte aligned (np % 4 == 0); the rows are the members (clim) or the groups (ens).
+const char* const kSelRange = " (0 ... 11: a month; 12 ... 16: DJF, MAM, JJA, SON, ANN)"; // a selector of greb_season.h
+
+// What every create says first: somewhere to put the plan, the grid and, where the kind asks these next, the variable
+// count and the member count.
+template <typename Plan>
+int begin_create(const std::string& who, Plan** out, int nx, int ny, const int* n_vars, const int* n_members) {
+  if (!out) return fail(nullptr, GREB_E_INVALID, who + ": `out` is NULL");
+  *out = nullptr;
+  if (int rc = check_grid(who, nx, ny)) return rc;
+  if (n_vars) if (int rc = check_n_vars(who, *n_vars)) return rc;
+  if (n_members && *n_members < 1) return fail(nullptr, GREB_E_INVALID, who + ": n_members = " + std::to_string(*n_members));
+  return 0;
+}
+// member m's control is none or a member (no control map: nothing to check) ...
+int check_control_of(const std::string& who, const int32_t* control, int m, int n_members) {
+  if (!control || (control[m] >= -1 && control[m] < n_members)) return 0;
+  return fail(nullptr, GREB_E_INVALID, who + ": member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
+                                           " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
+}
+// ... and every member's
+int check_control(const std::string& who, const int32_t* control, int n_members) {
+  for (int m = 0; m < n_members; ++m)
+    if (int rc = check_control_of(who, control, m, n_members)) return rc;
+  return 0;
+}
+// The members a lin or gram plan uses (`use` NULL: all) in ascending member index, and their controls where there is a
+// map: each member's control is checked, a used one needs one, and one member at least is used.
+int used_members(const std::string& who, const int32_t* use, const int32_t* control, int n_members, std::vector<int>* member,
+                 std::vector<int>* control_of_used) {
+  for (int m = 0; m < n_members; ++m) {
+    if (int rc = check_control_of(who, control, m, n_members)) return rc;
+    if (use && !use[m]) continue;
+    if (control && control[m] < 0)
+      return fail(nullptr, GREB_E_INVALID, who + ": member " + std::to_string(m) +
+                                               " is used but has no control (control = -1) while a control map is given");
+    member->push_back(m);
+    if (control) control_of_used->push_back(control[m]);
+  }
+  if (member->empty()) return fail(nullptr, GREB_E_INVALID, who + ": no used member (`use` is zero everywhere)");
+  return 0;
+}
+// The lists of the members by group (ens, cross; `what` = "member", `of` = "group") or of the records by block (gram): group
+// g is member[offs[g] ... offs[g + 1]) in ascending index, of the members with group[m] = g (-1: in none).  `also(m)` is
+// what else the kind asks of member m, once its group is in range.
+int group_lists(const std::string& who, const char* what, const char* of, const int32_t* group, int n_groups, int n_members,
+                std::vector<int>* offs, std::vector<int>* member, const std::function<int(int)>& also = nullptr) {
+  offs->assign((size_t)n_groups + 1, 0);
+  for (int m = 0; m < n_members; ++m) {
+    if (group[m] < -1 || group[m] >= n_groups)
+      return fail(nullptr, GREB_E_INVALID, who + ": " + what + " " + std::to_string(m) + ": " + of + " = " + std::to_string(group[m]) +
+                                               " (-1 = none, or 0 ... " + std::to_string(n_groups - 1) + ")");
+    if (also) if (int rc = also(m)) return rc;
+    if (group[m] >= 0) ++(*offs)[(size_t)group[m] + 1];
+  }
+  for (int g = 0; g < n_groups; ++g) {
+    if ((*offs)[(size_t)g + 1] == 0) return fail(nullptr, GREB_E_INVALID, who + ": " + of + " " + std::to_string(g) + " is empty");
+    (*offs)[(size_t)g + 1] += (*offs)[(size_t)g];
+  }
+  member->resize((size_t)offs->back());
+  std::vector<int> at(offs->begin(), offs->end() - 1);
+  for (int m = 0; m < n_members; ++m)
+    if (group[m] >= 0) (*member)[(size_t)at[(size_t)group[m]]++] = m;
+  return 0;
+}
+
+// The years a clim, cross or reg plan has taken since the last finish: one period is followed at a time, on one device.
+// `holds` says what of it lies there ("sums are", "state is").
+struct Period {
+  const char* holds;
+  int added = 0, added_device = -1;
+  int check_add(const std::string& who, int k, int device) const {
+    if (k != added)
+      return fail(nullptr, GREB_E_INVALID, who + ": k = " + std::to_string(k) + ", but " + std::to_string(added) +
+                                               " years were added since the last finish (years go in ascending order, k = 0 first)");
+    return k > 0 ? check_device(who, device) : 0;
+  }
+  int check_finish(const std::string& who, int n_years, int device) const {
+    if (n_years != added || n_years < 1)
+      return fail(nullptr, GREB_E_INVALID, who + ": n_years = " + std::to_string(n_years) + ", but " + std::to_string(added) +
+                                               " years were added since the last finish");
+    return check_device(who, device);
+  }
+  int check_idle(greb_engine* e, const std::string& who) const { // a scenario run follows a period of its own
+    if (added == 0) return 0;
+    return fail(e, GREB_E_INVALID, who + ": the plan holds " + std::to_string(added) + " years of an unfinished period");
+  }
+  void advance(int k, int device) { added = k + 1; added_device = device; }
+  void reset() { added = 0; added_device = -1; }
+ private:
+  int check_device(const std::string& who, int device) const {
+    if (device == added_device) return 0;
+    return fail(nullptr, GREB_E_INVALID, who + ": device " + std::to_string(device) + ", but this period's " + holds + " on device " +
+                                             std::to_string(added_device));
+  }
+};
+
+// The products of a plan: per product the entry points' parameter (without "_dev"), what selects it, the elements of
+// one row's record (0: not selected) and its rows where they are its own (lin).  An output slot holds [row][record] of each
+// selected product in turn, 16-byte aligned (np % 4 == 0); the rows are the members (clim) or the groups (ens).
 struct Products {
-  const char* const* names; // the entry points' parameters (without "_dev")
-  const char* const* flags; // what selects each
-  size_t size[5] = {};      // floats of one row's record (0: not selected)
-  size_t rows = 0, at[5] = {}, out_slot = 0;
-  void layout(size_t n_rows) {
-    rows = n_rows; out_slot = 0;
-    for (int i = 0; i < 5; ++i) { at[i] = out_slot; out_slot += rows * size[i]; }
+  struct One { const char* name; const char* flag; size_t size, rows = 0; };
+  static constexpr int kMax = 6;
+  One p[kMax] = {};
+  int n = 0;
+  size_t at[kMax] = {}, out_slot = 0;
+  Products(std::initializer_list<One> l) { for (const One& o : l) p[n++] = o; }
+  void layout(size_t n_rows = 0) {
+    out_slot = 0;
+    for (int i = 0; i < n; ++i) {
+      if (n_rows) p[i].rows = n_rows;
+      at[i] = out_slot; out_slot += p[i].rows * p[i].size;
+    }
   }
   // every selected product has somewhere to go (suffix "_dev": on the device); what is not selected is ignored
-  int check(greb_engine* e, const std::string& who, float* p[5], const char* suffix, bool aligned) const {
-    for (int i = 0; i < 5; ++i) {
-      if (!size[i]) { p[i] = nullptr; continue; }
-      if (!p[i]) return fail(e, GREB_E_INVALID, who + ": " + flags[i] + " selected but `" + names[i] + suffix + "` is NULL");
-      if (aligned) if (int rc = check_aligned(who, p[i], std::string(names[i]) + suffix)) return rc;
+  template <typename T>
+  int check(greb_engine* e, const std::string& who, T* ptr[], const char* suffix, bool aligned) const {
+    for (int i = 0; i < n; ++i) {
+      if (!p[i].size) { ptr[i] = nullptr; continue; }
+      if (!ptr[i]) return fail(e, GREB_E_INVALID, who + ": " + p[i].flag + " selected but `" + p[i].name + suffix + "` is NULL");
+      if (aligned) if (int rc = check_aligned(who, ptr[i], std::string(p[i].name) + suffix)) return rc;
     }
     return 0;
   }
-  void pointers(float* slot, float* out[5]) const { for (int i = 0; i < 5; ++i) out[i] = size[i] ? slot + at[i] : nullptr; }
+  void pointers(float* slot, float* out[]) const { for (int i = 0; i < n; ++i) out[i] = p[i].size ? slot + at[i] : nullptr; }
 };
 
-// What run_clim and run_ens share.  Unit u of n_units is made in output slot u & 1 of *buf (slot()), and every row's
+// The year of a run of which every year is a unit: its records, then what `launch(mon, y)` enqueues -- the only thing that
+// writes output slot y & 1, hence `writing` here and not before the year.  delivers = false: nothing leaves before the end.
+template <typename Launch>
+std::function<int(const YearCalls&, int)> year_hook(greb_engine* e, const Records* src, Launch launch, bool delivers = true) {
+  return [e, src, launch, delivers](const YearCalls& run, int y) -> int {
+    const float* mon = nullptr;
+    if (int rc = src->integrate(e, run, y, &mon)) return rc;
+    if (delivers) if (int rc = run.writing(y)) return rc;
+    if (int rc = launch(mon, y)) return rc;
+    return delivers ? run.complete(y) : 0;
+  };
+}
+
+// What run_clim, run_ens and run_lin share.  Unit u of n_units is made in output slot u & 1 of *buf (slot()), and every row's
 // record of it leaves from there to its place in the caller's [row][n_units][record] arrays.
 struct ProductSink {
   greb_engine* e; const Products& pr; float** buf; size_t* cap; float* const* host; int n_units;
@@ -202,8 +320,8 @@ struct ProductSink {
       return plan_on_device();
     };
     s.deliver = [k](int u, int sl) -> int {
-      for (int i = 0; i < 5; ++i)
-        if (k.pr.size[i]) HIP_TRY(k.e, unit_to_host(k.e, k.host[i], k.n_units, u, k.slot(sl) + k.pr.at[i], k.pr.size[i], k.pr.rows));
+      for (int i = 0; i < k.pr.n; ++i)
+        if (k.pr.p[i].size) HIP_TRY(k.e, unit_to_host(k.e, k.host[i], k.n_units, u, k.slot(sl) + k.pr.at[i], k.pr.p[i].size, k.pr.p[i].rows));
       return 0;
     };
   }
@@ -255,10 +373,7 @@ DiagArgs diag_args(const greb_diag* d, const greb_diag::Dev* dv, const float* mo
 // The plan of greb_diag_create_vars for whoever makes one (`who`: "diag_create", or "reg_create" for the regional means a
 // regression plan takes its indices from): the checks, the combined weights and the reciprocals of their sums.
 int make_diag(const std::string& who, int nx, int ny, const float* region_w, int n_regions, int n_vars, greb_diag** out) {
-  if (!out) return fail(nullptr, GREB_E_INVALID, who + ": `out` is NULL");
-  *out = nullptr;
-  if (int rc = check_grid(who, nx, ny)) return rc;
-  if (int rc = check_n_vars(who, n_vars)) return rc;
+  if (int rc = begin_create(who, out, nx, ny, &n_vars, nullptr)) return rc;
   if (n_regions < 0 || n_regions > kDiagMaxRegions)
     return fail(nullptr, GREB_E_INVALID, who + ": n_regions = " + std::to_string(n_regions) + " (0 ... " +
                                              std::to_string(kDiagMaxRegions) + "; the globe is region 0 on top of them)");
@@ -346,9 +461,10 @@ int run_diag(const std::string& who, Records src, greb_engine* e, int years, con
   if (!d) return fail(e, GREB_E_INVALID, who + ": no plan (greb_diag is NULL)");
   if (int rc = src.check_plan(e, who, d->nv)) return rc;
   if (int rc = check_what(e, who, what, GREB_D_REGIONS | GREB_D_ZONAL | GREB_D_ANNUAL)) return rc;
-  if ((what & GREB_D_REGIONS) && !regions) return fail(e, GREB_E_INVALID, who + ": GREB_D_REGIONS selected but `regions` is NULL");
-  if ((what & GREB_D_ZONAL) && !zonal) return fail(e, GREB_E_INVALID, who + ": GREB_D_ZONAL selected but `zonal` is NULL");
-  if ((what & GREB_D_ANNUAL) && !annual) return fail(e, GREB_E_INVALID, who + ": GREB_D_ANNUAL selected but `annual` is NULL");
+  float* host[3] = {regions, zonal, annual};
+  const Products pr{{"regions", "GREB_D_REGIONS", what & GREB_D_REGIONS}, {"zonal", "GREB_D_ZONAL", what & GREB_D_ZONAL},
+                    {"annual", "GREB_D_ANNUAL", what & GREB_D_ANNUAL}};
+  if (int rc = pr.check(e, who, host, "", false)) return rc;
   if (!e || years < 1 || !co2_ppm) return fail(e, GREB_E_INVALID, who + ": bad argument (engine, years or co2_ppm)");
   if (int rc = check_engine(e, who, d->nx, d->ny, -1)) return rc;
   const size_t np = (size_t)e->np, nm = (size_t)e->nm, nv = (size_t)src.nv;
@@ -365,16 +481,13 @@ int run_diag(const std::string& who, Records src, greb_engine* e, int years, con
     if (int rc = src.prepare(e)) return rc;
     return diag_on_device(d, e->device, e->nm, do_r, &dv);
   };
-  s.year = [&](const YearCalls& run, int y) -> int {
-    const float* mon = nullptr;
-    if (int rc = src.integrate(e, run, y, &mon)) return rc;
-    if (int rc = run.writing(y)) return rc; // (here, not before the year: only the reduction writes the slot)
+  s.year = year_hook(e, &src, [&](const float* mon, int y) -> int {
     float* out = out_slot ? e->diag_out + (size_t)(y & 1) * out_slot : nullptr;
     const DiagArgs g = diag_args(d, dv, mon, do_r ? e->diag_reg + (size_t)y * reg_year : nullptr, (size_t)years * reg_year,
                                  do_z ? out : nullptr, do_a ? out + zon_slot : nullptr);
     HIP_TRY(e, launch_diag_year(g, e->nm, e->stream));
-    return run.complete(y);
-  };
+    return 0;
+  });
   s.deliver = [&](int y, int sl) -> int {
     float* out = e->diag_out + (size_t)sl * out_slot;
     if (do_z) HIP_TRY(e, unit_to_host(e, zonal, years, y, out, zon_year));
@@ -423,14 +536,12 @@ int greb_budget_combine_dev(const float* combo, int n_out, const float* budget_y
 
 // ---------------------------------------------------------------- climatology output (greb_clim.hip)
 // Grid, member count, each member's control and the products.  Per device: the fp64 sums and the control map's copy.
-// `added` counts the years since the last finish: one period is summed at a time, on one device.
 struct greb_clim {
   int nx = 0, ny = 0, nm = 0;
   int nv = kStateVars;          // variables per month of the records it sums
   unsigned what = 0;
   std::vector<int32_t> control; // [nm], or empty: no control map
-  int added = 0;                // years added since the last finish
-  int added_device = -1;        // ... on this device
+  Period period{"sums are"};
   struct Dev { DevBuf<double> S, T; DevBuf<int> control; };
   PerDevice<Dev> devs;
   size_t elems() const { return (size_t)nm * kClimMonths * nv * nx * ny; }
@@ -446,20 +557,14 @@ int clim_on_device(greb_clim* c, int device, greb_clim::Dev** out) {
   }, out);
 }
 
-const char* const kClimOutNames[5] = {"mean", "seasons", "trend", "mean_resp", "seasons_resp"};
-const char* const kClimFlagNames[5] = {"GREB_C_MEAN", "GREB_C_SEASONS", "GREB_C_TREND", "GREB_C_RESPONSE with GREB_C_MEAN",
-                                       "GREB_C_RESPONSE with GREB_C_SEASONS"};
 // floats of one member's record of each product of one period: MEAN, SEASONS, TREND, the MEAN response, the SEASONS response
 Products clim_products(const greb_clim* c) {
-  const size_t np = (size_t)c->nx * c->ny, mon = (size_t)kClimMonths * c->nv * np, sea = (size_t)kClimSeasons * c->nv * np;
+  const size_t np = (size_t)c->nx * c->ny;
+  const size_t mon = (c->what & GREB_C_MEAN) ? (size_t)kClimMonths * c->nv * np : 0, sea = (c->what & GREB_C_SEASONS) ? (size_t)kClimSeasons * c->nv * np : 0;
   const bool resp = (c->what & GREB_C_RESPONSE) != 0;
-  Products pr{kClimOutNames, kClimFlagNames};
-  pr.size[0] = (c->what & GREB_C_MEAN) ? mon : 0;
-  pr.size[1] = (c->what & GREB_C_SEASONS) ? sea : 0;
-  pr.size[2] = (c->what & GREB_C_TREND) ? mon : 0;
-  pr.size[3] = resp && (c->what & GREB_C_MEAN) ? mon : 0;
-  pr.size[4] = resp && (c->what & GREB_C_SEASONS) ? sea : 0;
-  return pr;
+  return {{"mean", "GREB_C_MEAN", mon}, {"seasons", "GREB_C_SEASONS", sea},
+          {"trend", "GREB_C_TREND", (c->what & GREB_C_TREND) ? (size_t)kClimMonths * c->nv * np : 0},
+          {"mean_resp", "GREB_C_RESPONSE with GREB_C_MEAN", resp ? mon : 0}, {"seasons_resp", "GREB_C_RESPONSE with GREB_C_SEASONS", resp ? sea : 0}};
 }
 
 ClimFinishArgs clim_finish_args(const greb_clim* c, const greb_clim::Dev* dv, int n_years, float* const out[5]) {
@@ -478,22 +583,14 @@ int greb_clim_create(int nx, int ny, int n_members, const int32_t* control, unsi
 }
 
 int greb_clim_create_vars(int nx, int ny, int n_members, const int32_t* control, unsigned what, int n_vars, greb_clim** out) {
-  if (!out) return fail(nullptr, GREB_E_INVALID, "clim_create: `out` is NULL");
-  *out = nullptr;
-  if (int rc = check_grid("clim_create", nx, ny)) return rc;
-  if (int rc = check_n_vars("clim_create", n_vars)) return rc;
-  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "clim_create: n_members = " + std::to_string(n_members));
+  if (int rc = begin_create("clim_create", out, nx, ny, &n_vars, &n_members)) return rc;
   if (int rc = check_what(nullptr, "clim_create", what, GREB_C_MEAN | GREB_C_SEASONS | GREB_C_TREND | GREB_C_RESPONSE)) return rc;
   if ((what & GREB_C_RESPONSE) && !(what & (GREB_C_MEAN | GREB_C_SEASONS)))
     return fail(nullptr, GREB_E_INVALID, "clim_create: GREB_C_RESPONSE needs GREB_C_MEAN or GREB_C_SEASONS (it is their difference to "
                                          "the control)");
   if ((what & GREB_C_RESPONSE) && !control)
     return fail(nullptr, GREB_E_INVALID, "clim_create: GREB_C_RESPONSE selected but `control` is NULL");
-  if (control)
-    for (int m = 0; m < n_members; ++m)
-      if (control[m] < -1 || control[m] >= n_members)
-        return fail(nullptr, GREB_E_INVALID, "clim_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
-                                                 " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
+  if (int rc = check_control("clim_create", control, n_members)) return rc;
   greb_clim* c = new (std::nothrow) greb_clim();
   if (!c) return fail(nullptr, GREB_E_INVALID, "out of host memory");
   c->nx = nx; c->ny = ny; c->nm = n_members; c->what = what; c->nv = n_vars;
@@ -511,17 +608,12 @@ int greb_clim_add_year_dev(greb_clim* c, int device, const float* monthly_year_d
   if (!c) return fail(nullptr, GREB_E_INVALID, "clim_add_year_dev: no plan (greb_clim is NULL)");
   if (!monthly_year_dev) return fail(nullptr, GREB_E_INVALID, "clim_add_year_dev: monthly_year_dev is NULL");
   if (int rc = check_aligned("clim_add_year_dev", monthly_year_dev, "monthly_year_dev")) return rc;
-  if (k != c->added)
-    return fail(nullptr, GREB_E_INVALID, "clim_add_year_dev: k = " + std::to_string(k) + ", but " + std::to_string(c->added) +
-                                             " years were added since the last finish (years go in ascending order, k = 0 first)");
-  if (k > 0 && device != c->added_device)
-    return fail(nullptr, GREB_E_INVALID, "clim_add_year_dev: device " + std::to_string(device) + ", but this period's sums are on device " +
-                                             std::to_string(c->added_device));
+  if (int rc = c->period.check_add("clim_add_year_dev", k, device)) return rc;
   if (int rc = use_device("clim_add_year_dev: ", device)) return rc;
   greb_clim::Dev* dv = nullptr;
   if (int rc = clim_on_device(c, device, &dv)) return rc;
   HIP_TRY(nullptr, launch_clim_add_year(monthly_year_dev, dv->S.get(), dv->T.get(), c->elems(), k, (hipStream_t)stream));
-  c->added = k + 1; c->added_device = device;
+  c->period.advance(k, device);
   return 0;
 }
 
@@ -531,17 +623,12 @@ int greb_clim_finish_dev(greb_clim* c, int device, int n_years, float* mean_dev,
   const Products pr = clim_products(c);
   float* out[5] = {mean_dev, seasons_dev, trend_dev, mean_resp_dev, seasons_resp_dev};
   if (int rc = pr.check(nullptr, "clim_finish_dev", out, "_dev", true)) return rc;
-  if (n_years != c->added || n_years < 1)
-    return fail(nullptr, GREB_E_INVALID, "clim_finish_dev: n_years = " + std::to_string(n_years) + ", but " + std::to_string(c->added) +
-                                             " years were added since the last finish");
-  if (device != c->added_device)
-    return fail(nullptr, GREB_E_INVALID, "clim_finish_dev: device " + std::to_string(device) + ", but this period's sums are on device " +
-                                             std::to_string(c->added_device));
+  if (int rc = c->period.check_finish("clim_finish_dev", n_years, device)) return rc;
   if (int rc = use_device("clim_finish_dev: ", device)) return rc;
   greb_clim::Dev* dv = nullptr;
   if (int rc = clim_on_device(c, device, &dv)) return rc;
   HIP_TRY(nullptr, launch_clim_finish(clim_finish_args(c, dv, n_years, out), c->nm, (hipStream_t)stream));
-  c->added = 0; c->added_device = -1;
+  c->period.reset();
   return 0;
 }
 
@@ -573,8 +660,7 @@ int run_clim(const std::string& name, Records src, greb_engine* e, int years, co
   Products pr = clim_products(c);
   float* host[5] = {mean, seasons, trend, mean_resp, seasons_resp};
   if (int rc = pr.check(e, name, host, "", false)) return rc;
-  if (c->added != 0)
-    return fail(e, GREB_E_INVALID, name + ": the plan holds " + std::to_string(c->added) + " years of an unfinished period");
+  if (int rc = c->period.check_idle(e, name)) return rc;
   if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, name + ": bad argument (engine or co2_ppm)");
   if (int rc = check_engine(e, name, c->nx, c->ny, c->nm)) return rc;
   pr.layout((size_t)e->nm);
@@ -657,17 +743,12 @@ int ens_on_device(greb_ens* s, int device, EnsLists* out) {
   return 0;
 }
 
-// the five products: MEAN, VAR, the two of RANGE, QUANTILES
-const char* const kEnsOutNames[5] = {"mean", "var", "min", "max", "quant"};
-const char* const kEnsFlagNames[5] = {"GREB_S_MEAN", "GREB_S_VAR", "GREB_S_RANGE", "GREB_S_RANGE", "GREB_S_QUANTILES"};
-// floats of one group's record of each product, for rows of n elements
+// floats of one group's record of each product, for rows of n elements: MEAN, VAR, the two of RANGE, QUANTILES
 Products ens_products(const greb_ens* s, size_t n) {
-  Products pr{kEnsOutNames, kEnsFlagNames};
-  pr.size[0] = (s->what & GREB_S_MEAN) ? n : 0;
-  pr.size[1] = (s->what & GREB_S_VAR) ? n : 0;
-  pr.size[2] = pr.size[3] = (s->what & GREB_S_RANGE) ? n : 0;
-  pr.size[4] = (s->what & GREB_S_QUANTILES) ? (size_t)s->probs.n * n : 0;
-  return pr;
+  const size_t range = (s->what & GREB_S_RANGE) ? n : 0;
+  return {{"mean", "GREB_S_MEAN", (s->what & GREB_S_MEAN) ? n : 0}, {"var", "GREB_S_VAR", (s->what & GREB_S_VAR) ? n : 0},
+          {"min", "GREB_S_RANGE", range}, {"max", "GREB_S_RANGE", range},
+          {"quant", "GREB_S_QUANTILES", (s->what & GREB_S_QUANTILES) ? (size_t)s->probs.n * n : 0}};
 }
 
 // the moments launch and one quantile launch per group, of x[nm][n] into out[5] (null where not selected)
@@ -690,31 +771,18 @@ extern "C" {
 
 int greb_ens_create(int nx, int ny, int n_members, const int32_t* group, int n_groups, const int32_t* control,
                     const float* probs, int n_probs, unsigned what, greb_ens** out) {
-  if (!out) return fail(nullptr, GREB_E_INVALID, "ens_create: `out` is NULL");
-  *out = nullptr;
-  if (int rc = check_grid("ens_create", nx, ny)) return rc;
-  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "ens_create: n_members = " + std::to_string(n_members));
-  if (n_groups < 1 || n_groups > kEnsMaxGroups)
-    return fail(nullptr, GREB_E_INVALID, "ens_create: n_groups = " + std::to_string(n_groups) + " (1 ... " +
-                                             std::to_string(kEnsMaxGroups) + ")");
+  if (int rc = begin_create("ens_create", out, nx, ny, nullptr, &n_members)) return rc;
+  if (int rc = check_count(nullptr, "ens_create", "n_groups", n_groups, kEnsMaxGroups)) return rc;
   if (!group) return fail(nullptr, GREB_E_INVALID, "ens_create: `group` is NULL");
   if (int rc = check_what(nullptr, "ens_create", what, GREB_S_MEAN | GREB_S_VAR | GREB_S_RANGE | GREB_S_QUANTILES)) return rc;
-  std::vector<int> count((size_t)n_groups, 0);
-  for (int m = 0; m < n_members; ++m) {
-    if (group[m] < -1 || group[m] >= n_groups)
-      return fail(nullptr, GREB_E_INVALID, "ens_create: member " + std::to_string(m) + ": group = " + std::to_string(group[m]) +
-                                               " (-1 = none, or 0 ... " + std::to_string(n_groups - 1) + ")");
-    if (control && (control[m] < -1 || control[m] >= n_members))
-      return fail(nullptr, GREB_E_INVALID, "ens_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
-                                               " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
-    if (group[m] < 0) continue;
-    if (control && control[m] < 0)
-      return fail(nullptr, GREB_E_INVALID, "ens_create: member " + std::to_string(m) + " is in group " + std::to_string(group[m]) +
-                                               " but has no control (control = -1) while a control map is given");
-    ++count[(size_t)group[m]];
-  }
-  for (int g = 0; g < n_groups; ++g)
-    if (count[(size_t)g] == 0) return fail(nullptr, GREB_E_INVALID, "ens_create: group " + std::to_string(g) + " is empty");
+  std::vector<int> offs, member;
+  auto grouped_has_control = [=](int m) -> int {
+    if (int rc = check_control_of("ens_create", control, m, n_members)) return rc;
+    if (group[m] < 0 || !control || control[m] >= 0) return 0;
+    return fail(nullptr, GREB_E_INVALID, "ens_create: member " + std::to_string(m) + " is in group " + std::to_string(group[m]) +
+                                             " but has no control (control = -1) while a control map is given");
+  };
+  if (int rc = group_lists("ens_create", "member", "group", group, n_groups, n_members, &offs, &member, grouped_has_control)) return rc;
   EnsProbs pr{};
   if (what & GREB_S_QUANTILES) {
     if (n_probs < 1 || n_probs > kEnsMaxProbs || !probs)
@@ -730,25 +798,16 @@ int greb_ens_create(int nx, int ny, int n_members, const int32_t* group, int n_g
       pr.p[i] = probs[i];
     }
     for (int g = 0; g < n_groups; ++g)
-      if (count[(size_t)g] > kEnsMaxSorted)
+      if (const int count = offs[(size_t)g + 1] - offs[(size_t)g]; count > kEnsMaxSorted)
         return fail(nullptr, GREB_E_UNSUPPORTED, "ens_create: GREB_S_QUANTILES with group " + std::to_string(g) + " of " +
-                                                     std::to_string(count[(size_t)g]) + " members (at most " +
+                                                     std::to_string(count) + " members (at most " +
                                                      std::to_string(kEnsMaxSorted) + " are sorted in one compute unit's LDS)");
   }
   greb_ens* s = new (std::nothrow) greb_ens();
   if (!s) return fail(nullptr, GREB_E_INVALID, "out of host memory");
   s->nx = nx; s->ny = ny; s->nm = n_members; s->ng = n_groups; s->what = what; s->probs = pr; s->has_control = control != nullptr;
-  s->offs.assign((size_t)n_groups + 1, 0);
-  for (int g = 0; g < n_groups; ++g) s->offs[(size_t)g + 1] = s->offs[(size_t)g] + count[(size_t)g];
-  s->member.resize((size_t)s->offs[(size_t)n_groups]);
-  if (control) s->control.resize(s->member.size());
-  std::vector<int> at(s->offs.begin(), s->offs.end() - 1);
-  for (int m = 0; m < n_members; ++m) { // ascending member index inside every group
-    if (group[m] < 0) continue;
-    const size_t k = (size_t)at[(size_t)group[m]]++;
-    s->member[k] = m;
-    if (control) s->control[k] = control[m];
-  }
+  s->offs = offs; s->member = member;
+  for (size_t k = 0; control && k < member.size(); ++k) s->control.push_back(control[member[k]]);
   *out = s;
   return 0;
 }
@@ -796,15 +855,11 @@ int run_ens(const std::string& who, Records src, greb_engine* e, int years, cons
     if (int rc = src.prepare(e)) return rc;
     return ens_on_device(s, e->device, &l);
   });
-  sink.year = [&](const YearCalls& run, int y) -> int {
-    const float* mon = nullptr;
-    if (int rc = src.integrate(e, run, y, &mon)) return rc;
-    if (int rc = run.writing(y)) return rc; // (here, not before the year: only the reduction writes the slot)
+  sink.year = year_hook(e, &src, [&](const float* mon, int y) -> int {
     float* out[5];
     pr.pointers(k.slot(y), out);
-    if (int rc = ens_launch(e, s, l, mon, n, out, e->stream)) return rc;
-    return run.complete(y);
-  };
+    return ens_launch(e, s, l, mon, n, out, e->stream);
+  });
   return run_years(e, years, co2_ppm, yearly, sink);
 }
 } // namespace
@@ -861,24 +916,15 @@ int lin_on_device(greb_lin* l, int device, LinTables* out) {
   return 0;
 }
 
-// The two products: `coef` has K rows of a record, `rss` one.  An output slot holds coef [K][n], then rss [n].
-struct LinOut {
-  size_t n, coef, rss; // floats of a record; of each product in a slot (0: not selected)
-  LinOut(const greb_lin* l, size_t rec) : n(rec), coef((l->what & GREB_L_COEF) ? (size_t)l->nk * rec : 0), rss((l->what & GREB_L_RSS) ? rec : 0) {}
-  size_t slot() const { return coef + rss; }
-  // every selected product has somewhere to go (suffix "_dev": on the device); what is not selected is ignored
-  int check(greb_engine* e, const std::string& who, float** c, float** r, const char* suffix) const {
-    if (!coef) *c = nullptr;
-    if (!rss) *r = nullptr;
-    if (coef && !*c) return fail(e, GREB_E_INVALID, who + ": GREB_L_COEF selected but `coef" + suffix + "` is NULL");
-    if (rss && !*r) return fail(e, GREB_E_INVALID, who + ": GREB_L_RSS selected but `rss" + suffix + "` is NULL");
-    return 0;
-  }
-};
+// The two products for records of `rec` floats: `coef` has K rows of a record, `rss` one.  An output slot holds coef
+// [K][rec], then rss [rec].
+Products lin_products(const greb_lin* l, size_t rec) {
+  return {{"coef", "GREB_L_COEF", (l->what & GREB_L_COEF) ? rec : 0, (size_t)l->nk}, {"rss", "GREB_L_RSS", (l->what & GREB_L_RSS) ? rec : 0, 1}};
+}
 
-int lin_launch(greb_engine* e, const LinTables& t, const float* x, size_t n, float* coef, float* rss, hipStream_t stream) {
-  if (coef) HIP_TRY(e, launch_lin_coef(x, n, t, coef, stream));
-  if (rss) HIP_TRY(e, launch_lin_rss(x, n, t, rss, stream));
+int lin_launch(greb_engine* e, const LinTables& t, const float* x, size_t n, float* const out[2], hipStream_t stream) {
+  if (out[0]) HIP_TRY(e, launch_lin_coef(x, n, t, out[0], stream));
+  if (out[1]) HIP_TRY(e, launch_lin_rss(x, n, t, out[1], stream));
   return 0;
 }
 } // namespace
@@ -887,30 +933,15 @@ extern "C" {
 
 int greb_lin_create(int nx, int ny, int n_members, const double* weight, int n_terms, const int32_t* use, const int32_t* control,
                     const double* design, unsigned what, greb_lin** out) {
-  if (!out) return fail(nullptr, GREB_E_INVALID, "lin_create: `out` is NULL");
-  *out = nullptr;
-  if (int rc = check_grid("lin_create", nx, ny)) return rc;
-  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "lin_create: n_members = " + std::to_string(n_members));
-  if (n_terms < 1 || n_terms > kLinMaxTerms)
-    return fail(nullptr, GREB_E_INVALID, "lin_create: n_terms = " + std::to_string(n_terms) + " (1 ... " + std::to_string(kLinMaxTerms) + ")");
+  if (int rc = begin_create("lin_create", out, nx, ny, nullptr, &n_members)) return rc;
+  if (int rc = check_count(nullptr, "lin_create", "n_terms", n_terms, kLinMaxTerms)) return rc;
   if (int rc = check_what(nullptr, "lin_create", what, GREB_L_COEF | GREB_L_RSS)) return rc;
   if (!weight) return fail(nullptr, GREB_E_INVALID, "lin_create: `weight` is NULL");
   if ((what & GREB_L_RSS) && !design)
     return fail(nullptr, GREB_E_INVALID, "lin_create: GREB_L_RSS selected but `design` is NULL (the residual is that of the fit design * coef)");
-  int n_used = 0;
-  for (int m = 0; m < n_members; ++m) {
-    if (control && (control[m] < -1 || control[m] >= n_members))
-      return fail(nullptr, GREB_E_INVALID, "lin_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
-                                               " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
-    if (use && !use[m]) continue;
-    if (control && control[m] < 0)
-      return fail(nullptr, GREB_E_INVALID, "lin_create: member " + std::to_string(m) +
-                                               " is used but has no control (control = -1) while a control map is given");
-    ++n_used;
-  }
-  if (n_used == 0) return fail(nullptr, GREB_E_INVALID, "lin_create: no used member (`use` is zero everywhere)");
-  for (int m = 0; m < n_members; ++m) {
-    if (use && !use[m]) continue;
+  std::vector<int> member, control_of_used;
+  if (int rc = used_members("lin_create", use, control, n_members, &member, &control_of_used)) return rc;
+  for (const int m : member) {
     for (int k = 0; k < n_terms; ++k) {
       const bool w_ok = std::isfinite(weight[(size_t)k * n_members + m]);
       if (w_ok && (!design || std::isfinite(design[(size_t)m * n_terms + k]))) continue;
@@ -924,14 +955,12 @@ int greb_lin_create(int nx, int ny, int n_members, const double* weight, int n_t
   if (!l) return fail(nullptr, GREB_E_INVALID, "out of host memory");
   l->nx = nx; l->ny = ny; l->nm = n_members; l->nk = n_terms; l->what = what; l->has_control = control != nullptr;
   l->stride = kLinChunk * ((n_terms + kLinChunk - 1) / kLinChunk);
-  l->member.reserve((size_t)n_used);
-  l->weight.assign((size_t)n_used * l->stride, 0.0);
-  if (design) l->design.assign((size_t)n_used * l->stride, 0.0);
-  for (int m = 0; m < n_members; ++m) { // ascending member index
-    if (use && !use[m]) continue;
-    const size_t at = l->member.size() * (size_t)l->stride;
-    l->member.push_back(m);
-    if (control) l->control.push_back(control[m]);
+  l->member = member; l->control = control_of_used;
+  l->weight.assign(member.size() * l->stride, 0.0);
+  if (design) l->design.assign(member.size() * l->stride, 0.0);
+  for (size_t u = 0; u < member.size(); ++u) {
+    const size_t at = u * (size_t)l->stride;
+    const int m = member[u];
     for (int k = 0; k < n_terms; ++k) {
       l->weight[at + k] = weight[(size_t)k * n_members + m];
       if (design) l->design[at + k] = design[(size_t)m * n_terms + k];
@@ -951,11 +980,12 @@ int greb_lin_reduce_dev(greb_lin* l, int device, const float* x_dev, size_t n, f
   if (!x_dev) return fail(nullptr, GREB_E_INVALID, "lin_reduce_dev: x_dev is NULL");
   if (int rc = check_aligned("lin_reduce_dev", x_dev, "x_dev")) return rc;
   if (n < 1) return fail(nullptr, GREB_E_INVALID, "lin_reduce_dev: n = 0");
-  if (int rc = LinOut(l, n).check(nullptr, "lin_reduce_dev", &coef_dev, &rss_dev, "_dev")) return rc;
+  float* out[2] = {coef_dev, rss_dev};
+  if (int rc = lin_products(l, n).check(nullptr, "lin_reduce_dev", out, "_dev", false)) return rc;
   if (int rc = use_device("lin_reduce_dev: ", device)) return rc;
   LinTables t{};
   if (int rc = lin_on_device(l, device, &t)) return rc;
-  return lin_launch(nullptr, t, x_dev, n, coef_dev, rss_dev, (hipStream_t)stream);
+  return lin_launch(nullptr, t, x_dev, n, out, (hipStream_t)stream);
 }
 
 } // extern "C"
@@ -967,32 +997,26 @@ int run_lin(const std::string& who, Records src, greb_engine* e, int years, cons
   if (!l) return fail(e, GREB_E_INVALID, who + ": no plan (greb_lin is NULL)");
   if (years < 1) return fail(e, GREB_E_INVALID, who + ": years = " + std::to_string(years));
   const size_t n = (size_t)12 * src.nv * l->nx * l->ny; // one member's model year
-  const LinOut o(l, n);
-  if (int rc = o.check(e, who, &coef, &rss, "")) return rc;
+  Products pr = lin_products(l, n);
+  float* host[2] = {coef, rss};
+  if (int rc = pr.check(e, who, host, "", false)) return rc;
   if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, who + ": bad argument (engine or co2_ppm)");
   if (int rc = check_engine(e, who, l->nx, l->ny, l->nm)) return rc;
+  pr.layout();
   LinTables t{};
   // A unit is a year's coefficients and residual map, made in output slot y & 1 of e->lin_out.  Nothing on the device
   // grows with `years` (besides the yearly scalars).
-  auto slot = [&](int u) { return e->lin_out + (size_t)(u & 1) * o.slot(); };
+  const ProductSink k{e, pr, &e->lin_out, &e->lin_out_cap, host, years};
   RunSink sink;
-  sink.prepare = [&]() -> int {
-    if (int rc = ensure(e, &e->lin_out, &e->lin_out_cap, 2 * o.slot())) return rc;
+  k.install(sink, [&]() -> int {
     if (int rc = src.prepare(e)) return rc;
     return lin_on_device(l, e->device, &t);
-  };
-  sink.year = [&](const YearCalls& run, int y) -> int {
-    const float* mon = nullptr;
-    if (int rc = src.integrate(e, run, y, &mon)) return rc;
-    if (int rc = run.writing(y)) return rc; // (here, not before the year: only the reduction writes the slot)
-    if (int rc = lin_launch(e, t, mon, n, o.coef ? slot(y) : nullptr, o.rss ? slot(y) + o.coef : nullptr, e->stream)) return rc;
-    return run.complete(y);
-  };
-  sink.deliver = [&](int y, int sl) -> int {
-    if (o.coef) HIP_TRY(e, unit_to_host(e, coef, years, y, slot(sl), n, (size_t)l->nk));
-    if (o.rss) HIP_TRY(e, unit_to_host(e, rss, years, y, slot(sl) + o.coef, n, 1));
-    return 0;
-  };
+  });
+  sink.year = year_hook(e, &src, [&](const float* mon, int y) -> int {
+    float* out[2];
+    pr.pointers(k.slot(y), out);
+    return lin_launch(e, t, mon, n, out, e->stream);
+  });
   return run_years(e, years, co2_ppm, yearly, sink);
 }
 } // namespace
@@ -1067,38 +1091,15 @@ extern "C" {
 
 int greb_gram_create(int nx, int ny, int n_members, int n_records, const int32_t* block, int n_blocks, const int32_t* use,
                      const int32_t* control, const float* scale, greb_gram** out) {
-  if (!out) return fail(nullptr, GREB_E_INVALID, "gram_create: `out` is NULL");
-  *out = nullptr;
-  if (int rc = check_grid("gram_create", nx, ny)) return rc;
-  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "gram_create: n_members = " + std::to_string(n_members));
+  if (int rc = begin_create("gram_create", out, nx, ny, nullptr, &n_members)) return rc;
   if (n_records < 1) return fail(nullptr, GREB_E_INVALID, "gram_create: n_records = " + std::to_string(n_records));
-  if (n_blocks < 1 || n_blocks > kGramMaxBlocks)
-    return fail(nullptr, GREB_E_INVALID, "gram_create: n_blocks = " + std::to_string(n_blocks) + " (1 ... " +
-                                             std::to_string(kGramMaxBlocks) + ")");
+  if (int rc = check_count(nullptr, "gram_create", "n_blocks", n_blocks, kGramMaxBlocks)) return rc;
   if (!block) return fail(nullptr, GREB_E_INVALID, "gram_create: `block` is NULL");
-  std::vector<int> count((size_t)n_blocks, 0);
-  for (int r = 0; r < n_records; ++r) {
-    if (block[r] < -1 || block[r] >= n_blocks)
-      return fail(nullptr, GREB_E_INVALID, "gram_create: record " + std::to_string(r) + ": block = " + std::to_string(block[r]) +
-                                               " (-1 = none, or 0 ... " + std::to_string(n_blocks - 1) + ")");
-    if (block[r] >= 0) ++count[(size_t)block[r]];
-  }
-  for (int b = 0; b < n_blocks; ++b)
-    if (count[(size_t)b] == 0) return fail(nullptr, GREB_E_INVALID, "gram_create: block " + std::to_string(b) + " is empty");
-  int n_used = 0;
-  for (int m = 0; m < n_members; ++m) {
-    if (control && (control[m] < -1 || control[m] >= n_members))
-      return fail(nullptr, GREB_E_INVALID, "gram_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
-                                               " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
-    if (use && !use[m]) continue;
-    if (control && control[m] < 0)
-      return fail(nullptr, GREB_E_INVALID, "gram_create: member " + std::to_string(m) +
-                                               " is used but has no control (control = -1) while a control map is given");
-    ++n_used;
-  }
-  if (n_used == 0) return fail(nullptr, GREB_E_INVALID, "gram_create: no used member (`use` is zero everywhere)");
-  if (n_used > kGramMaxUsed)
-    return fail(nullptr, GREB_E_UNSUPPORTED, "gram_create: " + std::to_string(n_used) + " used members (at most " +
+  std::vector<int> offs, record, member, control_of_used;
+  if (int rc = group_lists("gram_create", "record", "block", block, n_blocks, n_records, &offs, &record)) return rc;
+  if (int rc = used_members("gram_create", use, control, n_members, &member, &control_of_used)) return rc;
+  if (member.size() > (size_t)kGramMaxUsed)
+    return fail(nullptr, GREB_E_UNSUPPORTED, "gram_create: " + std::to_string(member.size()) + " used members (at most " +
                                                  std::to_string(kGramMaxUsed) + ")");
   const size_t np = (size_t)nx * ny;
   for (size_t i = 0; scale && i < np; ++i)
@@ -1111,17 +1112,7 @@ int greb_gram_create(int nx, int ny, int n_members, int n_records, const int32_t
   greb_gram* g = new (std::nothrow) greb_gram();
   if (!g) return fail(nullptr, GREB_E_INVALID, "out of host memory");
   g->nx = nx; g->ny = ny; g->nm = n_members; g->nrec = n_records; g->nb = n_blocks; g->has_control = control != nullptr;
-  for (int m = 0; m < n_members; ++m) { // ascending member index
-    if (use && !use[m]) continue;
-    g->member.push_back(m);
-    if (control) g->control.push_back(control[m]);
-  }
-  g->offs.assign((size_t)n_blocks + 1, 0);
-  for (int b = 0; b < n_blocks; ++b) {
-    for (int r = 0; r < n_records; ++r) // ascending record inside the block
-      if (block[r] == b) g->record.push_back(r);
-    g->offs[(size_t)b + 1] = (int)g->record.size();
-  }
+  g->member = member; g->control = control_of_used; g->record = record; g->offs = offs;
   if (scale) g->scale.assign(scale, scale + np);
   *out = g;
   return 0;
@@ -1167,22 +1158,14 @@ int run_gram(const std::string& who, Records src, greb_engine* e, int years, con
   auto slot = [&](int u) { return e->gram_out + (size_t)(u & 1) * out; };
   RunSink sink;
   sink.prepare = [&]() -> int {
-    if (e->gram_out_cap < 2 * out) {
-      if (e->gram_out) HIP_TRY(e, hipFree(e->gram_out));
-      e->gram_out = nullptr; e->gram_out_cap = 0;
-      HIP_TRY(e, dev_alloc(&e->gram_out, 2 * out));
-      e->gram_out_cap = 2 * out;
-    }
+    if (int rc = ensure(e, &e->gram_out, &e->gram_out_cap, 2 * out)) return rc;
     if (int rc = src.prepare(e)) return rc;
     return gram_on_device(g, e->device, &t);
   };
-  sink.year = [&](const YearCalls& run, int y) -> int {
-    const float* mon = nullptr;
-    if (int rc = src.integrate(e, run, y, &mon)) return rc;
-    if (int rc = run.writing(y)) return rc; // (here, not before the year: only the reduction writes the slot)
+  sink.year = year_hook(e, &src, [&](const float* mon, int y) -> int {
     HIP_TRY(e, launch_gram(mon, len, t, slot(y), e->stream));
-    return run.complete(y);
-  };
+    return 0;
+  });
   sink.deliver = [&](int y, int sl) -> int {
     HIP_TRY(e, hipMemcpyAsync(G + (size_t)y * out, slot(sl), out * sizeof(double), hipMemcpyDeviceToHost, e->copy_stream));
     return 0;
@@ -1210,14 +1193,13 @@ int greb_engine_run_budget_gram(greb_engine* e, int years, const float* co2_ppm,
 // Grid, member count, variable count, the events in the caller's order and as the update kernel walks them (CrossTable:
 // sorted by variable, then selector), each member's control, the group lists (group g is member[offs[g] ... offs[g + 1]) in
 // ascending member index) and the products.  Per device: the state words the products need, the hit bytes and the two
-// output slots of FRACTION, and the lists' copy (one allocation: control, offs, member).  `added` counts the years since the
-// last finish: one period is followed at a time, on one device.
+// output slots of FRACTION, and the lists' copy (one allocation: control, offs, member).
 struct greb_cross {
   int nx = 0, ny = 0, nm = 0, nv = 0, ne = 0, ng = 0;
   unsigned what = 0;
   CrossTable table{};
   std::vector<int> control, offs, member;
-  int added = 0, added_device = -1;
+  Period period{"state is"};
   struct Dev { DevBuf<int> first, last, last_miss, count, peak_year, lists; DevBuf<float> peak, frac_out; DevBuf<unsigned char> hit; };
   PerDevice<Dev> devs;
   size_t np() const { return (size_t)nx * ny; }
@@ -1264,29 +1246,20 @@ int cross_launch_year(greb_engine* e, const greb_cross* c, const greb_cross::Dev
   return 0;
 }
 
-// the six maps: their parameters' names, what selects each, and whether the caller gave every selected one
-const char* const kCrossOutNames[6] = {"first", "last", "stay", "count", "peak", "peak_year"};
-const char* const kCrossFlagNames[6] = {"GREB_T_FIRST", "GREB_T_LAST", "GREB_T_STAY", "GREB_T_COUNT", "GREB_T_PEAK", "GREB_T_PEAK"};
-const unsigned kCrossFlags[6] = {GREB_T_FIRST, GREB_T_LAST, GREB_T_STAY, GREB_T_COUNT, GREB_T_PEAK, GREB_T_PEAK};
-int check_cross_maps(greb_engine* e, const std::string& who, const greb_cross* c, void* p[6], const char* suffix, bool aligned) {
-  for (int i = 0; i < 6; ++i) {
-    if (!(c->what & kCrossFlags[i])) { p[i] = nullptr; continue; }
-    if (!p[i]) return fail(e, GREB_E_INVALID, who + ": " + kCrossFlagNames[i] + " selected but `" + kCrossOutNames[i] + suffix + "` is NULL");
-    if (aligned) if (int rc = check_aligned(who, p[i], std::string(kCrossOutNames[i]) + suffix)) return rc;
-  }
-  return 0;
+// the six maps, of one word per (member, event, point), and the year's FRACTION
+Products cross_maps(const greb_cross* c) {
+  auto size = [c](unsigned flag) { return (c->what & flag) ? c->elems() : 0; };
+  return {{"first", "GREB_T_FIRST", size(GREB_T_FIRST)}, {"last", "GREB_T_LAST", size(GREB_T_LAST)}, {"stay", "GREB_T_STAY", size(GREB_T_STAY)},
+          {"count", "GREB_T_COUNT", size(GREB_T_COUNT)}, {"peak", "GREB_T_PEAK", size(GREB_T_PEAK)}, {"peak_year", "GREB_T_PEAK", size(GREB_T_PEAK)}};
 }
+Products cross_fraction(const greb_cross* c) { return {{"fraction", "GREB_T_FRACTION", (c->what & GREB_T_FRACTION) ? c->fraction() : 0}}; }
 } // namespace
 
 extern "C" {
 
 int greb_cross_create(int nx, int ny, int n_members, int n_vars, const greb_cross_event* events, int n_events, const int32_t* control,
                       const int32_t* group, int n_groups, unsigned what, greb_cross** out) {
-  if (!out) return fail(nullptr, GREB_E_INVALID, "cross_create: `out` is NULL");
-  *out = nullptr;
-  if (int rc = check_grid("cross_create", nx, ny)) return rc;
-  if (int rc = check_n_vars("cross_create", n_vars)) return rc;
-  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, "cross_create: n_members = " + std::to_string(n_members));
+  if (int rc = begin_create("cross_create", out, nx, ny, &n_vars, &n_members)) return rc;
   if (int rc = check_what(nullptr, "cross_create", what, kCrossAll)) return rc;
   if (n_events < 1 || n_events > GREB_CROSS_MAX_EVENTS || !events)
     return fail(nullptr, GREB_E_INVALID, "cross_create: n_events = " + std::to_string(n_events) + (events ? "" : " and `events` NULL") +
@@ -1296,8 +1269,7 @@ int greb_cross_create(int nx, int ny, int n_members, int n_vars, const greb_cros
     const std::string who = "cross_create: event " + std::to_string(i) + ": ";
     if (ev.var < 0 || ev.var >= n_vars)
       return fail(nullptr, GREB_E_INVALID, who + "var = " + std::to_string(ev.var) + " (0 ... " + std::to_string(n_vars - 1) + ")");
-    if (ev.sel < 0 || ev.sel >= kCrossSelectors)
-      return fail(nullptr, GREB_E_INVALID, who + "sel = " + std::to_string(ev.sel) + " (0 ... 11: a month; 12 ... 16: DJF, MAM, JJA, SON, ANN)");
+    if (ev.sel < 0 || ev.sel >= season::kSelectors) return fail(nullptr, GREB_E_INVALID, who + "sel = " + std::to_string(ev.sel) + kSelRange);
     if (ev.rel != 0 && ev.rel != 1) return fail(nullptr, GREB_E_INVALID, who + "rel = " + std::to_string(ev.rel) + " (0 or 1)");
     if (ev.rel && !control) return fail(nullptr, GREB_E_INVALID, who + "rel = 1 (member minus its control) but `control` is NULL");
     if (ev.dir != 1 && ev.dir != -1) return fail(nullptr, GREB_E_INVALID, who + "dir = " + std::to_string(ev.dir) + " (+1: q >= thr, -1: q <= thr)");
@@ -1307,60 +1279,20 @@ int greb_cross_create(int nx, int ny, int n_members, int n_vars, const greb_cros
       return fail(nullptr, GREB_E_INVALID, who + buf);
     }
   }
-  if (control)
-    for (int m = 0; m < n_members; ++m)
-      if (control[m] < -1 || control[m] >= n_members)
-        return fail(nullptr, GREB_E_INVALID, "cross_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
-                                                 " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
+  if (int rc = check_control("cross_create", control, n_members)) return rc;
   if ((what & GREB_T_FRACTION) && !group)
     return fail(nullptr, GREB_E_INVALID, "cross_create: GREB_T_FRACTION selected but `group` is NULL (it is the share of a group's members)");
-  std::vector<int> count;
+  std::vector<int> offs, member;
   if (group) {
-    if (n_groups < 1 || n_groups > GREB_ENS_MAX_GROUPS)
-      return fail(nullptr, GREB_E_INVALID, "cross_create: n_groups = " + std::to_string(n_groups) + " (1 ... " +
-                                               std::to_string(GREB_ENS_MAX_GROUPS) + ")");
-    count.assign((size_t)n_groups, 0);
-    for (int m = 0; m < n_members; ++m) {
-      if (group[m] < -1 || group[m] >= n_groups)
-        return fail(nullptr, GREB_E_INVALID, "cross_create: member " + std::to_string(m) + ": group = " + std::to_string(group[m]) +
-                                                 " (-1 = none, or 0 ... " + std::to_string(n_groups - 1) + ")");
-      if (group[m] >= 0) ++count[(size_t)group[m]];
-    }
-    for (int g = 0; g < n_groups; ++g)
-      if (count[(size_t)g] == 0) return fail(nullptr, GREB_E_INVALID, "cross_create: group " + std::to_string(g) + " is empty");
+    if (int rc = check_count(nullptr, "cross_create", "n_groups", n_groups, GREB_ENS_MAX_GROUPS)) return rc;
+    if (int rc = group_lists("cross_create", "member", "group", group, n_groups, n_members, &offs, &member)) return rc;
   }
   greb_cross* c = new (std::nothrow) greb_cross();
   if (!c) return fail(nullptr, GREB_E_INVALID, "out of host memory");
   c->nx = nx; c->ny = ny; c->nm = n_members; c->nv = n_vars; c->ne = n_events; c->what = what;
   if (control) c->control.assign(control, control + n_members);
-  if (group) {
-    c->ng = n_groups;
-    c->offs.assign((size_t)n_groups + 1, 0);
-    for (int g = 0; g < n_groups; ++g) c->offs[(size_t)g + 1] = c->offs[(size_t)g] + count[(size_t)g];
-    c->member.resize((size_t)c->offs[(size_t)n_groups]);
-    std::vector<int> at(c->offs.begin(), c->offs.end() - 1);
-    for (int m = 0; m < n_members; ++m) // ascending member index inside every group
-      if (group[m] >= 0) c->member[(size_t)at[(size_t)group[m]]++] = m;
-  }
-  // the events by variable, then selector (the caller's order among equals); what each variable's events read
-  std::vector<int> order((size_t)n_events);
-  for (int i = 0; i < n_events; ++i) order[(size_t)i] = i;
-  std::stable_sort(order.begin(), order.end(), [events](int a, int b) {
-    return events[a].var != events[b].var ? events[a].var < events[b].var : events[a].sel < events[b].sel;
-  });
-  CrossTable& t = c->table;
-  int v = -1;
-  for (int i = 0; i < n_events; ++i) {
-    const greb_cross_event& ev = events[order[(size_t)i]];
-    t.ev[i] = CrossTable::Ev{ev.sel, ev.rel, ev.dir, ev.thr, order[(size_t)i]};
-    if (v < 0 || t.var[v] != ev.var) { ++v; t.var[v] = ev.var; t.vstart[v] = i; }
-    static constexpr int kSeasonMonths[5] = {0x803, 0x01c, 0x0e0, 0x700, 0xfff}; // DJF MAM JJA SON ANN, bit mo
-    const int months = ev.sel < 12 ? 1 << ev.sel : kSeasonMonths[ev.sel - 12];
-    t.months[v] |= months;
-    if (ev.rel) { t.ctl_months[v] |= months; t.rel_sels[v] |= 1 << ev.sel; }
-  }
-  t.n_vars_used = v + 1;
-  t.vstart[t.n_vars_used] = n_events;
+  if (group) { c->ng = n_groups; c->offs = offs; c->member = member; }
+  build_year_table(c->table, events, n_events, [](CrossEv& to, const greb_cross_event& ev) { to.dir = ev.dir; to.thr = ev.thr; });
   *out = c;
   return 0;
 }
@@ -1374,21 +1306,13 @@ int greb_cross_add_year_dev(greb_cross* c, int device, const float* x_dev, int k
   if (!c) return fail(nullptr, GREB_E_INVALID, "cross_add_year_dev: no plan (greb_cross is NULL)");
   if (!x_dev) return fail(nullptr, GREB_E_INVALID, "cross_add_year_dev: x_dev is NULL");
   if (int rc = check_aligned("cross_add_year_dev", x_dev, "x_dev")) return rc;
-  if (c->what & GREB_T_FRACTION) {
-    if (!fraction_dev) return fail(nullptr, GREB_E_INVALID, "cross_add_year_dev: GREB_T_FRACTION selected but `fraction_dev` is NULL");
-    if (int rc = check_aligned("cross_add_year_dev", fraction_dev, "fraction_dev")) return rc;
-  }
-  if (k != c->added)
-    return fail(nullptr, GREB_E_INVALID, "cross_add_year_dev: k = " + std::to_string(k) + ", but " + std::to_string(c->added) +
-                                             " years were added since the last finish (years go in ascending order, k = 0 first)");
-  if (k > 0 && device != c->added_device)
-    return fail(nullptr, GREB_E_INVALID, "cross_add_year_dev: device " + std::to_string(device) + ", but this period's state is on device " +
-                                             std::to_string(c->added_device));
+  if (int rc = cross_fraction(c).check(nullptr, "cross_add_year_dev", &fraction_dev, "_dev", true)) return rc;
+  if (int rc = c->period.check_add("cross_add_year_dev", k, device)) return rc;
   if (int rc = use_device("cross_add_year_dev: ", device)) return rc;
   greb_cross::Dev* dv = nullptr;
   if (int rc = cross_on_device(c, device, &dv)) return rc;
   if (int rc = cross_launch_year(nullptr, c, dv, x_dev, k, fraction_dev, (hipStream_t)stream)) return rc;
-  c->added = k + 1; c->added_device = device;
+  c->period.advance(k, device);
   return 0;
 }
 
@@ -1396,13 +1320,8 @@ int greb_cross_finish_dev(greb_cross* c, int device, int n_years, int32_t* first
                           int32_t* count_dev, float* peak_dev, int32_t* peak_year_dev, void* stream) {
   if (!c) return fail(nullptr, GREB_E_INVALID, "cross_finish_dev: no plan (greb_cross is NULL)");
   void* out[6] = {first_dev, last_dev, stay_dev, count_dev, peak_dev, peak_year_dev};
-  if (int rc = check_cross_maps(nullptr, "cross_finish_dev", c, out, "_dev", true)) return rc;
-  if (n_years != c->added || n_years < 1)
-    return fail(nullptr, GREB_E_INVALID, "cross_finish_dev: n_years = " + std::to_string(n_years) + ", but " + std::to_string(c->added) +
-                                             " years were added since the last finish");
-  if (device != c->added_device)
-    return fail(nullptr, GREB_E_INVALID, "cross_finish_dev: device " + std::to_string(device) + ", but this period's state is on device " +
-                                             std::to_string(c->added_device));
+  if (int rc = cross_maps(c).check(nullptr, "cross_finish_dev", out, "_dev", true)) return rc;
+  if (int rc = c->period.check_finish("cross_finish_dev", n_years, device)) return rc;
   if (int rc = use_device("cross_finish_dev: ", device)) return rc;
   greb_cross::Dev* dv = nullptr;
   if (int rc = cross_on_device(c, device, &dv)) return rc;
@@ -1411,7 +1330,7 @@ int greb_cross_finish_dev(greb_cross* c, int device, int n_years, int32_t* first
   a.first = (int32_t*)out[0]; a.last = (int32_t*)out[1]; a.stay = (int32_t*)out[2]; a.count = (int32_t*)out[3];
   a.peak = (float*)out[4]; a.peak_year = (int32_t*)out[5];
   if (c->what & ~GREB_T_FRACTION) HIP_TRY(nullptr, launch_cross_finish(a, (hipStream_t)stream));
-  c->added = 0; c->added_device = -1;
+  c->period.reset();
   return 0;
 }
 
@@ -1425,11 +1344,10 @@ int run_cross(const std::string& who, Records src, greb_engine* e, int years, co
   if (int rc = src.check_plan(e, who, c->nv)) return rc;
   if (years < 1) return fail(e, GREB_E_INVALID, who + ": years = " + std::to_string(years));
   void* host[6] = {first, last, stay, count, peak, peak_year};
-  if (int rc = check_cross_maps(e, who, c, host, "", false)) return rc;
+  if (int rc = cross_maps(c).check(e, who, host, "", false)) return rc;
   const bool frac = (c->what & GREB_T_FRACTION) != 0;
-  if (frac && !fraction) return fail(e, GREB_E_INVALID, who + ": GREB_T_FRACTION selected but `fraction` is NULL");
-  if (c->added != 0)
-    return fail(e, GREB_E_INVALID, who + ": the plan holds " + std::to_string(c->added) + " years of an unfinished period");
+  if (int rc = cross_fraction(c).check(e, who, &fraction, "", false)) return rc;
+  if (int rc = c->period.check_idle(e, who)) return rc;
   if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, who + ": bad argument (engine or co2_ppm)");
   if (int rc = check_engine(e, who, c->nx, c->ny, c->nm)) return rc;
   const size_t el = c->elems(), fr = c->fraction();
@@ -1444,13 +1362,9 @@ int run_cross(const std::string& who, Records src, greb_engine* e, int years, co
     if (int rc = src.prepare(e)) return rc;
     return cross_on_device(c, e->device, &dv);
   };
-  sink.year = [&](const YearCalls& run, int y) -> int {
-    const float* mon = nullptr;
-    if (int rc = src.integrate(e, run, y, &mon)) return rc;
-    if (frac) if (int rc = run.writing(y)) return rc; // (here, not before the year: only the fraction pass writes the slot)
-    if (int rc = cross_launch_year(e, c, dv, mon, y, frac ? slot(y) : nullptr, e->stream)) return rc;
-    return frac ? run.complete(y) : 0;
-  };
+  sink.year = year_hook(e, &src, [&](const float* mon, int y) -> int {
+    return cross_launch_year(e, c, dv, mon, y, frac ? slot(y) : nullptr, e->stream);
+  }, frac);
   if (frac)
     sink.deliver = [&](int y, int sl) -> int {
       HIP_TRY(e, hipMemcpyAsync(fraction + (size_t)y * fr, slot(sl), fr * sizeof(float), hipMemcpyDeviceToHost, e->copy_stream));
@@ -1497,8 +1411,7 @@ int greb_engine_run_budget_cross(greb_engine* e, int years, const float* co2_ppm
 // the indices are taken from have the bits a greb_diag plan over the same weights returns), the indices in the caller's
 // order, the terms in the caller's order (index_of) and as the update kernel walks them (RegTable: sorted by variable, then
 // selector), each member's control and the products.  Per device: the term state, the index state, one year's regional
-// means, the control's copy; for greb_engine_run_reg the map the products leave through and the INDEX series.  `added`
-// counts the years since the last finish: one period is followed at a time, on one device.
+// means, the control's copy; for greb_engine_run_reg the map the products leave through and the INDEX series.
 struct greb_reg {
   int nx = 0, ny = 0, nm = 0, nv = 0, nt = 0, ni = 0;
   unsigned what = 0;
@@ -1507,7 +1420,7 @@ struct greb_reg {
   RegIndexTable itable{};
   int index_of[kRegMaxTerms] = {};
   std::vector<int> control;
-  int added = 0, added_device = -1;
+  Period period{"state is"};
   struct Dev {
     DevBuf<float> y0, g0, regions, out, series;
     DevBuf<double> sy, sgy, syy, G, sg, sgg;
@@ -1569,20 +1482,12 @@ RegFinishArgs reg_finish_args(const greb_reg* r, const greb_reg::Dev* dv, int n_
   return a;
 }
 
-// the three maps: their parameters' names, what selects each, and whether the caller gave every selected one
-const char* const kRegOutNames[3] = {"slope", "intercept", "r2"};
-const char* const kRegFlagNames[3] = {"GREB_R_SLOPE", "GREB_R_INTERCEPT", "GREB_R_R2"};
-const unsigned kRegFlags[3] = {GREB_R_SLOPE, GREB_R_INTERCEPT, GREB_R_R2};
-int check_reg_maps(greb_engine* e, const std::string& who, const greb_reg* r, float* p[3], const char* suffix, bool aligned) {
-  for (int i = 0; i < 3; ++i) {
-    if (!(r->what & kRegFlags[i])) { p[i] = nullptr; continue; }
-    if (!p[i]) return fail(e, GREB_E_INVALID, who + ": " + kRegFlagNames[i] + " selected but `" + kRegOutNames[i] + suffix + "` is NULL");
-    if (aligned) if (int rc = check_aligned(who, p[i], std::string(kRegOutNames[i]) + suffix)) return rc;
-  }
-  return 0;
+// the three maps, of one float per (member, term, point), and a year's INDEX values
+Products reg_maps(const greb_reg* r) {
+  auto size = [r](unsigned flag) { return (r->what & flag) ? r->elems() : 0; };
+  return {{"slope", "GREB_R_SLOPE", size(GREB_R_SLOPE)}, {"intercept", "GREB_R_INTERCEPT", size(GREB_R_INTERCEPT)}, {"r2", "GREB_R_R2", size(GREB_R_R2)}};
 }
-
-const char* const kSelRange = " (0 ... 11: a month; 12 ... 16: DJF, MAM, JJA, SON, ANN)";
+Products reg_index(const greb_reg* r) { return {{"index", "GREB_R_INDEX", (r->what & GREB_R_INDEX) ? (size_t)r->nm * r->ni : 0}}; }
 } // namespace
 
 extern "C" {
@@ -1590,10 +1495,7 @@ extern "C" {
 int greb_reg_create(int nx, int ny, int n_members, int n_vars, const float* region_w, int n_regions, const int32_t* control,
                     const greb_reg_index* indices, int n_indices, const greb_reg_term* terms, int n_terms, unsigned what,
                     greb_reg** out) {
-  if (!out) return fail(nullptr, GREB_E_INVALID, "reg_create: `out` is NULL");
-  *out = nullptr;
-  if (int rc = check_grid("reg_create", nx, ny)) return rc;
-  if (int rc = check_n_vars("reg_create", n_vars)) return rc;
+  if (int rc = begin_create("reg_create", out, nx, ny, &n_vars, nullptr)) return rc;
   if (n_members < 1 || n_members > GREB_REG_MAX_MEMBERS) // (the member is a grid dimension of the update and finish kernels)
     return fail(nullptr, GREB_E_INVALID, "reg_create: n_members = " + std::to_string(n_members) + " (1 ... " +
                                              std::to_string(GREB_REG_MAX_MEMBERS) + ")");
@@ -1612,7 +1514,7 @@ int greb_reg_create(int nx, int ny, int n_members, int n_vars, const float* regi
     const std::string who = "reg_create: index " + std::to_string(j) + ": ";
     if (ix.var < 0 || ix.var >= n_vars)
       return fail(nullptr, GREB_E_INVALID, who + "var = " + std::to_string(ix.var) + " (0 ... " + std::to_string(n_vars - 1) + ")");
-    if (ix.sel < 0 || ix.sel >= kRegSelectors) return fail(nullptr, GREB_E_INVALID, who + "sel = " + std::to_string(ix.sel) + kSelRange);
+    if (ix.sel < 0 || ix.sel >= season::kSelectors) return fail(nullptr, GREB_E_INVALID, who + "sel = " + std::to_string(ix.sel) + kSelRange);
     if (ix.rel != 0 && ix.rel != 1) return fail(nullptr, GREB_E_INVALID, who + "rel = " + std::to_string(ix.rel) + " (0 or 1)");
     if (ix.region < 0 || ix.region > n_regions)
       return fail(nullptr, GREB_E_INVALID, who + "region = " + std::to_string(ix.region) + " (0: the globe, ... " + std::to_string(n_regions) + ")");
@@ -1622,7 +1524,7 @@ int greb_reg_create(int nx, int ny, int n_members, int n_vars, const float* regi
     const std::string who = "reg_create: term " + std::to_string(t) + ": ";
     if (tm.var < 0 || tm.var >= n_vars)
       return fail(nullptr, GREB_E_INVALID, who + "var = " + std::to_string(tm.var) + " (0 ... " + std::to_string(n_vars - 1) + ")");
-    if (tm.sel < 0 || tm.sel >= kRegSelectors) return fail(nullptr, GREB_E_INVALID, who + "sel = " + std::to_string(tm.sel) + kSelRange);
+    if (tm.sel < 0 || tm.sel >= season::kSelectors) return fail(nullptr, GREB_E_INVALID, who + "sel = " + std::to_string(tm.sel) + kSelRange);
     if (tm.rel != 0 && tm.rel != 1) return fail(nullptr, GREB_E_INVALID, who + "rel = " + std::to_string(tm.rel) + " (0 or 1)");
     if (tm.index < 0 || tm.index >= n_indices)
       return fail(nullptr, GREB_E_INVALID, who + "index = " + std::to_string(tm.index) + " (0 ... " + std::to_string(n_indices - 1) + ")");
@@ -1633,11 +1535,7 @@ int greb_reg_create(int nx, int ny, int n_members, int n_vars, const float* regi
   for (int j = 0; j < n_indices; ++j) // (one that no term names)
     if (indices[j].rel && !control)
       return fail(nullptr, GREB_E_INVALID, "reg_create: index " + std::to_string(j) + ": rel = 1 (member minus its control) but `control` is NULL");
-  if (control)
-    for (int m = 0; m < n_members; ++m)
-      if (control[m] < -1 || control[m] >= n_members)
-        return fail(nullptr, GREB_E_INVALID, "reg_create: member " + std::to_string(m) + ": control = " + std::to_string(control[m]) +
-                                                 " (-1 = none, or 0 ... " + std::to_string(n_members - 1) + ")");
+  if (int rc = check_control("reg_create", control, n_members)) return rc;
   greb_diag* diag = nullptr;
   if (int rc = make_diag("reg_create", nx, ny, region_w, n_regions, n_vars, &diag)) return rc; // the weights
   greb_reg* r = new (std::nothrow) greb_reg();
@@ -1645,26 +1543,8 @@ int greb_reg_create(int nx, int ny, int n_members, int n_vars, const float* regi
   r->nx = nx; r->ny = ny; r->nm = n_members; r->nv = n_vars; r->nt = n_terms; r->ni = n_indices; r->what = what; r->diag = diag;
   if (control) r->control.assign(control, control + n_members);
   for (int j = 0; j < n_indices; ++j) r->itable.ix[j] = RegIndexTable::Ix{indices[j].var, indices[j].sel, indices[j].rel, indices[j].region};
-  // the terms by variable, then selector (the caller's order among equals); what each variable's terms read
-  std::vector<int> order((size_t)n_terms);
-  for (int i = 0; i < n_terms; ++i) order[(size_t)i] = i;
-  std::stable_sort(order.begin(), order.end(), [terms](int a, int b) {
-    return terms[a].var != terms[b].var ? terms[a].var < terms[b].var : terms[a].sel < terms[b].sel;
-  });
-  RegTable& t = r->table;
-  int v = -1;
-  for (int i = 0; i < n_terms; ++i) {
-    const greb_reg_term& tm = terms[order[(size_t)i]];
-    r->index_of[i] = terms[i].index;
-    t.term[i] = RegTable::Term{tm.sel, tm.rel, tm.index, order[(size_t)i]};
-    if (v < 0 || t.var[v] != tm.var) { ++v; t.var[v] = tm.var; t.vstart[v] = i; }
-    static constexpr int kSeasonMonths[5] = {0x803, 0x01c, 0x0e0, 0x700, 0xfff}; // DJF MAM JJA SON ANN, bit mo
-    const int months = tm.sel < 12 ? 1 << tm.sel : kSeasonMonths[tm.sel - 12];
-    t.months[v] |= months;
-    if (tm.rel) { t.ctl_months[v] |= months; t.rel_sels[v] |= 1 << tm.sel; }
-  }
-  t.n_vars_used = v + 1;
-  t.vstart[t.n_vars_used] = n_terms;
+  for (int i = 0; i < n_terms; ++i) r->index_of[i] = terms[i].index;
+  build_year_table(r->table, terms, n_terms, [](RegTerm& to, const greb_reg_term& tm) { to.index = tm.index; });
   *out = r;
   return 0;
 }
@@ -1678,39 +1558,26 @@ int greb_reg_add_year_dev(greb_reg* r, int device, const float* x_dev, int k, fl
   if (!r) return fail(nullptr, GREB_E_INVALID, "reg_add_year_dev: no plan (greb_reg is NULL)");
   if (!x_dev) return fail(nullptr, GREB_E_INVALID, "reg_add_year_dev: x_dev is NULL");
   if (int rc = check_aligned("reg_add_year_dev", x_dev, "x_dev")) return rc;
-  if ((r->what & GREB_R_INDEX) && !index_dev)
-    return fail(nullptr, GREB_E_INVALID, "reg_add_year_dev: GREB_R_INDEX selected but `index_dev` is NULL");
-  if (k != r->added)
-    return fail(nullptr, GREB_E_INVALID, "reg_add_year_dev: k = " + std::to_string(k) + ", but " + std::to_string(r->added) +
-                                             " years were added since the last finish (years go in ascending order, k = 0 first)");
-  if (k > 0 && device != r->added_device)
-    return fail(nullptr, GREB_E_INVALID, "reg_add_year_dev: device " + std::to_string(device) + ", but this period's state is on device " +
-                                             std::to_string(r->added_device));
+  if (int rc = reg_index(r).check(nullptr, "reg_add_year_dev", &index_dev, "_dev", false)) return rc;
+  if (int rc = r->period.check_add("reg_add_year_dev", k, device)) return rc;
   if (int rc = use_device("reg_add_year_dev: ", device)) return rc;
   greb_reg::Dev* dv = nullptr;
   if (int rc = reg_on_device(r, device, &dv)) return rc;
-  if (int rc = reg_launch_year(nullptr, r, device, dv, x_dev, k, (r->what & GREB_R_INDEX) ? index_dev : nullptr, (size_t)r->ni,
-                               (hipStream_t)stream))
-    return rc;
-  r->added = k + 1; r->added_device = device;
+  if (int rc = reg_launch_year(nullptr, r, device, dv, x_dev, k, index_dev, (size_t)r->ni, (hipStream_t)stream)) return rc;
+  r->period.advance(k, device);
   return 0;
 }
 
 int greb_reg_finish_dev(greb_reg* r, int device, int n_years, float* slope_dev, float* intercept_dev, float* r2_dev, void* stream) {
   if (!r) return fail(nullptr, GREB_E_INVALID, "reg_finish_dev: no plan (greb_reg is NULL)");
   float* out[3] = {slope_dev, intercept_dev, r2_dev};
-  if (int rc = check_reg_maps(nullptr, "reg_finish_dev", r, out, "_dev", true)) return rc;
-  if (n_years != r->added || n_years < 1)
-    return fail(nullptr, GREB_E_INVALID, "reg_finish_dev: n_years = " + std::to_string(n_years) + ", but " + std::to_string(r->added) +
-                                             " years were added since the last finish");
-  if (device != r->added_device)
-    return fail(nullptr, GREB_E_INVALID, "reg_finish_dev: device " + std::to_string(device) + ", but this period's state is on device " +
-                                             std::to_string(r->added_device));
+  if (int rc = reg_maps(r).check(nullptr, "reg_finish_dev", out, "_dev", true)) return rc;
+  if (int rc = r->period.check_finish("reg_finish_dev", n_years, device)) return rc;
   if (int rc = use_device("reg_finish_dev: ", device)) return rc;
   greb_reg::Dev* dv = nullptr;
   if (int rc = reg_on_device(r, device, &dv)) return rc;
   HIP_TRY(nullptr, launch_reg_finish(reg_finish_args(r, dv, n_years, out[0], out[1], out[2]), (hipStream_t)stream));
-  r->added = 0; r->added_device = -1;
+  r->period.reset();
   return 0;
 }
 
@@ -1724,11 +1591,10 @@ int run_reg(const std::string& who, Records src, greb_engine* e, int years, cons
   if (int rc = src.check_plan(e, who, r->nv)) return rc;
   if (years < 1) return fail(e, GREB_E_INVALID, who + ": years = " + std::to_string(years));
   float* host[3] = {slope, intercept, r2};
-  if (int rc = check_reg_maps(e, who, r, host, "", false)) return rc;
+  if (int rc = reg_maps(r).check(e, who, host, "", false)) return rc;
   const bool series = (r->what & GREB_R_INDEX) != 0;
-  if (series && !index) return fail(e, GREB_E_INVALID, who + ": GREB_R_INDEX selected but `index` is NULL");
-  if (r->added != 0)
-    return fail(e, GREB_E_INVALID, who + ": the plan holds " + std::to_string(r->added) + " years of an unfinished period");
+  if (int rc = reg_index(r).check(e, who, &index, "", false)) return rc;
+  if (int rc = r->period.check_idle(e, who)) return rc;
   if (!e || !co2_ppm) return fail(e, GREB_E_INVALID, who + ": bad argument (engine or co2_ppm)");
   if (int rc = check_engine(e, who, r->nx, r->ny, r->nm)) return rc;
   const size_t el = r->elems(), ser = (size_t)r->nm * years * r->ni;
@@ -1749,12 +1615,10 @@ int run_reg(const std::string& who, Records src, greb_engine* e, int years, cons
     }
     return 0;
   };
-  sink.year = [&](const YearCalls& run, int y) -> int {
-    const float* mon = nullptr;
-    if (int rc = src.integrate(e, run, y, &mon)) return rc;
+  sink.year = year_hook(e, &src, [&](const float* mon, int y) -> int {
     return reg_launch_year(e, r, e->device, dv, mon, y, series ? dv->series.get() + (size_t)y * r->ni : nullptr, (size_t)years * r->ni,
                            e->stream);
-  };
+  }, false);
   // The maps, once, after the last year: each selected one is made in the plan's output map and leaves from there.
   sink.finish = [&]() -> int {
     for (int i = 0; i < 3; ++i) {

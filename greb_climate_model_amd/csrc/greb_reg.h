@@ -6,30 +6,24 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "greb_yearwalk.h"
+
 namespace greb {
 
 constexpr int kRegThreads = 256;
 constexpr int kRegMaxTerms = 16;
 constexpr int kRegMaxIndices = 8;
 constexpr int kRegMaxMembers = 65535; // grid.y of the update and finish kernels
-constexpr int kRegSelectors = 17; // 0 ... 11 the months, 12 ... 16 DJF MAM JJA SON ANN (greb_cross.h)
 
-// The plan's terms as the update kernel walks them: sorted by variable, then by selector.  The terms of distinct
-// variable v are term[vstart[v]] ... term[vstart[v + 1] - 1].  Travels by value in the kernel arguments and is read
-// through the scalar cache.
-struct RegTable {
-  struct Term {
-    int sel, rel; // selector, member minus control
-    int index;    // the index it is regressed on
-    int out;      // the term's index in the caller's order: where its state and products lie
-  } term[kRegMaxTerms];
-  int n_vars_used;               // distinct variables among the terms
-  int var[kRegMaxTerms];         // [n_vars_used] the variable
-  int vstart[kRegMaxTerms + 1];  // [n_vars_used + 1]
-  int months[kRegMaxTerms];      // [n_vars_used] bit mo: the variable's terms need month mo of the member
-  int ctl_months[kRegMaxTerms];  // ... of the member's control (the months of the `rel` terms)
-  int rel_sels[kRegMaxTerms];    // [n_vars_used] bit s: a term with selector s is `rel`
+// A term as the update kernel walks the plan's (greb_yearwalk.h: sorted by variable, then by selector).
+struct RegTerm {
+  int sel, rel; // selector, member minus control
+  int index;    // the index it is regressed on
+  int out;      // the term's index in the caller's order: where its state and products lie
 };
+using RegTable = YearTable<RegTerm, kRegMaxTerms>;
+// (the kernels' scalar loads address the table in the kernel arguments)
+static_assert(sizeof(RegTable) == 584 && offsetof(RegTable, vstart) == 324, "the layout greb_reg.hip was written to");
 
 // the indices in the caller's order
 struct RegIndexTable {

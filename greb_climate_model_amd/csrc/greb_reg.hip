@@ -10,28 +10,22 @@
 //                        greb_season.h over the twelve means; `rel`: ONE fp32 subtraction of the control's), year 0 STORES
 //                        g0 and zero sums, later years add G = (double)g - (double)g0 and G * G; G is left for the update
 //                        kernel and g is the year's INDEX.
-//   reg_update_kernel    grid (blocks of 256 point quads, member, distinct variable of the terms), the form of
-//                        cross_update_kernel: a lane owns four consecutive points, loads the months its variable's terms
-//                        need as 16-byte vectors (the control's too where a term is `rel`), walks the terms sorted by
-//                        selector through a table in the kernel arguments, forms each selector's quantity once, and adds
-//                        Y = (double)y - (double)y0, G * Y and Y * Y to the term's sums [member][term][np], one array per
-//                        word.  G is wave-uniform and comes by a scalar load.  Year k = 0 STORES y0 and zero sums: no
-//                        clearing pass.
+//   reg_update_kernel    grid (blocks of 256 point quads, member, distinct variable of the terms): year_walk of
+//                        greb_yearwalk.h, as cross_update_kernel.  Every term adds Y = (double)y - (double)y0, G * Y and
+//                        Y * Y to its sums [member][term][np], one array per word.  G is wave-uniform and comes by a scalar
+//                        load.  Year k = 0 STORES y0 and zero sums: no clearing pass.
 //   reg_finish_kernel    grid (blocks of point quads, member, term): the sums -> slope, intercept, R2.
 //
 // One owner per element, no atomics, no LDS: results are deterministic and a member's numbers do not depend on the batch
 // it is in.  THE ORDER OF OPERATIONS IS THE DEFINITION (regress.reference in Python performs the same IEEE operations):
 // this file is built with -ffp-contract=off (build.py: EXTRA_FLAGS), so that no multiply is fused into the add behind it.
 #include "greb_reg.h"
-#include "greb_season.h"
 
 namespace greb {
 namespace {
 
 using season::f4;
 using season::kMonths;
-using season::months_of;
-using season::quantity; // (greb_season.h: one statement of the yearly quantity for greb_cross and greb_reg)
 using season::series_quantity;
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -95,43 +89,10 @@ __device__ inline void update_term(const RegState& st, size_t g, const f4 y, dou
 
 template <bool FIRST>
 __global__ __launch_bounds__(kRegThreads) void reg_update_kernel(RegUpdateArgs a) {
-  const size_t gp = a.np >> 2, quad = (size_t)blockIdx.x * kRegThreads + threadIdx.x;
-  if (quad >= gp) return;
-  const int m = (int)blockIdx.y, v = (int)blockIdx.z;
-  const int var = a.t.var[v], own = a.t.months[v], rel_sels = a.t.rel_sels[v];
-  const int c = a.control ? a.control[m] : -1;
-  const int ctl = c >= 0 ? a.t.ctl_months[v] : 0;
-  const size_t mon = (size_t)a.n_vars * gp; // quads of one month of one member
-  const f4* xm = reinterpret_cast<const f4*>(a.x) + ((size_t)m * kMonths * a.n_vars + var) * gp + quad;
-  const f4* xc = reinterpret_cast<const f4*>(a.x) + ((size_t)(c >= 0 ? c : 0) * kMonths * a.n_vars + var) * gp + quad;
-  f4 x[kMonths], y[kMonths];
-#pragma unroll
-  for (int mo = 0; mo < kMonths; ++mo) {
-    x[mo] = f4{0.f, 0.f, 0.f, 0.f};
-    if (own >> mo & 1) x[mo] = xm[mo * mon];
-  }
-#pragma unroll
-  for (int mo = 0; mo < kMonths; ++mo) {
-    y[mo] = f4{0.f, 0.f, 0.f, 0.f};
-    if (ctl >> mo & 1) y[mo] = xc[mo * mon];
-  }
-  const float nan = __builtin_nanf("");
-  const f4 nan4 = {nan, nan, nan, nan};
-  const double* G = a.G + (size_t)m * a.n_indices; // (wave-uniform)
-  int i = a.t.vstart[v];
-  const int end = a.t.vstart[v + 1];
-#pragma unroll
-  for (int s = 0; s < kRegSelectors; ++s) {
-    if (i >= end || a.t.term[i].sel != s) continue; // (uniform)
-    const f4 own_a = quantity(s, x);
-    f4 rel_q = nan4; // a member without a control: a quiet NaN
-    if ((rel_sels >> s & 1) && c >= 0) rel_q = own_a - quantity(s, y); // ONE fp32 subtraction
-    for (; i < end && a.t.term[i].sel == s; ++i) {
-      const RegTable::Term t = a.t.term[i];
-      const size_t g = ((size_t)m * a.n_terms + t.out) * gp + quad;
-      update_term<FIRST>(a.st, g, t.rel ? rel_q : own_a, FIRST ? 0.0 : G[t.index]);
-    }
-  }
+  const double* G = a.G + (size_t)(int)blockIdx.y * a.n_indices; // the member's (wave-uniform)
+  year_walk<kRegThreads>(a.t, a.x, a.control, a.np, a.n_vars, a.n_terms, [st = a.st, G](const RegTerm& t, size_t g, const f4 q) {
+    update_term<FIRST>(st, g, q, FIRST ? 0.0 : G[t.index]);
+  });
 }
 
 __global__ __launch_bounds__(kRegThreads) void reg_finish_kernel(RegFinishArgs a) {
@@ -184,7 +145,7 @@ hipError_t launch_reg_index(const RegIndexArgs& a, hipStream_t s) {
     return hipErrorInvalidValue;
   for (int j = 0; j < a.n_indices; ++j) { // what the kernel indexes with: nothing may point outside the regional means
     const RegIndexTable::Ix& ix = a.t.ix[j];
-    if (ix.var < 0 || ix.var >= a.n_vars || ix.sel < 0 || ix.sel >= kRegSelectors || ix.region < 0 || ix.region >= a.nr || (ix.rel && !a.control))
+    if (ix.var < 0 || ix.var >= a.n_vars || ix.sel < 0 || ix.sel >= season::kSelectors || ix.region < 0 || ix.region >= a.nr || (ix.rel && !a.control))
       return hipErrorInvalidValue;
   }
   const size_t total = (size_t)a.n_members * a.n_indices;
@@ -196,18 +157,10 @@ hipError_t launch_reg_update(const RegUpdateArgs& a, hipStream_t s) {
   const RegTable& t = a.t;
   if (!a.x || !a.G || !a.st.y0 || !a.st.sy || !a.st.sgy || a.np < 4 || (a.np & 3) || a.n_members < 1 || a.n_members > kRegMaxMembers ||
       a.n_vars < 1 || a.n_terms < 1 || a.n_terms > kRegMaxTerms || a.n_indices < 1 || a.n_indices > kRegMaxIndices || a.k < 0 ||
-      t.n_vars_used < 1 || t.n_vars_used > a.n_terms || t.vstart[0] != 0 || t.vstart[t.n_vars_used] != a.n_terms)
+      !year_table_ok(t, a.n_vars, a.n_terms, a.control != nullptr))
     return hipErrorInvalidValue;
-  for (int v = 0; v < t.n_vars_used; ++v) { // what the kernel indexes with: nothing may point outside the records or the state
-    if (t.var[v] < 0 || t.var[v] >= a.n_vars || t.vstart[v + 1] <= t.vstart[v]) return hipErrorInvalidValue;
-    for (int i = t.vstart[v]; i < t.vstart[v + 1]; ++i) {
-      const RegTable::Term& tm = t.term[i];
-      if (tm.sel < 0 || tm.sel >= kRegSelectors || tm.out < 0 || tm.out >= a.n_terms || tm.index < 0 || tm.index >= a.n_indices ||
-          (i > t.vstart[v] && tm.sel < t.term[i - 1].sel) || (months_of(tm.sel) & ~t.months[v]) ||
-          (tm.rel && (!a.control || (months_of(tm.sel) & ~t.ctl_months[v]) || !(t.rel_sels[v] >> tm.sel & 1))))
-        return hipErrorInvalidValue;
-    }
-  }
+  for (int i = 0; i < a.n_terms; ++i) // (the G the kernel reads)
+    if (t.item[i].index < 0 || t.item[i].index >= a.n_indices) return hipErrorInvalidValue;
   const size_t gp = a.np >> 2;
   const dim3 grid((unsigned)((gp + kRegThreads - 1) / kRegThreads), (unsigned)a.n_members, (unsigned)t.n_vars_used);
   if (a.k == 0) hipLaunchKernelGGL(reg_update_kernel<true>, grid, dim3(kRegThreads), 0, s, a);
