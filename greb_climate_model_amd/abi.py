@@ -239,6 +239,40 @@ def budget_prototypes(lib) -> None:
         f.restype = C.c_int
 
 
+DERIVE_MAX_INS, DERIVE_MAX_TOTAL, DERIVE_MAX_STACK, DERIVE_MAX_LOCALS, DERIVE_MAX_FIELDS = 64, 512, 8, 4, 8  # GREB_DERIVE_MAX_*
+# the ops of a derive program, GREB_DV_* of include/greb_engine.h in their numbering
+DV_NAMES = ("STATE", "TERM", "FIELD", "CONST", "TEE", "GET", "ADD", "SUB", "MUL", "DIV", "MIN", "MAX", "GE", "LT", "NEG", "ABS", "SQRT",
+            "EXP", "LOG", "ATAN", "SELECT")
+
+
+class GrebDeriveIns(C.Structure):
+    """struct greb_derive_ins: op (GREB_DV_*), arg (the index of STATE, TERM, FIELD, TEE, GET) and value (of CONST)."""
+    _fields_ = [("op", C.c_int32), ("arg", C.c_int32), ("value", C.c_float)]
+
+
+def derive_prototypes(lib) -> None:
+    """The argument types of greb_derive_* and of the seven reduced runs over derived records: those of the budget runs with
+    the derive plan in place of combo and n_out."""
+    i32p, f64p, vp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_void_p
+    lib.greb_derive_create.argtypes = [C.c_int, C.c_int, C.POINTER(GrebDeriveIns), i32p, C.c_int, c_float_p, C.c_int, C.POINTER(vp)]
+    lib.greb_derive_destroy.argtypes = [vp]
+    lib.greb_derive_uses_budget.argtypes = [vp]
+    lib.greb_derive_apply_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
+    head = [vp, C.c_int, c_float_p, vp, vp]  # engine, years, co2_ppm, derive plan, plan
+    lib.greb_engine_run_derived_diag.argtypes = head + [C.c_uint] + [c_float_p] * 4
+    lib.greb_engine_run_derived_clim.argtypes = head + [C.c_int, i32p, i32p] + [c_float_p] * 6
+    lib.greb_engine_run_derived_ens.argtypes = head + [c_float_p] * 6
+    lib.greb_engine_run_derived_lin.argtypes = head + [c_float_p] * 3
+    lib.greb_engine_run_derived_gram.argtypes = head + [f64p, c_float_p]
+    lib.greb_engine_run_derived_cross.argtypes = head + [i32p, i32p, i32p, i32p, c_float_p, i32p] + [c_float_p, c_float_p]
+    lib.greb_engine_run_derived_reg.argtypes = head + [c_float_p] * 5
+    for f in (lib.greb_derive_create, lib.greb_derive_destroy, lib.greb_derive_uses_budget, lib.greb_derive_apply_dev,
+              lib.greb_engine_run_derived_diag, lib.greb_engine_run_derived_clim, lib.greb_engine_run_derived_ens,
+              lib.greb_engine_run_derived_lin, lib.greb_engine_run_derived_gram, lib.greb_engine_run_derived_cross,
+              lib.greb_engine_run_derived_reg):
+        f.restype = C.c_int
+
+
 def nan_overrides(n: int):
     arr = (GrebMemberOverrides * n)()
     for o in arr:

@@ -94,8 +94,11 @@ def as_combo(records):
 
 def record_names(records) -> tuple:
     """The names of the variables a reduced run over `records` delivers: the axis its shapes call [5]."""
+    from . import derive
     if isinstance(records, str) and records == "state":
         return STATE_NAMES
+    if isinstance(records, derive.Program):
+        return records.names
     cb = as_combo(records)
     return TERMS if cb is None else cb.names
 

@@ -16,8 +16,8 @@ LIB = os.path.join(PKG, "libgreb_hip.so")
 # the same sources with -DGREB_TUNING: the timing-experiment knobs of tools/ (GREB_DEBUG_SKIP, GREB_DEBUG_NSUB, ...)
 # exist only in this variant; the release library above never reads the environment
 LIB_TUNING = os.path.join(PKG, "libgreb_hip_tuning.so")
-SOURCES = ["greb_engine.cpp", "greb_run.cpp", "greb_plans.cpp", "greb_members.cpp", "greb_batched.cpp", "greb_kernels.hip", "greb_member.hip", "greb_ensemble.hip", "greb_rows.hip", "greb_step_rows.hip", "greb_circ_rows.hip", "greb_strip_order.cpp", "greb_diag.hip", "greb_clim.hip", "greb_ens.hip", "greb_lin.hip", "greb_fluxes.hip", "greb_gram.hip", "greb_cross.hip", "greb_reg.hip"]
-HEADERS = ["greb_host.h", "greb_device.h", "greb_kernels.h", "greb_stencil.h", "greb_chain6.h", "greb_rows.h", "greb_step_strip.h", "greb_pair.h", "greb_physics_step.h", "greb_diag.h", "greb_clim.h", "greb_ens.h", "greb_lin.h", "greb_fluxes.h", "greb_gram.h", "greb_cross.h", "greb_reg.h", "greb_season.h", "greb_yearwalk.h", os.path.join(ROOT, "include", "greb_engine.h")]
+SOURCES = ["greb_engine.cpp", "greb_run.cpp", "greb_plans.cpp", "greb_members.cpp", "greb_batched.cpp", "greb_kernels.hip", "greb_member.hip", "greb_ensemble.hip", "greb_rows.hip", "greb_step_rows.hip", "greb_circ_rows.hip", "greb_strip_order.cpp", "greb_diag.hip", "greb_clim.hip", "greb_ens.hip", "greb_lin.hip", "greb_fluxes.hip", "greb_gram.hip", "greb_cross.hip", "greb_reg.hip", "greb_derive.hip"]
+HEADERS = ["greb_host.h", "greb_device.h", "greb_kernels.h", "greb_stencil.h", "greb_chain6.h", "greb_rows.h", "greb_step_strip.h", "greb_pair.h", "greb_physics_step.h", "greb_diag.h", "greb_clim.h", "greb_ens.h", "greb_lin.h", "greb_fluxes.h", "greb_gram.h", "greb_cross.h", "greb_reg.h", "greb_derive.h", "greb_season.h", "greb_yearwalk.h", os.path.join(ROOT, "include", "greb_engine.h")]
 # -O2: measured 1.4 % faster than -O3 on the fused member kernel (3 790 vs 3 735 yr/s), equal elsewhere
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value",
                "-I" + os.path.join(ROOT, "include")]
@@ -36,11 +36,13 @@ def hipcc() -> str:
 # accumulation is an explicit fma() of an exact product, and what its definition forbids is a reassociated sum (no fast-math).
 # greb_cross.hip: its season quantity is greb_clim.hip's seasons of one year (cross.reference): the same flag.
 # greb_reg.hip: that quantity, and fp64 sums and a finish whose every operation regress.reference repeats: the same flag.
+# greb_derive.hip: every op of a derive program is one fp32 operation with one rounding (derive.reference): the same flag.
 EXTRA_FLAGS = {"greb_rows.hip": ["-fno-slp-vectorize"], "greb_step_rows.hip": ["-fno-slp-vectorize"],
                "greb_circ_rows.hip": ["-fno-slp-vectorize"], "greb_clim.hip": ["-ffp-contract=off"],
                "greb_ens.hip": ["-ffp-contract=off"], "greb_lin.hip": ["-ffp-contract=off"],
                "greb_fluxes.hip": ["-ffp-contract=off"], "greb_gram.hip": ["-ffp-contract=off"],
-               "greb_cross.hip": ["-ffp-contract=off"], "greb_reg.hip": ["-ffp-contract=off"]}
+               "greb_cross.hip": ["-ffp-contract=off"], "greb_reg.hip": ["-ffp-contract=off"],
+               "greb_derive.hip": ["-ffp-contract=off"]}
 OBJ_DIR = os.path.join(PKG, "csrc", "_obj")
 
 

@@ -73,6 +73,7 @@ struct greb_engine {
   float* ens_out = nullptr; size_t ens_out_cap = 0;   // run_ens: the group statistics of two years (one per output slot)
   float* lin_out = nullptr; size_t lin_out_cap = 0;   // run_lin: the coefficients and the residual map of two years (likewise)
   double* gram_out = nullptr; size_t gram_out_cap = 0; // run_gram: the matrices of two years (likewise), in doubles
+  float* derive_out = nullptr; size_t derive_out_cap = 0; // run_derived_*: one year of derived records [nm][12][n_out][np]
   // host copies needed later
   std::vector<greb::RowTables> h_tabs;
   std::vector<int> h_tab_index;

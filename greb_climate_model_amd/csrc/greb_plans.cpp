@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <initializer_list>
 #include <new>
 
@@ -16,6 +17,7 @@
 #include "greb_cross.h"
 #include "greb_reg.h"
 #include "greb_fluxes.h"
+#include "greb_derive.h"
 
 using namespace greb;
 using namespace greb::host;
@@ -26,6 +28,11 @@ static_assert(kRegMaxTerms == GREB_REG_MAX_TERMS && kRegMaxIndices == GREB_REG_M
                   sizeof(greb_reg_term) == 16 && season::kSelectors == 17 && kRegMaxMembers == GREB_REG_MAX_MEMBERS,
               "greb_reg.h mirrors include/greb_engine.h");
 static_assert(kFluxTerms == GREB_NBUDGET && kFluxMaxOut == GREB_MAX_RECORD_VARS, "greb_fluxes.h mirrors include/greb_engine.h");
+static_assert(kDeriveStates == GREB_NVAR_OUT && kDeriveTerms == GREB_NBUDGET && kDeriveMaxOut == GREB_MAX_RECORD_VARS &&
+                  kDeriveMaxIns == GREB_DERIVE_MAX_INS && kDeriveMaxTotal == GREB_DERIVE_MAX_TOTAL &&
+                  kDeriveMaxStack == GREB_DERIVE_MAX_STACK && kDeriveMaxLocals == GREB_DERIVE_MAX_LOCALS &&
+                  kDeriveMaxFields == GREB_DERIVE_MAX_FIELDS && kDeriveOps == GREB_DV_SELECT + 1 && sizeof(greb_derive_ins) == 12,
+              "greb_derive.h mirrors include/greb_engine.h");
 
 namespace {
 constexpr int kStateVars = GREB_NVAR_OUT; // the variables of a year of state records
@@ -64,14 +71,29 @@ int make_combo(greb_engine* e, const std::string& who, const float* combo, int n
   return 0;
 }
 
+// what Records asks of a derive plan (greb_derive, below)
+int derive_n_out(const greb_derive* v);
+int derive_check_engine(greb_engine* e, const std::string& who, const greb_derive* v);
+int derive_on_engine(greb_engine* e, greb_derive* v);
+int derive_year(greb_engine* e, greb_derive* v, const float* state, const float* budget, float* out);
+
 // Where the records a reduced run hands its plan come from: the year's five state records (greb_engine_run_diag, ...), or
 // its budget records -- the thirteen terms as the step kernels leave them, or their combinations (greb_engine_run_budget_diag,
-// ...).  One year at a time in e->budget_dev: the terms in front, the combinations behind them; everything that reads a
-// year is enqueued on the compute stream before the next year's kernels.
+// ...) --, or records derived from either (greb_engine_run_derived_diag, ...).  One year at a time in e->budget_dev: the terms
+// in front, the combinations behind them; the derived records in e->derive_out; everything that reads a year is enqueued
+// on the compute stream before the next year's kernels.
 struct Records {
   int nv = kStateVars; // variables per month
   bool budget = false, combine = false;
   FluxCombo combo{};
+  greb_derive* derive = nullptr;
+  // the outputs of `v`: integrated as a state run where no output names a term, else as a budget run
+  int init_derived(greb_engine* e, const std::string& who, greb_derive* v) {
+    if (!v) return fail(e, GREB_E_INVALID, who + ": no derive plan (greb_derive is NULL)");
+    if (e) if (int rc = derive_check_engine(e, who, v)) return rc;
+    derive = v; budget = greb_derive_uses_budget(v) != 0; nv = derive_n_out(v);
+    return 0;
+  }
   // the state records, the terms (combo == NULL) or the rows of combo; `who` names the entry point
   int init(greb_engine* e, const std::string& who, bool from_budget, const float* c, int n_out) {
     budget = from_budget;
@@ -92,6 +114,10 @@ struct Records {
   static size_t terms_year(const greb_engine* e) { return (size_t)e->nm * 12 * GREB_NBUDGET * (size_t)e->np; }
   // as run_records with a budget: the sums made and zeroed on first use, the call counted
   int prepare(greb_engine* e) const {
+    if (derive) {
+      if (int rc = ensure(e, &e->derive_out, &e->derive_out_cap, year(e))) return rc;
+      if (int rc = derive_on_engine(e, derive)) return rc;
+    }
     if (!budget) return 0;
     if (!e->bsum) {
       const size_t n = (size_t)e->nm * GREB_NBUDGET * (size_t)e->np;
@@ -106,11 +132,18 @@ struct Records {
     if (!budget) {
       float* mon = staging_slot(e, y);
       *rec = mon;
-      return run.integrate(y, {mon, 1, 0});
+      if (int rc = run.integrate(y, {mon, 1, 0})) return rc;
+      if (!derive) return 0;
+      *rec = e->derive_out;
+      return derive_year(e, derive, mon, nullptr, e->derive_out);
     }
-    // (the kernels write their five records regardless -- into a staging slot nobody reads)
+    // (the kernels write their five records regardless -- into a staging slot only a derive stage reads)
     if (int rc = run.integrate(y, {staging_slot(e, 0), 1, 0, e->budget_dev, 1, 0})) return rc;
     *rec = e->budget_dev;
+    if (derive) {
+      *rec = e->derive_out;
+      return derive_year(e, derive, staging_slot(e, 0), e->budget_dev, e->derive_out);
+    }
     if (!combine) return 0;
     float* out = e->budget_dev + terms_year(e);
     HIP_TRY(e, launch_budget_combine(combo, e->budget_dev, e->nm, (size_t)e->np, out, e->stream));
@@ -1650,6 +1683,254 @@ int greb_engine_run_budget_reg(greb_engine* e, int years, const float* co2_ppm, 
   Records src;
   if (int rc = src.init(e, "run_budget_reg", true, combo, n_out)) return rc;
   return run_reg("run_budget_reg", src, e, years, co2_ppm, r, slope, intercept, r2, index, yearly);
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------- derived records (greb_derive.hip)
+// Grid, the outputs' programs as the kernel walks them (DeriveWord: the stack slot of every instruction decided here), the
+// records they name in ascending order and the caller's fields.  Per device: the program's and the fields' copies.
+struct greb_derive {
+  int nx = 0, ny = 0, n_out = 0, n_fields = 0;
+  std::vector<DeriveWord> words;
+  std::vector<unsigned char> src; // the inputs named: j < 5 state j, j < 18 term j - 5, else field j - 18
+  bool uses_budget = false;
+  int stack_cols = 1, local_cols = 0; // what the kernel keeps in LDS: the deepest stack less its top (at least 1), the locals set
+  std::vector<float> fields;      // [n_fields][ny][nx]
+  struct Dev { DevBuf<DeriveWord> words; DevBuf<float> fields; };
+  PerDevice<Dev> devs;
+};
+
+namespace {
+int derive_n_out(const greb_derive* v) { return v->n_out; }
+int derive_check_engine(greb_engine* e, const std::string& who, const greb_derive* v) { return check_engine(e, who, v->nx, v->ny, -1); }
+
+int derive_on_device(greb_derive* v, int device, greb_derive::Dev** out) {
+  return v->devs.get(device, [v](greb_derive::Dev& n) -> int {
+    HIP_TRY(nullptr, n.words.upload(v->words.data(), v->words.size()));
+    if (v->n_fields) HIP_TRY(nullptr, n.fields.upload(v->fields.data(), v->fields.size()));
+    return 0;
+  }, out);
+}
+int derive_on_engine(greb_engine* e, greb_derive* v) {
+  greb_derive::Dev* dv = nullptr;
+  return derive_on_device(v, e->device, &dv);
+}
+
+int derive_launch(greb_engine* e, greb_derive* v, int device, const float* state, const float* budget, int n_members, float* out,
+                  hipStream_t stream) {
+  greb_derive::Dev* dv = nullptr;
+  if (int rc = derive_on_device(v, device, &dv)) return rc;
+  DeriveArgs a{};
+  a.prog = dv->words.get(); a.fields = dv->fields.get(); a.state = state; a.budget = budget; a.out = out;
+  a.np = (size_t)v->nx * v->ny; a.n_words = (int)v->words.size(); a.n_out = v->n_out; a.n_in = (int)v->src.size();
+  a.stack_cols = v->stack_cols; a.local_cols = v->local_cols;
+  for (size_t s = 0; s < v->src.size(); ++s) a.src[s] = v->src[s];
+  HIP_TRY(e, launch_derive(a, n_members, stream));
+  return 0;
+}
+int derive_year(greb_engine* e, greb_derive* v, const float* state, const float* budget, float* out) {
+  return derive_launch(e, v, e->device, state, budget, e->nm, out, e->stream);
+}
+} // namespace
+
+extern "C" {
+
+int greb_derive_create(int nx, int ny, const greb_derive_ins* ins, const int32_t* n_ins, int n_out, const float* fields,
+                       int n_fields, greb_derive** out) {
+  const std::string who = "derive_create";
+  if (int rc = begin_create(who, out, nx, ny, nullptr, nullptr)) return rc;
+  if (int rc = check_count(nullptr, who, "n_out", n_out, GREB_MAX_RECORD_VARS)) return rc;
+  if (!ins || !n_ins) return fail(nullptr, GREB_E_INVALID, who + ": `ins` or `n_ins` is NULL");
+  if (n_fields < 0 || n_fields > GREB_DERIVE_MAX_FIELDS)
+    return fail(nullptr, GREB_E_INVALID, who + ": n_fields = " + std::to_string(n_fields) + " (0 ... " +
+                                             std::to_string(GREB_DERIVE_MAX_FIELDS) + ")");
+  if (n_fields > 0 && !fields) return fail(nullptr, GREB_E_INVALID, who + ": `fields` is NULL with n_fields > 0");
+  long long total = 0;
+  for (int k = 0; k < n_out; ++k) {
+    if (n_ins[k] < 1 || n_ins[k] > GREB_DERIVE_MAX_INS)
+      return fail(nullptr, GREB_E_INVALID, who + ": output " + std::to_string(k) + " has " + std::to_string(n_ins[k]) +
+                                               " instructions (1 ... " + std::to_string(GREB_DERIVE_MAX_INS) + ")");
+    total += n_ins[k];
+  }
+  if (total > GREB_DERIVE_MAX_TOTAL)
+    return fail(nullptr, GREB_E_INVALID, who + ": " + std::to_string(total) + " instructions in all (at most " +
+                                             std::to_string(GREB_DERIVE_MAX_TOTAL) + ")");
+  const size_t np = (size_t)nx * ny;
+  for (int f = 0; f < n_fields; ++f)
+    for (size_t i = 0; i < np; ++i)
+      if (!std::isfinite(fields[(size_t)f * np + i])) {
+        char buf[160];
+        std::snprintf(buf, sizeof(buf), ": field %d: value %g at row %zu, column %zu is not finite", f, (double)fields[(size_t)f * np + i],
+                      i / (size_t)nx, i % (size_t)nx);
+        return fail(nullptr, GREB_E_INVALID, who + buf);
+      }
+  // First pass: the inputs named, so that an input's slot among the loaded ones is known.  (Indices are checked below.)
+  unsigned named = 0;
+  for (long long i = 0; i < total; ++i) {
+    if (ins[i].op == GREB_DV_STATE && ins[i].arg >= 0 && ins[i].arg < kDeriveStates) named |= 1u << ins[i].arg;
+    if (ins[i].op == GREB_DV_TERM && ins[i].arg >= 0 && ins[i].arg < kDeriveTerms) named |= 1u << (kDeriveStates + ins[i].arg);
+    if (ins[i].op == GREB_DV_FIELD && ins[i].arg >= 0 && ins[i].arg < n_fields) named |= 1u << (kDeriveRecords + ins[i].arg);
+  }
+  int slot_of[kDeriveInputs] = {};
+  std::vector<unsigned char> src;
+  for (int j = 0; j < kDeriveInputs; ++j)
+    if ((named >> j) & 1u) { slot_of[j] = (int)src.size(); src.push_back((unsigned char)j); }
+  std::vector<DeriveWord> words;
+  int deepest = 1, locals = 0;
+  const greb_derive_ins* in = ins;
+  for (int k = 0; k < n_out; in += n_ins[k], ++k) {
+    int depth = 0;
+    unsigned set = 0; // locals set so far in this output
+    for (int i = 0; i < n_ins[k]; ++i) {
+      const int op = in[i].op, arg = in[i].arg;
+      const std::string at = who + ": output " + std::to_string(k) + ", instruction " + std::to_string(i);
+      auto index_in = [&](const char* what, int n) -> int {
+        if (arg >= 0 && arg < n) return 0;
+        return fail(nullptr, GREB_E_INVALID, at + ": " + what + " " + std::to_string(arg) + " (0 ... " + std::to_string(n - 1) + ")");
+      };
+      if (op < 0 || op >= kDeriveOps) return fail(nullptr, GREB_E_INVALID, at + ": unknown op " + std::to_string(op));
+      int pops = 0, word_arg = 0;
+      bool pushes = true;
+      switch (op) {
+        case GREB_DV_STATE:
+          if (int rc = index_in("state record", kDeriveStates)) return rc;
+          word_arg = slot_of[arg];
+          break;
+        case GREB_DV_TERM:
+          if (int rc = index_in("budget term", kDeriveTerms)) return rc;
+          word_arg = slot_of[kDeriveStates + arg];
+          break;
+        case GREB_DV_FIELD:
+          if (n_fields == 0) return fail(nullptr, GREB_E_INVALID, at + ": FIELD " + std::to_string(arg) + ", but the plan has no fields (n_fields = 0)");
+          if (int rc = index_in("field", n_fields)) return rc;
+          word_arg = slot_of[kDeriveRecords + arg];
+          break;
+        case GREB_DV_CONST: {
+          if (!std::isfinite(in[i].value)) {
+            char buf[64];
+            std::snprintf(buf, sizeof(buf), ": CONST %g is not finite", (double)in[i].value);
+            return fail(nullptr, GREB_E_INVALID, at + buf);
+          }
+          static_assert(sizeof(float) == sizeof(int32_t), "the value's bits travel in a word");
+          std::memcpy(&word_arg, &in[i].value, sizeof(float));
+        } break;
+        case GREB_DV_TEE:
+          if (int rc = index_in("local", GREB_DERIVE_MAX_LOCALS)) return rc;
+          pops = 1; word_arg = arg; // (the top stays where it is)
+          break;
+        case GREB_DV_GET:
+          if (int rc = index_in("local", GREB_DERIVE_MAX_LOCALS)) return rc;
+          if (!((set >> arg) & 1u))
+            return fail(nullptr, GREB_E_INVALID, at + ": GET of local " + std::to_string(arg) + ", which no earlier TEE of this output set");
+          word_arg = arg;
+          break;
+        case GREB_DV_SELECT: pops = 3; break;
+        default: pops = op >= GREB_DV_NEG ? 1 : 2; break;
+      }
+      if (depth < pops)
+        return fail(nullptr, GREB_E_INVALID, at + ": stack underflow (the op takes " + std::to_string(pops) + " values, the stack holds " +
+                                                 std::to_string(depth) + ")");
+      if (op == GREB_DV_TEE) { set |= 1u << arg; pushes = false; pops = 0; locals = std::max(locals, arg + 1); }
+      depth -= pops;
+      // the slot the result goes to; TEE: the slot it copies
+      const int slot = op == GREB_DV_TEE ? depth - 1 : depth;
+      if (pushes) ++depth;
+      if (depth > GREB_DERIVE_MAX_STACK)
+        return fail(nullptr, GREB_E_INVALID, at + ": the stack would hold " + std::to_string(depth) + " values (at most " +
+                                                 std::to_string(GREB_DERIVE_MAX_STACK) + ")");
+      deepest = std::max(deepest, depth);
+      words.push_back({op * 8 + slot, word_arg});
+    }
+    if (depth != 1)
+      return fail(nullptr, GREB_E_INVALID, who + ": output " + std::to_string(k) + ", instruction " + std::to_string(n_ins[k] - 1) +
+                                               ": the program leaves " + std::to_string(depth) + " values on the stack (exactly one is the output)");
+    words.push_back({kDeriveStore * 8, k});
+  }
+  greb_derive* v = new (std::nothrow) greb_derive();
+  if (!v) return fail(nullptr, GREB_E_INVALID, "out of host memory");
+  v->nx = nx; v->ny = ny; v->n_out = n_out; v->n_fields = n_fields;
+  v->words = std::move(words); v->src = std::move(src);
+  v->stack_cols = std::max(1, deepest - 1); v->local_cols = locals;
+  v->uses_budget = ((named >> kDeriveStates) & ((1u << kDeriveTerms) - 1u)) != 0;
+  if (n_fields) v->fields.assign(fields, fields + (size_t)n_fields * np);
+  *out = v;
+  return 0;
+}
+
+int greb_derive_destroy(greb_derive* v) {
+  delete v; // (PerDevice waits for each device before the program's copy goes)
+  return 0;
+}
+
+int greb_derive_uses_budget(const greb_derive* v) { return v && v->uses_budget ? 1 : 0; }
+
+int greb_derive_apply_dev(greb_derive* v, int device, const float* state_year_dev, const float* budget_year_dev, int n_members,
+                          float* out_dev, void* stream) {
+  const std::string who = "derive_apply_dev";
+  if (!v) return fail(nullptr, GREB_E_INVALID, who + ": no plan (greb_derive is NULL)");
+  if (!state_year_dev || !out_dev) return fail(nullptr, GREB_E_INVALID, who + ": state_year_dev or out_dev is NULL");
+  if (v->uses_budget && !budget_year_dev)
+    return fail(nullptr, GREB_E_INVALID, who + ": budget_year_dev is NULL, but the program names a budget term (GREB_DV_TERM)");
+  if (n_members < 1) return fail(nullptr, GREB_E_INVALID, who + ": n_members = " + std::to_string(n_members));
+  if (int rc = check_aligned(who, state_year_dev, "state_year_dev")) return rc;
+  if (int rc = check_aligned(who, budget_year_dev, "budget_year_dev")) return rc;
+  if (int rc = check_aligned(who, out_dev, "out_dev")) return rc;
+  if (int rc = use_device("derive_apply_dev: ", device)) return rc;
+  return derive_launch(nullptr, v, device, state_year_dev, v->uses_budget ? budget_year_dev : nullptr, n_members, out_dev,
+                       (hipStream_t)stream);
+}
+
+int greb_engine_run_derived_diag(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_diag* d, unsigned what,
+                                 float* regions, float* zonal, float* annual, float* yearly) {
+  Records src;
+  if (int rc = src.init_derived(e, "run_derived_diag", v)) return rc;
+  return run_diag("run_derived_diag", src, e, years, co2_ppm, d, what, regions, zonal, annual, yearly);
+}
+
+int greb_engine_run_derived_clim(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_clim* c, int n_periods,
+                                 const int32_t* first_year, const int32_t* n_years, float* mean, float* seasons, float* trend,
+                                 float* mean_resp, float* seasons_resp, float* yearly) {
+  Records src;
+  if (int rc = src.init_derived(e, "run_derived_clim", v)) return rc;
+  return run_clim("run_derived_clim", src, e, years, co2_ppm, c, n_periods, first_year, n_years, mean, seasons, trend, mean_resp,
+                  seasons_resp, yearly);
+}
+
+int greb_engine_run_derived_ens(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_ens* s, float* mean,
+                                float* var, float* min, float* max, float* quant, float* yearly) {
+  Records src;
+  if (int rc = src.init_derived(e, "run_derived_ens", v)) return rc;
+  return run_ens("run_derived_ens", src, e, years, co2_ppm, s, mean, var, min, max, quant, yearly);
+}
+
+int greb_engine_run_derived_lin(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_lin* l, float* coef,
+                                float* rss, float* yearly) {
+  Records src;
+  if (int rc = src.init_derived(e, "run_derived_lin", v)) return rc;
+  return run_lin("run_derived_lin", src, e, years, co2_ppm, l, coef, rss, yearly);
+}
+
+int greb_engine_run_derived_gram(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_gram* g, double* G,
+                                 float* yearly) {
+  Records src;
+  if (int rc = src.init_derived(e, "run_derived_gram", v)) return rc;
+  return run_gram("run_derived_gram", src, e, years, co2_ppm, g, G, yearly);
+}
+
+int greb_engine_run_derived_cross(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_cross* c, int32_t* first,
+                                  int32_t* last, int32_t* stay, int32_t* count, float* peak, int32_t* peak_year, float* fraction,
+                                  float* yearly) {
+  Records src;
+  if (int rc = src.init_derived(e, "run_derived_cross", v)) return rc;
+  return run_cross("run_derived_cross", src, e, years, co2_ppm, c, first, last, stay, count, peak, peak_year, fraction, yearly);
+}
+
+int greb_engine_run_derived_reg(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_reg* r, float* slope,
+                                float* intercept, float* r2, float* index, float* yearly) {
+  Records src;
+  if (int rc = src.init_derived(e, "run_derived_reg", v)) return rc;
+  return run_reg("run_derived_reg", src, e, years, co2_ppm, r, slope, intercept, r2, index, yearly);
 }
 
 } // extern "C"

@@ -51,6 +51,7 @@ def lib() -> C.CDLL:
         abi.gram_prototypes(L)
         abi.cross_prototypes(L)
         abi.reg_prototypes(L)
+        abi.derive_prototypes(L)
         _lib = L
     return _lib
 
@@ -78,7 +79,10 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_cross_create", "greb_cross_destroy", "greb_cross_add_year_dev", "greb_cross_finish_dev", "greb_engine_run_cross",
            "greb_engine_run_budget_cross",
            "greb_reg_create", "greb_reg_destroy", "greb_reg_add_year_dev", "greb_reg_finish_dev", "greb_engine_run_reg",
-           "greb_engine_run_budget_reg"]
+           "greb_engine_run_budget_reg",
+           "greb_derive_create", "greb_derive_destroy", "greb_derive_uses_budget", "greb_derive_apply_dev",
+           "greb_engine_run_derived_diag", "greb_engine_run_derived_clim", "greb_engine_run_derived_ens", "greb_engine_run_derived_lin",
+           "greb_engine_run_derived_gram", "greb_engine_run_derived_cross", "greb_engine_run_derived_reg"]
 
 
 def _check(rc: int, h=None):
@@ -278,10 +282,15 @@ class Engine:
     def _reduced(self, name: str, records, co2, plan, *args):
         """Call the reduced run `name` ("diag", "clim", "ens", "lin", "gram", "cross", "reg") over `records`: "state" -- the year's five state
         records (greb_engine_run_<name>) --, "budget" -- its thirteen flux terms -- or a budget.Combo -- sums of them
-        (greb_engine_run_budget_<name>).  `args`: what follows the plan in the C call."""
-        from . import budget
+        (greb_engine_run_budget_<name>) -- or a derive.Program -- per-point expressions of either
+        (greb_engine_run_derived_<name>).  `args`: what follows the plan in the C call."""
+        from . import budget, derive
         if isinstance(records, str) and records == "state":
             _check(getattr(lib(), "greb_engine_run_" + name)(self.h, int(co2.shape[1]), abi.fptr(co2), plan.h, *args), self.h)
+            return
+        if isinstance(records, derive.Program):
+            _check(getattr(lib(), "greb_engine_run_derived_" + name)(self.h, int(co2.shape[1]), abi.fptr(co2),
+                                                                     records.handle(self.nx, self.ny), plan.h, *args), self.h)
             return
         cb = budget.as_combo(records)
         _check(getattr(lib(), "greb_engine_run_budget_" + name)(self.h, int(co2.shape[1]), abi.fptr(co2),
@@ -293,8 +302,8 @@ class Engine:
         zonal means and annual-mean maps made on the device year by year (greb_engine_run_diag).  what: abi.D_* bits,
         default all three.  Returns a diag.Result (regions, zonal, annual, yearly, region names; a product that was
         not selected is None).  State, clock and yearly are those of run() over the same years.
-        records: "state" (the five state records), "budget" (the thirteen flux terms of run_budget) or a budget.combo(...)
-        (sums of them); the plan's n_vars must be that count, which stands where the shapes say 5, and the result
+        records: "state" (the five state records), "budget" (the thirteen flux terms of run_budget), a budget.combo(...)
+        (sums of them) or a derive.program(...) (per-point expressions of either); the plan's n_vars must be that count, which stands where the shapes say 5, and the result
         carries the variables' names (Result.vars)."""
         from . import budget, diag
         what = diag.ALL if what is None else int(what)

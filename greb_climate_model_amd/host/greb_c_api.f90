@@ -44,6 +44,12 @@ module greb_c_api
   type, bind(C) :: greb_reg_term
      integer(c_int32_t) :: var, sel, rel, index
   end type greb_reg_term
+  ! an instruction of a derive program (greb_derive_create): op (GREB_DV_* of greb_engine.h), arg (the 0-based index of STATE,
+  ! TERM, FIELD, TEE, GET) and value (of CONST)
+  type, bind(C) :: greb_derive_ins
+     integer(c_int32_t) :: op, arg
+     real(c_float) :: value
+  end type greb_derive_ins
 
   interface
      subroutine greb_params_default(p) bind(C, name="greb_params_default")
@@ -359,6 +365,94 @@ module greb_c_api
        import :: c_int, c_ptr, c_float
        type(c_ptr), value :: eng, combo, plan, slope, intercept, r2, index
        integer(c_int), value :: years, n_out
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
+     ! derived records (greb_derive.hip): a plan = grid, the outputs' postfix programs one after the other in ins(*) with their
+     ! lengths n_ins(n_out), and fields(nx,ny,n_fields) shared by all members (c_null_ptr with n_fields = 0)
+     integer(c_int) function greb_derive_create(nx, ny, ins, n_ins, n_out, fields, n_fields, plan) &
+          bind(C, name="greb_derive_create")
+       import :: c_int, c_int32_t, c_ptr, greb_derive_ins
+       integer(c_int), value :: nx, ny, n_out, n_fields
+       type(greb_derive_ins), intent(in) :: ins(*)
+       integer(c_int32_t), intent(in) :: n_ins(*)
+       type(c_ptr), value :: fields
+       type(c_ptr), intent(out) :: plan
+     end function
+     integer(c_int) function greb_derive_destroy(plan) bind(C, name="greb_derive_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan
+     end function
+     ! 1: some output names a budget term
+     integer(c_int) function greb_derive_uses_budget(plan) bind(C, name="greb_derive_uses_budget")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan
+     end function
+     ! device pointers (c_ptr): state_year_dev(nx,ny,5,12,n_members), budget_year_dev(nx,ny,13,12,n_members) (c_null_ptr where no
+     ! output names a term) -> out_dev(nx,ny,n_out,12,n_members); launches on `stream`, no synchronisation
+     integer(c_int) function greb_derive_apply_dev(plan, device, state_year_dev, budget_year_dev, n_members, out_dev, stream) &
+          bind(C, name="greb_derive_apply_dev")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: plan, state_year_dev, budget_year_dev, out_dev, stream
+       integer(c_int), value :: device, n_members
+     end function
+     ! the seven reduced runs over the derived records of `derive`: the arguments of the budget run of the same name with the
+     ! derive plan in place of combo and n_out; the output arrays as c_ptr (c_loc; c_null_ptr: a product not selected)
+     integer(c_int) function greb_engine_run_derived_diag(eng, years, co2_ppm, derive, plan, what, regions, zonal, annual, yearly) &
+          bind(C, name="greb_engine_run_derived_diag")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, derive, plan, regions, zonal, annual
+       integer(c_int), value :: years, what
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
+     integer(c_int) function greb_engine_run_derived_clim(eng, years, co2_ppm, derive, plan, n_periods, first_year, n_years, &
+          mean, seasons, trend, mean_resp, seasons_resp, yearly) &
+          bind(C, name="greb_engine_run_derived_clim")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, derive, plan, first_year, n_years, mean, seasons, trend, mean_resp, seasons_resp
+       integer(c_int), value :: years, n_periods
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
+     integer(c_int) function greb_engine_run_derived_ens(eng, years, co2_ppm, derive, plan, mean, var, vmin, vmax, quant, yearly) &
+          bind(C, name="greb_engine_run_derived_ens")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, derive, plan, mean, var, vmin, vmax, quant
+       integer(c_int), value :: years
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
+     integer(c_int) function greb_engine_run_derived_lin(eng, years, co2_ppm, derive, plan, coef, rss, yearly) &
+          bind(C, name="greb_engine_run_derived_lin")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, derive, plan, coef, rss
+       integer(c_int), value :: years
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
+     integer(c_int) function greb_engine_run_derived_gram(eng, years, co2_ppm, derive, plan, G, yearly) &
+          bind(C, name="greb_engine_run_derived_gram")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, derive, plan, G
+       integer(c_int), value :: years
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
+     integer(c_int) function greb_engine_run_derived_cross(eng, years, co2_ppm, derive, plan, first, last, stay, count, peak, &
+          peak_year, fraction, yearly) &
+          bind(C, name="greb_engine_run_derived_cross")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, derive, plan, first, last, stay, count, peak, peak_year, fraction
+       integer(c_int), value :: years
+       real(c_float), intent(in) :: co2_ppm(*)
+       real(c_float), intent(out) :: yearly(*)
+     end function
+     integer(c_int) function greb_engine_run_derived_reg(eng, years, co2_ppm, derive, plan, slope, intercept, r2, index, yearly) &
+          bind(C, name="greb_engine_run_derived_reg")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: eng, derive, plan, slope, intercept, r2, index
+       integer(c_int), value :: years
        real(c_float), intent(in) :: co2_ppm(*)
        real(c_float), intent(out) :: yearly(*)
      end function

@@ -675,6 +675,107 @@ int greb_engine_run_reg(greb_engine* e, int years, const float* co2_ppm, greb_re
 int greb_engine_run_budget_reg(greb_engine* e, int years, const float* co2_ppm, const float* combo, int n_out, greb_reg* r,
                                float* slope, float* intercept, float* r2, float* index, float* yearly);
 
+/* ---- derived records: per-point expressions of state and flux terms, formed before the reduction ------
+ * The three record sources above are linear in the records and have no constant term.  Relative humidity q / q_sat(T),
+ * ice cover as an indicator (albedo >= 0.4), a wet-bulb temperature, the Bowen ratio, even degrees Celsius are not: their
+ * mean, variance, quantile, crossing or regression cannot be made afterwards from the products of the plans, so the
+ * quantity is formed from each month's record BEFORE the reduction (greb_derive.hip), where the year's records lie:
+ *   state [n_members][12][5][np], budget [n_members][12][GREB_NBUDGET][np] where the program names a term
+ *     ->  derived [n_members][12][n_out][np]
+ * which every plan kind reduces exactly as it reduces the rows of a combo.  A plan holds the grid, n_out outputs
+ * (1 ... GREB_MAX_RECORD_VARS), per output a postfix program of greb_derive_ins and up to GREB_DERIVE_MAX_FIELDS 2-D
+ * fields [n_fields][ny][nx] of the caller's (exp(-z_topo / z_air), a land mask).  THE FIELDS ARE SHARED BY ALL MEMBERS: a
+ * member on a boundary set that replaces z_topo still sees the field the caller passed.  Limits: per output at most
+ * GREB_DERIVE_MAX_INS instructions, a stack of at most GREB_DERIVE_MAX_STACK values and GREB_DERIVE_MAX_LOCALS locals; at
+ * most GREB_DERIVE_MAX_TOTAL instructions in all.  An output's program runs on an empty stack and must leave one value.
+ *   push     GREB_DV_STATE i (0 ... 4: Tsurf, Tair, Tocean, q, albedo)   GREB_DV_TERM j (0 ... GREB_NBUDGET - 1)
+ *            GREB_DV_FIELD f (0 ... n_fields - 1)   GREB_DV_CONST value
+ *   locals   GREB_DV_TEE k: copy the top to local k, keep it on the stack   GREB_DV_GET k: push local k (set earlier in
+ *            the same output)
+ *   binary   pops b, then a, pushes  ADD a + b   SUB a - b   MUL a * b   DIV a / b   MIN a < b ? a : b   MAX a > b ? a : b
+ *            GE a >= b ? 1 : 0   LT a < b ? 1 : 0
+ *   unary    NEG (the sign bit flipped)  ABS  SQRT  EXP  LOG  ATAN
+ *   ternary  GREB_DV_SELECT pops b, a, c and pushes c != 0 ? a : b
+ * THE SEMANTICS ARE THE DEFINITION OF THE RESULTS: every arithmetic op is one IEEE fp32 operation with one rounding,
+ * nothing is fused or reassociated; DIV and SQRT are correctly rounded; MIN and MAX are the comparisons written above, so
+ * a NaN in b is taken and a NaN in a is not; GE and LT are false with a NaN, SELECT takes a for a NaN condition; EXP, LOG
+ * and ATAN convert the fp32 operand to fp64, call the fp64 function and round once to fp32 (two fp64 libraries may differ
+ * in the last fp64 bit, which moves the fp32 result only next to a rounding boundary).  Operands or results of DIV and
+ * SQRT that are subnormal in fp32 are outside this contract.  derive.reference in Python performs the same operations. */
+#define GREB_DERIVE_MAX_INS    64
+#define GREB_DERIVE_MAX_TOTAL  512
+#define GREB_DERIVE_MAX_STACK  8
+#define GREB_DERIVE_MAX_LOCALS 4
+#define GREB_DERIVE_MAX_FIELDS 8
+#define GREB_DV_STATE  0
+#define GREB_DV_TERM   1
+#define GREB_DV_FIELD  2
+#define GREB_DV_CONST  3
+#define GREB_DV_TEE    4
+#define GREB_DV_GET    5
+#define GREB_DV_ADD    6
+#define GREB_DV_SUB    7
+#define GREB_DV_MUL    8
+#define GREB_DV_DIV    9
+#define GREB_DV_MIN    10
+#define GREB_DV_MAX    11
+#define GREB_DV_GE     12
+#define GREB_DV_LT     13
+#define GREB_DV_NEG    14
+#define GREB_DV_ABS    15
+#define GREB_DV_SQRT   16
+#define GREB_DV_EXP    17
+#define GREB_DV_LOG    18
+#define GREB_DV_ATAN   19
+#define GREB_DV_SELECT 20
+typedef struct greb_derive_ins {
+  int32_t op;  /* GREB_DV_* */
+  int32_t arg; /* STATE, TERM, FIELD, TEE, GET: the index; else ignored */
+  float value; /* CONST: the value; else ignored */
+} greb_derive_ins;
+typedef struct greb_derive greb_derive;
+/* A plan: ins holds the programs of the outputs one after the other, n_ins[n_out] their lengths; fields may be NULL with
+ * n_fields = 0.  Host work only, validated without touching a device.  GREB_E_INVALID with a message that names output
+ * and instruction (greb_engine_last_error(NULL)): an unknown op, an index out of range, stack underflow, anything but
+ * exactly one value left at the end, a stack deeper than GREB_DERIVE_MAX_STACK, a GET of a local not set earlier in the
+ * same output, a CONST that is not finite, a count outside its limit, a field value that is not finite (the message names
+ * field, row and column), FIELD with n_fields = 0, a grid greb_diag_create does not take. */
+int greb_derive_create(int nx, int ny, const greb_derive_ins* ins, const int32_t* n_ins, int n_out, const float* fields,
+                       int n_fields, greb_derive** out);
+int greb_derive_destroy(greb_derive* v); /* waits for the device before it frees the program's copy */
+int greb_derive_uses_budget(const greb_derive* v); /* 1: some output names a TERM; 0: none (or v is NULL) */
+/* One model year on HIP device `device`: state_year_dev [n_members][12][5][ny][nx] and budget_year_dev
+ * [n_members][12][GREB_NBUDGET][ny][nx] (NULL allowed if and only if no output names a TERM) -> out_dev
+ * [n_members][12][n_out][ny][nx]; all 16-byte aligned, out_dev overlapping neither input.  Every input record some output
+ * names is read once, every output written once.  Launches on `stream` (a hipStream_t, may be NULL) and does not
+ * synchronise.  Arguments are checked before any device query; without a device: GREB_E_NOGPU (no CPU path). */
+int greb_derive_apply_dev(greb_derive* v, int device, const float* state_year_dev, const float* budget_year_dev, int n_members,
+                          float* out_dev, void* stream);
+/* The seven reduced runs over the DERIVED records of each year: V = the plan's n_out variables per month.  Shapes,
+ * delivery and device memory are those of the driver of the same name with 5 replaced by V, plus one year of derived
+ * records the engine keeps.  A program without a TERM is integrated by the kernels greb_engine_run_diag, ... launch (no
+ * budget instantiation, budget_runs not counted); one with a TERM as greb_engine_run_budget_diag, ... integrate.  The
+ * stage is enqueued behind the year on the compute stream.  co2_ppm, yearly, the model clock and the state the engine is
+ * left in are those of greb_engine_run over the same years, bit for bit.  GREB_E_INVALID, decided before any device work
+ * and leaving the engine as it was: `v` NULL or of another grid, a plan whose n_vars (gram: n_records / 12) is not V, and
+ * whatever the state driver of the same name rejects. */
+int greb_engine_run_derived_diag(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_diag* d, unsigned what,
+                                 float* regions, float* zonal, float* annual, float* yearly);
+int greb_engine_run_derived_clim(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_clim* c, int n_periods,
+                                 const int32_t* first_year, const int32_t* n_years, float* mean, float* seasons, float* trend,
+                                 float* mean_resp, float* seasons_resp, float* yearly);
+int greb_engine_run_derived_ens(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_ens* s, float* mean,
+                                float* var, float* min, float* max, float* quant, float* yearly);
+int greb_engine_run_derived_lin(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_lin* l, float* coef,
+                                float* rss, float* yearly);
+int greb_engine_run_derived_gram(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_gram* g, double* G,
+                                 float* yearly);
+int greb_engine_run_derived_cross(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_cross* c, int32_t* first,
+                                  int32_t* last, int32_t* stay, int32_t* count, float* peak, int32_t* peak_year, float* fraction,
+                                  float* yearly);
+int greb_engine_run_derived_reg(greb_engine* e, int years, const float* co2_ppm, greb_derive* v, greb_reg* r, float* slope,
+                                float* intercept, float* r2, float* index, float* yearly);
+
 /* ---- per-member forcing: regional and seasonal CO2, insolation tables and scale --------------------
  * Members of one engine may differ in the forcing itself, not only in the CO2 level: CO2 raised in one hemisphere, over
  * land or ocean only or in one half of the year, a changed solar constant, a changed latitudinal or seasonal distribution
