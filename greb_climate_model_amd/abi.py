@@ -14,6 +14,7 @@ F_ROW_STRIPS = 4
 F_NO_PERSISTENT = 8
 F_PERSISTENT = 16
 RUN_DEVICE_OUT = 1
+MAX_CHUNKS, CHUNKS_HALVING, CHUNKS_EQUAL, CHUNKS_QUARTERS = 10, 0, 1, 2  # GREB_MAX_CHUNKS, GREB_CHUNKS_* of include/greb_engine.h
 D_REGIONS, D_ZONAL, D_ANNUAL = 1, 2, 4  # reduced-output products, GREB_D_* of include/greb_engine.h
 D_MAX_REGIONS = 15
 C_MEAN, C_SEASONS, C_TREND, C_RESPONSE = 1, 2, 4, 8  # climatology products, GREB_C_* of include/greb_engine.h

@@ -33,7 +33,8 @@ extern "C" {
 
 #ifdef GREB_TUNING
 // diagnostic builds only (not part of include/greb_engine.h): where the fused member kernel writes its stamps,
-// [n_members][8 waves][8] unsigned long long on the device (tools/stamp_member.py); NULL switches them off
+// [n_members][8 waves][8] unsigned long long on the device, then the item records [n_members][kMaxChunks][8]
+// (tools/stamp_member.py); NULL switches them off
 int greb_tuning_set_stamps(greb_engine* e, unsigned long long* stamps_dev) {
   if (!e) return GREB_E_INVALID;
   e->stamps = stamps_dev;
@@ -135,6 +136,20 @@ int greb_step_variants(unsigned* out, int capacity) {
   if (capacity < 0 || (capacity > 0 && !out)) return fail(nullptr, GREB_E_INVALID, "step_variants: bad argument");
   for (int i = 0; i < kNVariants && i < capacity; ++i) out[i] = kVariants[i];
   return kNVariants;
+}
+
+int greb_member_chunk_table(int schedule, int nsteps, int* end, int capacity) {
+  if (schedule < 0 || schedule >= kNChunkSchedules || nsteps < 1 || capacity < 0 || (capacity > 0 && !end))
+    return fail(nullptr, GREB_E_INVALID, "member_chunk_table: bad argument");
+  const ChunkTable t = chunk_table(schedule, nsteps);
+  for (int c = 0; c < t.n && c < capacity; ++c) end[c] = t.end[c];
+  return t.n;
+}
+
+long long greb_member_queue_capacity(int members, int schedule, int nsteps) {
+  if (schedule < 0 || schedule >= kNChunkSchedules || nsteps < 1 || members < 1 || members > kMaxDealtMembers)
+    return fail(nullptr, GREB_E_INVALID, "member_queue_capacity: bad argument");
+  return (long long)members * chunk_table(schedule, nsteps).n;
 }
 
 int greb_member_deal_cover(int strict, int* counts) {

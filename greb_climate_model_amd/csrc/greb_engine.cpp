@@ -110,7 +110,7 @@ static MemberArgs base_args(greb_engine* e) {
   a.xsw = e->xsw_uniform ? e->xsw : 0u;
   a.xsw_m = e->xsw_uniform ? nullptr : e->xsw_dev;
   a.co2_flux_m = e->co2_flux_dev;
-  a.stamps = e->stamps;
+  a.stamps = e->stamps; a.stamp_members = e->nm;
   a.dbg = tuning_int("GREB_DEBUG_PHYS", 0);
   // no transport at all where EVERY member is without circulation: the tracers come back unchanged.  A member without
   // it beside members with it does zero sub-steps of its own (fused kernel) or drops its increments (point physics).
@@ -236,6 +236,19 @@ static int ledger_grant(greb_engine* e, int device_slots) {
 
 // after the stream has been synchronised: did a one-launch circulation call give up waiting?
 static int check_circulation(greb_engine* e) {
+  if (e->deal_status) { // the fused engine's dealt launches: did a workgroup give up waiting for an item?
+    unsigned d[4] = {0, 0, 0, 0};
+    if (hipMemcpy(d, e->deal_status, sizeof(d), hipMemcpyDeviceToHost) != hipSuccess)
+      return fail(e, GREB_E_STATE, "dealt member launch: status word unreadable");
+    if (d[0]) {
+      char buf[256];
+      std::snprintf(buf, sizeof(buf),
+                    "dealt member launch given up: a workgroup waited more than %.1f s for item %u of its queue; results are "
+                    "invalid, recreate the engine (greb_engine_set_dealing(e, -1, 0, 0) runs it without the queue)",
+                    kCircSpinTicks / 1e8, d[1]);
+      return fail(e, GREB_E_STATE, buf);
+    }
+  }
   for (auto& kv : e->plans) {
     unsigned d[5] = {0, 0, 0, 0, 0};
     const int rc = circ_rows_status(kv.second.circ, d);
@@ -275,13 +288,51 @@ static int make_strip_plan(greb_engine* e, int nrun, StripPlan& p) {
   return 0;
 }
 
+// The fused engine's year for `nrun` members as a dealt launch, where it is one (greb_member.hip: "The deal of member-year
+// chunks"): more members than workgroups, or dealing forced.  The queue and its image are made the first time a year of
+// that many members and chunks runs; every launch starts from a copy of the image, enqueued in front of it.
+static int deal_prepare(greb_engine* e, MemberArgs& a, int nrun, int* workgroups) {
+  if (e->deal_workgroups < 0 || a.nsteps < 1 || nrun > kMaxDealtMembers) return 0;
+  if (e->cus <= 0) HIP_TRY(e, hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, e->device));
+  const int w = e->deal_workgroups > 0 ? e->deal_workgroups : e->cus;
+  if (w < 1 || (nrun <= w && !e->deal_force)) return 0;
+  const ChunkTable t = chunk_table(e->deal_schedule, a.nsteps);
+  const size_t capacity = (size_t)nrun * (size_t)t.n, words = kQItems + capacity;
+  if (!e->deal_status) {
+    DevBuf<unsigned> st;
+    HIP_TRY(e, st.alloc(4));
+    HIP_TRY(e, hipMemset(st.get(), 0, 4 * sizeof(unsigned)));
+    e->deal_status = st.release();
+  }
+  if (e->deal_members != nrun || e->deal_chunks != t.n) {
+    HIP_TRY(e, hipStreamSynchronize(e->stream)); // (a launch in flight reads the queue this one replaces)
+    std::vector<unsigned> image(words, 0u);
+    image[kQTail] = (unsigned)nrun;
+    for (int m = 0; m < nrun; ++m) image[kQItems + (size_t)m] = ((unsigned)m << 4) + 1u;
+    DevBuf<unsigned> q, img;
+    HIP_TRY(e, q.alloc(words));
+    HIP_TRY(e, img.upload(image.data(), words));
+    adopt(e->deal_queue, q);
+    adopt(e->deal_image, img);
+    e->deal_members = nrun; e->deal_chunks = t.n;
+  }
+  HIP_TRY(e, hipMemcpyAsync(e->deal_queue, e->deal_image, words * sizeof(unsigned), hipMemcpyDeviceToDevice, e->stream));
+  a.queue = e->deal_queue; a.q_status = e->deal_status; a.q_capacity = (unsigned)capacity; a.chunks = t;
+  *workgroups = w;
+  ++e->deal_launches;
+  return 0;
+}
+
 // One model year (730 steps) for the first `nrun` members, `a` describing that year.
 //   fused layout : one launch of the member kernel
 //   other grids  : 24 fused band sub-steps + 1 point-physics launch per model step
 //   row strips   : the 24 sub-steps in one launch or one launch each (StripPlan) + 1 point-physics launch per model step
 int greb::host::run_year(greb_engine* e, const MemberArgs& a, int nrun) {
   if (e->fused) {
-    HIP_TRY(e, launch_member_kernel(a, nrun, e->strict, e->stream));
+    MemberArgs b = a;
+    int workgroups = 0;
+    if (int rc = deal_prepare(e, b, nrun, &workgroups)) return rc;
+    HIP_TRY(e, launch_member_kernel(b, nrun, e->strict, e->stream, workgroups));
     return 0;
   }
   const size_t np = (size_t)e->np;
@@ -642,7 +693,8 @@ int greb_engine_destroy(greb_engine* e) {
                   e->cldclim, e->swetclim, e->toclim, e->z_ocean, e->wz_air, e->wz_vapor, e->state, e->acc,
                   e->corr, e->corr_index, e->tab_index, e->tabs, e->phys, e->co2_dev, e->monthly_dev, e->yearly_dev,
                   e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev, e->diag_out, e->diag_reg, e->clim_out, e->ens_out, e->lin_out, e->gram_out, e->derive_out, e->bsum, e->budget_dev,
-                  e->f_space, e->f_season, e->f_solar, e->force_dev, e->bsets_dev, e->bset_dev, e->neutral_force_dev};
+                  e->f_space, e->f_season, e->f_solar, e->force_dev, e->bsets_dev, e->bset_dev, e->neutral_force_dev,
+                  e->deal_queue, e->deal_image, e->deal_status};
   for (void* q : ptrs) if (q) (void)hipFree(q);
   for (const auto& b : e->bound) if (b.frec) (void)hipFree(b.frec);
   for (size_t k = 1; k < e->bound.size(); ++k)
@@ -729,6 +781,11 @@ const char* greb_engine_describe(greb_engine* e) {
                   family(scenario));
     s += buf;
   }
+  if (e->fused) { // the deal of member-year chunks: the setting, and how many launches so far went through the queue
+    std::snprintf(buf, sizeof(buf), ", \"dealing\": {\"workgroups\": %d, \"schedule\": %d, \"forced\": %s, \"dealt_launches\": %lld}",
+                  e->deal_workgroups, e->deal_schedule, e->deal_force ? "true" : "false", e->deal_launches);
+    s += buf;
+  }
   if (e->call != greb_engine::kCallNever) {
     std::snprintf(buf, sizeof(buf), ", \"wavefront_slots_granted\": %d, \"circulation\": [", e->slots_granted);
     s += buf;
@@ -774,6 +831,12 @@ int greb_engine_set_corrections(greb_engine* e, int member, const float* corr, c
     if (corr && (ci == (size_t)m || m == m0)) HIP_TRY(e, hipMemcpy(e->corr + ci * n, corr, n * sizeof(float), hipMemcpyHostToDevice));
     if (state5) HIP_TRY(e, hipMemcpy(e->state + (size_t)m * s5, state5, s5 * sizeof(float), hipMemcpyHostToDevice));
   }
+  return 0;
+}
+
+int greb_engine_set_dealing(greb_engine* e, int workgroups, int schedule, int force) {
+  if (!e || schedule < 0 || schedule >= kNChunkSchedules) return fail(e, GREB_E_INVALID, "set_dealing: bad argument");
+  e->deal_workgroups = workgroups; e->deal_schedule = schedule; e->deal_force = force != 0;
   return 0;
 }
 

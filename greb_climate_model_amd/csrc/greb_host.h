@@ -98,6 +98,15 @@ struct greb_engine {
   // model clock
   long long it_flux = 0; // steps done in the flux phase
   long long it_scnr = 0; // steps done in the scenario
+  // the deal of member-year chunks (fused engine; greb_member.hip, greb_engine_set_dealing)
+  int deal_workgroups = 0;              // > 0: workgroups of a dealt launch; 0: the device's compute units; < 0: no dealing
+  int deal_schedule = greb::kChunksHalving;
+  bool deal_force = false;              // deal also where the members do not outnumber the workgroups
+  unsigned* deal_queue = nullptr;       // kQItems + members x chunks words, re-made from deal_image before every dealt launch
+  unsigned* deal_image = nullptr;       // head 0, tail = members, chunk 0 of every member, empty slots
+  unsigned* deal_status = nullptr;      // [4], sticky: a workgroup gave up waiting for an item (finish_years)
+  int deal_members = 0, deal_chunks = 0; // what queue and image were made for
+  long long deal_launches = 0;          // launches that went through the queue so far (describe)
   unsigned long long* stamps = nullptr; // -DGREB_TUNING builds only: device buffer for the member kernel's stamps
   std::string last_error;
 };

@@ -73,6 +73,32 @@ static_assert(forcing_record_offset(0, kFrFields - 1, 0) * sizeof(float) <= 4095
               "a field's offset must fit the immediate of a global load");
 static_assert(kFrBytes < (1ull << 31), "offsets into a record are 32-bit");
 
+// The chunks a dealt launch of the fused member kernel cuts every member's steps into (greb_member.hip): chunk c is the
+// steps [end[c - 1], end[c]) of the launch, end[-1] = 0.  Host-built, the same for every member.
+constexpr int kMaxChunks = 10;
+struct ChunkTable { int n; int end[kMaxChunks]; };
+// The schedules: kChunksHalving -- each chunk half of what is left, so that the LAST one, which sets what the launch's
+// tail can still cost, is short while the chunks, each of which pays the kernel's prologue, stay few: 365 / 183 / 91 / 46 /
+// 23 / 12 / 10 of a year's 730 steps (other step counts in proportion); kChunksEqual -- ten equal chunks; kChunksQuarters
+// -- the halving schedule with its first half cut in two: 183 / 182 / 183 / 91 / 46 / 23 / 12 / 10, so that the members of
+// an incomplete last round start after a quarter of a year, not after half of one.
+enum { kChunksHalving = 0, kChunksEqual = 1, kChunksQuarters = 2, kNChunkSchedules };
+inline ChunkTable chunk_table(int schedule, int nsteps) {
+  constexpr int kHalving[7] = {365, 548, 639, 685, 708, 720, 730};
+  constexpr int kQuarters[8] = {183, 365, 548, 639, 685, 708, 720, 730};
+  ChunkTable t{};
+  const int n = schedule == kChunksEqual ? kMaxChunks : (schedule == kChunksQuarters ? 8 : 7);
+  for (int c = 0; c < n; ++c) {
+    const long long e = schedule == kChunksEqual ? (long long)nsteps * (c + 1) / n
+                                                 : (long long)nsteps * (schedule == kChunksQuarters ? kQuarters[c] : kHalving[c]) / 730;
+    if (e > (t.n ? t.end[t.n - 1] : 0)) t.end[t.n++] = (int)e; // (a launch of a few steps: no empty chunks)
+  }
+  return t;
+}
+// the queue's words in front of its items, and an item: (member << 4 | chunk) + 1, 0 = not pushed yet
+enum { kQHead = 0, kQTail = 1, kQItems = 4 };
+constexpr int kMaxDealtMembers = 1 << 27;
+
 // Everything the fused member kernel needs (passed by value as a kernel argument).
 struct MemberArgs {
   int nx, ny, np;
@@ -127,6 +153,13 @@ struct MemberArgs {
   // greb_physics_step.h, member_boundary).  Appended likewise.
   const BoundarySet* bsets;     // [1 + sets made]; entry 0 holds the thirteen pointers above
   const int* bset_m;            // [nm] each member's set; null: every member of the launch is on the engine's own data
+  // the ready queue of a dealt launch (greb_member.hip: "The deal of member-year chunks"; null: workgroup b integrates
+  // member b for the whole launch).  Appended likewise.
+  unsigned* queue;              // kQ* words, then `q_capacity` item words
+  unsigned* q_status;           // [4], sticky: [0] != 0: a workgroup gave up waiting for an item, [1] the slot it waited for
+  unsigned q_capacity;          // members x chunks: the ring never wraps within a launch
+  ChunkTable chunks;            // the steps of the launch cut into chunks, the same for every member
+  int stamp_members;            // -DGREB_TUNING builds only: members the stamp buffer was made for (the item records follow theirs)
 };
 
 // The set table on the device: kSetTableEntries BoundarySet, then as many forcing-record pointers (entry 0: the engine's
@@ -199,7 +232,7 @@ void member_deal_cover(bool strict, int* counts);
 // returns the number of records there are
 int member_lds_table(bool strict, int* out, int capacity);
 void member_lds_map(int* words8);
-hipError_t launch_member_kernel(const MemberArgs& a, int n_members, bool strict, hipStream_t s);
+hipError_t launch_member_kernel(const MemberArgs& a, int n_members, bool strict, hipStream_t s, int workgroups = 0);
 // the forcing record (kFrBytes at `rec`) of the set whose thirteen device arrays `b` names (greb_member.hip)
 hipError_t launch_pack_forcing(const BoundarySet& b, float* rec, hipStream_t s);
 hipError_t launch_circulation_g96(const float* X, const float* wz, const float* u, const float* v, float* dX,

@@ -1,8 +1,9 @@
 // greb_member.hip -- the fused GREB member engine for MI355X (gfx950, wave64), 96x48 grid.
 //
-// One 512-thread workgroup integrates one ensemble member for a whole launch (one model year):
-// point physics, 2 x 24 circulation sub-steps, Euler update, sea ice, monthly/annual accumulation
-// (src/greb.f90:239-364, 528-553) without leaving the CU.
+// One 512-thread workgroup integrates one member-year CHUNK: a run of consecutive model steps of one ensemble member --
+// the whole launch (one model year) where there are no more members than workgroups, else an item of the launch's ready
+// queue (see "The deal of member-year chunks") -- point physics, 2 x 24 circulation sub-steps, Euler update, sea ice,
+// monthly/annual accumulation (src/greb.f90:239-364, 528-553) without leaving the CU.
 //
 // Residency
 //   LDS (157 KB)  X[2 buffers][48][96][{Tair,q}]  the two transported tracers, INTERLEAVED and
@@ -897,18 +898,23 @@ template <bool STRICT>
 struct Circ {
   __device__ __forceinline__ void init(lfloat* lds, const float* wz_air, const float* wz_vapor,
                                        const RowTables* __restrict__ tab) {
+    // The thread id as a value of this call: the member kernel runs its prologue once per (member, chunk) item, and
+    // addresses made from threadIdx.x itself are made once in front of that loop and then held -- spilled -- across the
+    // whole body.
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
     // guard rows of X[0], X[1], W: zero, never written again
-    for (int i = threadIdx.x; i < 6 * RS; i += kThreads) {
+    for (int i = tid; i < 6 * RS; i += kThreads) {
       const int g = i / RS, o = i % RS; // buffer g >> 1, lower / upper guard g & 1
       lds[(g >> 1) * XB + (g & 1) * (NY + 1) * RS + o] = 0.f;
     }
-    stage_row_consts(lds + kOffRowK, *tab, 0, NY);
+    stage_row_consts(lds + kOffRowK, *tab, 0, NY, tid);
     // FAST: the diffusion constant as the bulk tasks use it, dif_cc/20, in the row's spare word -- the same single fp32
     // multiply the tasks did (each thread rescales the rows it has just staged: LDS operations of a thread stay in order)
     if (!STRICT)
-      for (int k = threadIdx.x; k < NY; k += blockDim.x)
+      for (int k = tid; k < NY; k += blockDim.x)
         lds[kOffRowK + k * kRowKWords + kRowKCsDif] = lds[kOffRowK + k * kRowKWords] * 0.05f;
-    for (int i = threadIdx.x; i < NP / 4; i += kThreads)
+    for (int i = tid; i < NP / 4; i += kThreads)
       st8(lds + kOffW + (i / NQ) * RS, i % NQ, zip(ld4(wz_air + 4 * i), ld4(wz_vapor + 4 * i)));
   }
 
@@ -1040,12 +1046,114 @@ hipError_t launch_circulation_g96(const float* X, const float* wz, const float* 
 // kVBound: the thirteen boundary fields are those of the member's set.  Only the set index, one scalar register, lives
 // across the sub-steps: the pointers are fetched from the set table where they are used (greb_physics_step.h:
 // member_boundary), as the other variants fetch theirs from the kernel arguments.
+//
+// The deal of member-year chunks.  A launch of more members than workgroups (MemberArgs::queue set) cuts every member's
+// steps into the chunks of MemberArgs::chunks and deals (member, chunk) items to the workgroups from a ready queue: a CU
+// that is done early -- the CUs' clocks differ by several per cent -- takes the next item instead of idling until the
+// slowest CU has finished its last whole member, and an ensemble that is no multiple of the CU count does not pay a whole
+// round for its remainder.  Everything a member carries from step to step is in global memory after every step (state,
+// acc, corr, the budget sums) and the step's clock follows from it0 + s, so a chunk is the launch's body run for the steps
+// [s0, s1) of member m: prologue (Circ::init, the tracers from `state`), step loop, nothing else.
+// The queue: `q_capacity` = members x chunks item words behind a head and a tail counter, re-made on the stream before
+// every launch with chunk 0 of every member in the first `members` slots.  A workgroup takes the next INDEX (atomic add on
+// head), leaves when that is beyond the capacity, else waits until the slot is filled; having run the chunk it pushes the
+// member's next one (atomic add on tail, store of the item).  A slot below the capacity is always filled in the end: by
+// the image, or by a workgroup that holds an item and is therefore running -- nothing depends on which workgroups are
+// resident or in what order they start.  The wait is bounded all the same (kCircSpinTicks); a workgroup that gives up sets
+// q_status, which ends every other wait, and the host reports it (greb_engine.cpp: finish_years).
+// A member's next chunk usually runs on another XCD, whose L2 may hold lines of that member from an earlier chunk: the
+// push is a release at agent scope behind a workgroup barrier, the pop an acquire at agent scope in front of the first
+// load of the member's data.  Only scalars (m, s0, s1) depend on the item.
+constexpr int kLdsItemWord = kLdsFloats; // behind the map above
+constexpr size_t kLdsBytesLaunch = kLdsBytes + 16;
+static_assert(kLdsBytesLaunch <= 160 * 1024, "the item word must fit the CU's LDS beside the member");
+
+__device__ __forceinline__ int item_member(unsigned item) { return (int)((item - 1u) >> 4); }
+__device__ __forceinline__ int item_chunk(unsigned item) { return (int)((item - 1u) & 15u); }
+__device__ __forceinline__ __attribute__((address_space(3))) unsigned* item_words(lfloat* lds) {
+  return (__attribute__((address_space(3))) unsigned*)(lds + kLdsItemWord);
+}
+// word i of the two, block-uniform, read anew wherever it is used
+__device__ __forceinline__ unsigned item_word(lfloat* lds, int i) {
+  return (unsigned)__builtin_amdgcn_readfirstlane((int)*(volatile __attribute__((address_space(3))) unsigned*)(item_words(lds) + i));
+}
+// the next item of this workgroup, in every thread (block-uniform); 0: none -- the queue is drained, or the wait was given up
+__device__ __forceinline__ unsigned pop_item(const MemberArgs& a, lfloat* lds) {
+  __attribute__((address_space(3))) unsigned* word = item_words(lds) + 2; // (a word of its own: see member_kernel on the other two)
+  if (threadIdx.x == 0) {
+    unsigned item = 0u;
+    const unsigned idx = __hip_atomic_fetch_add(a.queue + kQHead, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (idx < a.q_capacity) {
+      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+      for (;;) {
+        item = __hip_atomic_load(a.queue + kQItems + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (item != 0u) break;
+        if (__hip_atomic_load(a.q_status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break; // somebody gave up
+        if (__builtin_amdgcn_s_memrealtime() - t0 > kCircSpinTicks) {
+          __hip_atomic_store(a.q_status + 1, idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(a.q_status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          break;
+        }
+        __builtin_amdgcn_s_sleep(64); // ~4 000 cycles between two polls
+      }
+    }
+    *word = item;
+  }
+  __syncthreads(); // (the word is not written again before every thread has passed the barrier behind the prologue)
+  const unsigned item = (unsigned)__builtin_amdgcn_readfirstlane((int)*word);
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  return item;
+}
+
+// after the last step of a chunk: hand the member on
+__device__ __forceinline__ void push_next(const MemberArgs& a, unsigned item) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); // every wave's stores of the chunk ...
+  __syncthreads();
+  if (threadIdx.x == 0 && item_chunk(item) + 1 < a.chunks.n) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); // ... in front of the item
+    const unsigned slot = __hip_atomic_fetch_add(a.queue + kQTail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (slot < a.q_capacity) // (item + 1: the same member's next chunk)
+      __hip_atomic_store(a.queue + kQItems + slot, item + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 template <bool STRICT, unsigned V>
-__global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
+__global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a_launch) {
   constexpr bool FLUX = V & kVFlux, EXP = V & kVExp, BUDGET = V & kVBudget, FORCE = V & kVForce, BOUND = V & kVBound;
   extern __shared__ __align__(16) float lds_raw[];
   lfloat* lds = (lfloat*)lds_raw;
-  const int m = blockIdx.x, tid = threadIdx.x;
+  const int tid = threadIdx.x;
+  const bool dealt = a_launch.queue != nullptr;
+#pragma unroll 1
+  for (;;) { // one (member, chunk) item per trip; a launch that is not dealt makes one trip
+  // The kernel arguments of a trip, through a pointer that is opaque to the compiler: read through the parameter itself,
+  // every argument the body uses is loaded once in front of this loop and held in a scalar register for the whole launch
+  // (they are loop-invariant), across the sub-steps too -- 50 more scalar registers spilled and, in their wake, scratch.
+  const __attribute__((address_space(4))) MemberArgs* a_trip =
+      (const __attribute__((address_space(4))) MemberArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(a_trip));
+  const MemberArgs& a = *(const MemberArgs*)a_trip;
+  // The item and the step its chunk ends at live in two LDS words: the step loop reads its bound there once per model step,
+  // and what follows the loop reads the item again, so that neither holds a scalar register across the sub-steps.
+  int m = blockIdx.x, s0 = 0;
+  {
+    int s1 = a.nsteps;
+    unsigned item = ((unsigned)m << 4) + 1u;
+    if (dealt) {
+      item = pop_item(a, lds);
+      if (item == 0u) break;
+      m = item_member(item);
+#pragma unroll
+      for (int c = 0; c < kMaxChunks; ++c) { // (constant indices: the kernel arguments stay where they are)
+        if (c + 1 == item_chunk(item)) s0 = a.chunks.end[c];
+        if (c == item_chunk(item)) s1 = a.chunks.end[c];
+      }
+    }
+    if (tid == 0) { item_words(lds)[0] = item; item_words(lds)[1] = (unsigned)s1; } // read behind the prologue's barrier
+  }
+#ifdef GREB_TUNING
+  const unsigned long long tl_r0 = a.stamps ? __builtin_amdgcn_s_memrealtime() : 0, tl_c0 = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
+#endif
   float* state = a.state + (size_t)m * 5 * NP;
   float* acc = a.acc + (size_t)m * 6 * NP;
   float* corr = a.corr + (size_t)a.corr_index[m] * 3 * kNT * NP;
@@ -1062,8 +1170,12 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
     const BoundPtr B = member_boundary<BOUND>(a, bset);
     circ.init(lds, BOUND ? (const float*)B->wz_air : a.wz_air, BOUND ? (const float*)B->wz_vapor : a.wz_vapor, tab);
   }
-  for (int i = tid; i < NP / 4; i += kThreads)
-    st8(lds + kOffX + (i / NQ) * RS, i % NQ, zip(ld4(state + NP + 4 * i), ld4(state + 3 * NP + 4 * i))); // (Tair, q)
+  {
+    int t = tid;
+    asm volatile("" : "+v"(t)); // (as in Circ::init)
+    for (int i = t; i < NP / 4; i += kThreads)
+      st8(lds + kOffX + (i / NQ) * RS, i % NQ, zip(ld4(state + NP + 4 * i), ld4(state + 3 * NP + 4 * i))); // (Tair, q)
+  }
   int cur = 0;
   const unsigned xsw = EXP ? member_switches(a, m) : 0u;
   const int nsub = (EXP && (xsw & kXNoCirc)) ? 0 : a.nsub;
@@ -1087,7 +1199,7 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
 #endif
 
 #pragma unroll 1
-  for (int s = 0; s < a.nsteps; ++s) {
+  for (int s = s0; s < (int)item_word(lds, 1); ++s) {
     const long long it = a.it0 + s;
     const StepClock ck = step_clock<FLUX>(a, it, NP);
     const int ityr = ck.ityr, yr_rel = ck.yr_rel;
@@ -1205,10 +1317,25 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a) {
   if (stamp && (tid & 63) == 0) {
     unsigned long long* o = a.stamps + ((size_t)m * (kThreads / 64) + (tid >> 6)) * 8;
     o[0] = __builtin_amdgcn_s_memtime() - st_c0; o[1] = __builtin_amdgcn_s_memrealtime() - st_r0;
-    o[2] = st_wind; o[3] = st_circ; o[4] = st_busy; o[5] = st_phys; o[6] = (unsigned long long)a.nsteps; o[7] = (unsigned long long)nsub;
+    o[2] = st_wind; o[3] = st_circ; o[4] = st_busy; o[5] = st_phys; o[6] = (unsigned long long)((int)item_word(lds, 1) - s0); o[7] = (unsigned long long)nsub;
+  }
+  // ... and the item's lifetime (tools/stamp_member.py tail): behind the wave records, per (member, chunk), start and end in
+  // s_memrealtime ticks, the XCC and hardware ids, shader cycles of the whole item and of its prologue, its steps
+  if (stamp && tid == 0) {
+    unsigned hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    const int chunk = item_chunk(item_word(lds, 0));
+    unsigned long long* o = a.stamps + (size_t)a.stamp_members * (kThreads / 64) * 8 + ((size_t)m * kMaxChunks + chunk) * 8;
+    o[0] = tl_r0; o[1] = __builtin_amdgcn_s_memrealtime(); o[2] = ((unsigned long long)xcc << 32) | hw;
+    o[3] = __builtin_amdgcn_s_memtime() - tl_c0; o[4] = st_c0 - tl_c0; o[5] = (unsigned long long)s0; o[6] = (unsigned long long)item_word(lds, 1);
+    o[7] = (unsigned long long)blockIdx.x;
   }
 #endif
   // all five state fields were written back every step
+  if (!dealt) break;
+  push_next(a, item_word(lds, 0)); // (behind the step loop's closing barrier: every thread's stores of this chunk are issued)
+  }
 }
 
 // The forcing record of one boundary set (greb_kernels.h): one thread per (step, point).  The wind-speed term is
@@ -1244,17 +1371,21 @@ hipError_t launch_pack_forcing(const BoundarySet& b, float* rec, hipStream_t s) 
 template <bool STRICT, unsigned V>
 struct MemberFamily { static auto kernel() { return &member_kernel<STRICT, V>; } };
 
-hipError_t launch_member_kernel(const MemberArgs& a, int n_members, bool strict, hipStream_t s) {
+// workgroups: those of a dealt launch (a.queue set, made for n_members members by the caller); ignored otherwise
+hipError_t launch_member_kernel(const MemberArgs& a, int n_members, bool strict, hipStream_t s, int workgroups) {
   if (a.nx != NX || a.ny != NY) return hipErrorInvalidValue;
+  if (a.queue && (workgroups < 1 || !a.q_status || a.chunks.n < 1 || a.chunks.n > kMaxChunks || n_members > kMaxDealtMembers ||
+                  a.q_capacity != (unsigned)n_members * (unsigned)a.chunks.n || a.chunks.end[a.chunks.n - 1] != a.nsteps))
+    return hipErrorInvalidValue;
   if (!strict && !a.bsets) return hipErrorInvalidValue; // the FAST kernels read their forcing record behind the set table
   unsigned v;
   if (hipError_t e = select_variant(a, &v); e != hipSuccess) return e;
   const auto kern = pick_variant<MemberFamily>(strict, v);
   if (!kern) return hipErrorInvalidValue;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytesLaunch);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(n_members), dim3(kThreads), kLdsBytes, s, a);
+  hipLaunchKernelGGL(kern, dim3(a.queue ? workgroups : n_members), dim3(kThreads), kLdsBytesLaunch, s, a);
   return hipGetLastError();
 }
 

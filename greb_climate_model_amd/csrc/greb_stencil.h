@@ -42,8 +42,9 @@ struct RowK {
 // s_waitcnt vmcnt is in-order, so one table load would wait for every prefetch ahead of it.
 constexpr int kRowKWords = 8;
 // rows k_begin .. k_end-1 to dst[0 ..]
-__device__ __forceinline__ void stage_row_consts(lfloat* dst, const RowTables& tab, int k_begin, int k_end) {
-  for (int k = k_begin + threadIdx.x; k < k_end; k += blockDim.x) {
+// (tid: the caller's own copy of threadIdx.x, see Circ::init)
+__device__ __forceinline__ void stage_row_consts(lfloat* dst, const RowTables& tab, int k_begin, int k_end, int tid = threadIdx.x) {
+  for (int k = k_begin + tid; k < k_end; k += blockDim.x) {
     const int sub = tab.subcycled[k];
     lfloat* d = dst + (k - k_begin) * kRowKWords;
     d[0] = sub ? tab.dif_ccx2[k] : tab.dif_ccx[k];

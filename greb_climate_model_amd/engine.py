@@ -82,7 +82,8 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_engine_run_budget_reg",
            "greb_derive_create", "greb_derive_destroy", "greb_derive_uses_budget", "greb_derive_apply_dev",
            "greb_engine_run_derived_diag", "greb_engine_run_derived_clim", "greb_engine_run_derived_ens", "greb_engine_run_derived_lin",
-           "greb_engine_run_derived_gram", "greb_engine_run_derived_cross", "greb_engine_run_derived_reg"]
+           "greb_engine_run_derived_gram", "greb_engine_run_derived_cross", "greb_engine_run_derived_reg",
+           "greb_engine_set_dealing", "greb_member_chunk_table", "greb_member_queue_capacity"]
 
 
 def _check(rc: int, h=None):
@@ -210,6 +211,12 @@ class Engine:
                 L.greb_engine_destroy(self.h)
                 self.h = None
             raise GrebError(rc, msg)
+
+    def set_dealing(self, workgroups: int = 0, schedule: int = abi.CHUNKS_HALVING, force: bool = False) -> None:
+        """greb_engine_set_dealing (fused 96x48 engine): launches of more members than `workgroups` (0: the device's compute
+        units) deal (member, chunk) items to that many workgroups from a ready queue; workgroups < 0 switches dealing off;
+        force deals also where the members do not outnumber the workgroups.  Results do not depend on it."""
+        _check(lib().greb_engine_set_dealing(self.h, int(workgroups), int(schedule), int(bool(force))), self.h)
 
     def describe(self) -> dict:
         """greb_engine_describe: grid, members, arithmetic, which circulation form runs (and the trial's timings)."""
@@ -585,6 +592,26 @@ def substep_launch_order(params, nx, ny, n_members, kappa=None):
         ptr = [a.ctypes.data_as(C.POINTER(C.c_int)) for a in out]
         assert f(C.byref(params), nx, ny, n_members, kp, *ptr, n) == n
     return out
+
+
+def member_chunk_table(schedule: int = abi.CHUNKS_HALVING, nsteps: int = abi.NSTEP_YR) -> list[int]:
+    """Host only: the chunks a dealt launch of the fused member kernel cuts `nsteps` steps into, as the index one past each
+    chunk's last step (include/greb_engine.h: greb_member_chunk_table)."""
+    end = (C.c_int * abi.MAX_CHUNKS)()
+    n = lib().greb_member_chunk_table(int(schedule), int(nsteps), end, abi.MAX_CHUNKS)
+    if n < 0:
+        _check(n)
+    return [int(end[i]) for i in range(n)]
+
+
+def member_queue_capacity(members: int, schedule: int = abi.CHUNKS_HALVING, nsteps: int = abi.NSTEP_YR) -> int:
+    """Host only: the item words of the ready queue of such a launch of `members` members (greb_member_queue_capacity)."""
+    f = lib().greb_member_queue_capacity
+    f.restype = C.c_longlong
+    n = int(f(int(members), int(schedule), int(nsteps)))
+    if n < 0:
+        _check(n)
+    return n
 
 
 def member_deal_cover(strict=False):

@@ -959,6 +959,29 @@ int greb_member_lds_table(int strict, int* records, int capacity);
  * and where the last ends (the kernel's LDS size).  Returns 0, < 0 on a bad argument. */
 int greb_member_lds_map(int* words8);
 
+/* ---- the deal of member-year chunks (fused 96x48 member kernel) --------------------------------------
+ * A launch of more members than workgroups cuts every member's steps into chunks and deals (member, chunk) items to the
+ * workgroups from a ready queue on the device (greb_member.hip): a compute unit that is done early takes the next item
+ * instead of idling until the slowest one has finished a whole member-year, and an ensemble that is no multiple of the
+ * compute units does not pay a whole round for the remainder.  The results do not depend on it, bit for bit.
+ * greb_engine_set_dealing: workgroups > 0: that many; 0: the device's compute units (the default); < 0: no dealing --
+ * workgroup b integrates member b for the whole launch, as every launch of no more members than workgroups does anyway
+ * unless force != 0 (tests: the queue with a handful of members).  schedule: GREB_CHUNKS_*.  Takes effect with the next
+ * year launched.
+ * greb_member_chunk_table (host only, no GPU call): the chunks `nsteps` steps of a launch are cut into, as the index one
+ * past each chunk's last step (0-based steps; end[n - 1] == nsteps); at most `capacity` written; returns their number, at
+ * most GREB_MAX_CHUNKS, or < 0.  greb_member_queue_capacity: the item words of the queue of such a launch of `members`
+ * members = members x chunks, or < 0.
+ * A workgroup that waits more than a second for an item gives the launch up; the call that waits for the year then
+ * returns GREB_E_STATE. */
+#define GREB_MAX_CHUNKS 10
+#define GREB_CHUNKS_HALVING 0 /* 365 / 183 / 91 / 46 / 23 / 12 / 10 steps of a year's 730 */
+#define GREB_CHUNKS_EQUAL   1 /* ten equal chunks */
+#define GREB_CHUNKS_QUARTERS 2 /* 183 / 182 / 183 / 91 / 46 / 23 / 12 / 10: the halving schedule, its first half cut in two */
+int greb_engine_set_dealing(greb_engine* e, int workgroups, int schedule, int force);
+int greb_member_chunk_table(int schedule, int nsteps, int* end, int capacity);
+long long greb_member_queue_capacity(int members, int schedule, int nsteps);
+
 /* ---- forcing records (diagnostic) -------------------------------------------------------------------
  * The FAST fused 96x48 member kernel reads the boundary data of the point physics from one packed, read-only record per
  * boundary set, made on the device when the set's data is uploaded, in two parts: the static fields [row 0..47][field][96]
