@@ -153,7 +153,7 @@ struct MemberArgs {
   // greb_physics_step.h, member_boundary).  Appended likewise.
   const BoundarySet* bsets;     // [1 + sets made]; entry 0 holds the thirteen pointers above
   const int* bset_m;            // [nm] each member's set; null: every member of the launch is on the engine's own data
-  // the ready queue of a dealt launch (greb_member.hip: "The deal of member-year chunks"; null: workgroup b integrates
+  // the ready queue of a dealt launch (greb_member.hip: "The deal of member-year chunks", greb_member_queue.h; null: workgroup b integrates
   // member b for the whole launch).  Appended likewise.
   unsigned* queue;              // kQ* words, then `q_capacity` item words
   unsigned* q_status;           // [4], sticky: [0] != 0: a workgroup gave up waiting for an item, [1] the slot it waited for

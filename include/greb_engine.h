@@ -940,7 +940,7 @@ int greb_circulation_launch_plan(const greb_params* p, int nx, int ny, int n_mem
                                  int* field, int* k0, int* k1, int* chain, int* dep4, int capacity);
 
 /* Diagnostic, host only (no GPU call): how often one circulation sub-step of the fused 96x48 member kernel computes each
- * 4-longitude quad of each row under the kernel's static work deal (greb_member.hip), FAST (strict = 0) or STRICT:
+ * 4-longitude quad of each row under the kernel's static work deal (greb_member_deal.h), FAST (strict = 0) or STRICT:
  * counts[48 * 24], counts[k * 24 + q].  A complete deal has 1 for rows 1 .. 46 and 0 for the polar rows 0 and 47,
  * which have their own wave(s); the library asserts this when it is compiled, this is the same table for tests.
  * Returns 0, < 0 on a bad argument. */
@@ -961,7 +961,7 @@ int greb_member_lds_map(int* words8);
 
 /* ---- the deal of member-year chunks (fused 96x48 member kernel) --------------------------------------
  * A launch of more members than workgroups cuts every member's steps into chunks and deals (member, chunk) items to the
- * workgroups from a ready queue on the device (greb_member.hip): a compute unit that is done early takes the next item
+ * workgroups from a ready queue on the device (greb_member.hip, greb_member_queue.h): a compute unit that is done early takes the next item
  * instead of idling until the slowest one has finished a whole member-year, and an ensemble that is no multiple of the
  * compute units does not pay a whole round for the remainder.  The results do not depend on it, bit for bit.
  * greb_engine_set_dealing: workgroups > 0: that many; 0: the device's compute units (the default); < 0: no dealing --

@@ -1,4 +1,4 @@
-"""GPU: which lane computes which row-quad in the fused 96x48 member kernel (greb_member.hip: task_rowquad deals the tasks
+"""GPU: which lane computes which row-quad in the fused 96x48 member kernel (greb_member_deal.h: task_rowquad deals the tasks
 to the LDS's lane groups) must not show in the results.  The kernel's own sub-step loop through its batched mirror
 (greb_circulation_batched -> launch_circulation_g96) against the oracle's `circulation`, batch 2, for 1, 3 (an odd count:
 the result ends in the other buffer) and 24 sub-steps (the full call): STRICT bit-exact, FAST within the bound of

@@ -1,5 +1,5 @@
 """GPU: the wind signs the fused 96x48 member kernel keeps as lane masks instead of splitting every staged wind into
-max(u,0) and min(u,0) in every sub-step (greb_pair.h: wind_term; greb_member.hip: make_signs).
+max(u,0) and min(u,0) in every sub-step (greb_pair.h: wind_term; greb_member_bulk.h: make_signs).
 
   * every sign pattern -- positive, negative, +0.0, -0.0 in each of the four positions of a quad, in the first and the
     last quad of a row, in a row of each task family and in rows 1 and 46; all winds zero; all winds of one sign -- through

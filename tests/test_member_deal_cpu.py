@@ -1,4 +1,4 @@
-"""CPU: the fused member kernel's static work deal (greb_member.hip: deal_fast / deal_strict, task_rowquad) computes every
+"""CPU: the fused member kernel's static work deal (greb_member_deal.h: deal_fast / deal_strict, task_rowquad) computes every
 4-longitude quad of rows 1 .. 46 exactly once per sub-step and leaves the polar rows to their own waves.  The library
 proves this when it is compiled (static_assert on deal_is_complete); greb_member_deal_cover hands out the same constexpr
 table -- counted by row-quads from the very enumeration the kernel's lanes use, not by pass indices -- so a deal that

@@ -1,4 +1,4 @@
-"""CPU: the chunk table and the queue size of the fused member kernel's dealt launches (greb_member.hip, greb_kernels.h:
+"""CPU: the chunk table and the queue size of the fused member kernel's dealt launches (greb_member.hip, greb_member_queue.h, greb_kernels.h:
 chunk_table), as the library exports them -- the kernel walks the very table the host builds."""
 import pytest
 

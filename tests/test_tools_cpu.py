@@ -1,5 +1,5 @@
 """Host-side tools: the deal notation of tools/deal_search.py must always describe a complete schedule of the fused
-kernel (greb_member.hip: 3 ST, 3 FT, 1 S1 and 5 F1 passes, each exactly once, nothing on the polar wave), or a variant
+kernel (greb_member_deal.h: 3 ST, 3 FT, 1 S1 and 5 F1 passes, each exactly once, nothing on the polar wave), or a variant
 library would silently skip or double rows."""
 import importlib.util
 import os
@@ -33,7 +33,7 @@ def test_every_candidate_deal_is_a_complete_schedule():
 def test_shipped_deal_matches_a_candidate():
     """The table compiled into the release library is one of the measured candidates (the first of the list)."""
     ds = _load()
-    src = open(os.path.join(ROOT, "greb_climate_model_amd", "csrc", "greb_member.hip")).read()
+    src = open(os.path.join(ROOT, "greb_climate_model_amd", "csrc", "greb_member_deal.h")).read()
     m = re.search(r"#else\s+constexpr Pass t\[8\]\[3\] = \{(.*?)\};\s+#endif", src, re.S)
     assert m, "deal_fast table not found"
     body = re.sub(r"/\*.*?\*/", "", m.group(1))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Deal experiments for the fused member kernel's FAST schedule (greb_member.hip: deal_fast).
+"""Deal experiments for the fused member kernel's FAST schedule (greb_member_deal.h: deal_fast).
 
   python tools/deal_search.py build          here (no GPU): one -DGREB_TUNING library per candidate deal under
                                              greb_climate_model_amd/variants/ (git-ignored, travels with gpurun)
