@@ -81,6 +81,14 @@ class GrebMemberForcing(C.Structure):
     _fields_ = [("co2_pattern", C.c_int32), ("co2_ref", C.c_float), ("solar_table", C.c_int32), ("solar_scale", C.c_float)]
 
 
+MAX_SST_PATTERNS = 1024  # GREB_MAX_SST_PATTERNS: prescribed-SST patterns of one engine
+
+
+class GrebMemberSst(C.Structure):
+    """struct greb_member_sst: a member's SST pattern (-1: none, the ocean surface is free) and the amplitude on its anomaly."""
+    _fields_ = [("pattern", C.c_int32), ("amp", C.c_float)]
+
+
 # what a member may NOT change (it feeds data every member shares): greb_engine_create_members rejects a difference
 MEMBER_SHARED = ("pi", "z_air", "z_vapor", "dt", "dt_crcl", "ipx", "ipy", "year0")
 

@@ -50,6 +50,12 @@ struct greb_engine {
   std::vector<greb_member_forcing> h_force;            // [nm], or empty: no member forcing set
   greb::MemberForcing* force_dev = nullptr;            // [nm], current whenever forced_members > 0
   int forced_members = 0;                              // members that name a pattern or a table or scale the insolation
+  // prescribed SST (set_sst_tables, set_member_sst): scenario phase only
+  int n_sst = 0;
+  float *s_anom = nullptr, *s_weight = nullptr, *s_season = nullptr; // [n_sst][np], [n_sst][np] or null (1 everywhere), [n_sst][730]
+  std::vector<greb_member_sst> h_sst;                  // [nm], or empty: no member SST set
+  greb::MemberSst* sst_dev = nullptr;                  // [nm], current whenever sst_members > 0
+  int sst_members = 0;                                 // members that name a pattern
   // boundary sets (add_boundary_set, set_member_boundary): both phases
   struct BoundSet {
     float* dev[greb::kBoundaryFields] = {}; // the set's thirteen device arrays in BoundarySet's order: its own or the engine's
@@ -65,7 +71,8 @@ struct greb_engine {
   greb::BoundarySet* bsets_dev = nullptr;              // the set table (greb_kernels.h: kSetTableBytes), made with the engine where it
                                                        // keeps forcing records, else with the first set
   int* bset_dev = nullptr;                             // [nm], current whenever members_on_sets > 0
-  greb::MemberForcing* neutral_force_dev = nullptr;    // [nm] {-1, ., -1, 1}: what a BOUND scenario launch takes when no member is forced
+  greb::MemberForcing* neutral_force_dev = nullptr;    // [nm] {-1, ., -1, 1}: what a BOUND scenario launch, or one with a
+                                                       // prescribed-SST member, takes when no member is forced
   float* yearly_dev = nullptr; size_t yearly_cap = 0;
   float* diag_out = nullptr; size_t diag_out_cap = 0; // run_diag: zonal means and annual maps of two years (one per staging slot)
   float* diag_reg = nullptr; size_t diag_reg_cap = 0; // run_diag: the region series of the whole call

@@ -39,6 +39,12 @@ struct MemberForcing {
   float solar_scale; // multiplies the table
 };
 
+// greb_member_sst of include/greb_engine.h as the kernels read it: two words per member
+struct MemberSst {
+  int pattern; // -1: the member's ocean surface is free; else the pattern it is held to
+  float amp;   // multiplies the pattern's anomaly
+};
+
 // One boundary set (greb_engine_add_boundary_set) as the kernels read it: the nine input fields of greb_fields that a set
 // may replace and the four derived from them, each pointer either the set's own array or the engine's.  Entry 0 of the
 // table is the engine's own data.
@@ -160,6 +166,12 @@ struct MemberArgs {
   unsigned q_capacity;          // members x chunks: the ring never wraps within a launch
   ChunkTable chunks;            // the steps of the launch cut into chunks, the same for every member
   int stamp_members;            // -DGREB_TUNING builds only: members the stamp buffer was made for (the item records follow theirs)
+  // prescribed SST (read by the kVForce variants only, beside force_m; scenario phase only: greb_physics_step.h,
+  // member_force and prescribe_sst).  Appended likewise.
+  const MemberSst* sst_m;       // [nm] each member's two words; null: no member of the launch is prescribed
+  const float* s_anom;          // [n_sst][np]  anomalies in K
+  const float* s_weight;        // [n_sst][np]  nudging weights in [0, 1]; null: 1 everywhere
+  const float* s_season;        // [n_sst][730] the anomalies' seasonal factor (all ones where the caller gave none)
 };
 
 // The set table on the device: kSetTableEntries BoundarySet, then as many forcing-record pointers (entry 0: the engine's
@@ -176,7 +188,8 @@ enum { kBsw, kBLWsurf, kBLWdown, kBLWabs, kBQsens, kBQlat, kBQlatAir, kBdqEva, k
 // templates over <bool STRICT, unsigned V>: V is a mask of the features compiled in, and a launch takes the instantiation
 // whose features its MemberArgs ask for (select_variant).  A new variant is one entry of kVariants and its branch there.
 // kVFlux: flux-correction phase (:311-364), else scenario; kVExp: honours the experiment switches (xsw, xsw_m);
-// kVBudget: budget output (bsum, brec); kVForce: per-member forcing (force_m); kVBound: boundary sets (bsets, bset_m)
+// kVBudget: budget output (bsum, brec); kVForce: per-member forcing (force_m) and prescribed SST (sst_m); kVBound: boundary
+// sets (bsets, bset_m)
 enum : unsigned { kVFlux = 1, kVExp = 2, kVBudget = 4, kVForce = 8, kVBound = 16 };
 // The flux-correction phase delivers no budget and is not forced; forcing and boundary sets exist in the switch-aware
 // kernels only; a boundary-aware scenario kernel is forcing-aware (without a forced member its launch carries words that

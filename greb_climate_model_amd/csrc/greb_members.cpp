@@ -198,6 +198,104 @@ int greb_engine_set_member_forcing(greb_engine* e, const greb_member_forcing* f)
   return 0;
 }
 
+static_assert(sizeof(greb_member_sst) == sizeof(MemberSst) && sizeof(MemberSst) == 8, "the kernels read greb_member_sst as it is");
+
+int greb_engine_set_sst_tables(greb_engine* e, int n_patterns, const float* anom, const float* weight, const float* season) {
+  const char* who = "set_sst_tables: ";
+  if (!e) return fail(nullptr, GREB_E_INVALID, std::string(who) + "no engine (greb_engine is NULL)");
+  if (n_patterns < 0 || n_patterns > GREB_MAX_SST_PATTERNS)
+    return fail(e, GREB_E_INVALID, who + ("n_patterns = " + std::to_string(n_patterns)) + " (0 ... " + std::to_string(GREB_MAX_SST_PATTERNS) + ")");
+  if (n_patterns > 0 && !anom) return fail(e, GREB_E_INVALID, std::string(who) + "anom is NULL with n_patterns > 0");
+  const size_t np = (size_t)e->np, nx = (size_t)e->nx;
+  char buf[200];
+  for (int k = 0; k < n_patterns; ++k) {
+    for (size_t i = 0; i < np; ++i) {
+      const float v = anom[(size_t)k * np + i];
+      if (!std::isfinite(v)) {
+        std::snprintf(buf, sizeof(buf), "%sanom: pattern %d: value %g at row %zu, column %zu is not finite", who, k, (double)v, i / nx, i % nx);
+        return fail(e, GREB_E_INVALID, buf);
+      }
+    }
+    for (size_t i = 0; weight && i < np; ++i) {
+      const float v = weight[(size_t)k * np + i];
+      if (!(v >= 0.f && v <= 1.f)) { // (a NaN fails both comparisons)
+        std::snprintf(buf, sizeof(buf), "%sweight: pattern %d: weight %g at row %zu, column %zu is not in [0, 1]", who, k, (double)v, i / nx,
+                      i % nx);
+        return fail(e, GREB_E_INVALID, buf);
+      }
+    }
+    for (int t = 0; season && t < kNT; ++t) {
+      const float v = season[(size_t)k * kNT + t];
+      if (!std::isfinite(v)) {
+        std::snprintf(buf, sizeof(buf), "%sseason: pattern %d: value %g at step %d is not finite", who, k, (double)v, t + 1);
+        return fail(e, GREB_E_INVALID, buf);
+      }
+    }
+  }
+  for (size_t m = 0; m < e->h_sst.size(); ++m) // the members' current indices must stay inside the new tables
+    if (e->h_sst[m].pattern >= n_patterns) {
+      std::snprintf(buf, sizeof(buf), "%smember %zu is prescribed with pattern %d: outside the new %d patterns (change or clear the member "
+                    "SST first)", who, m, e->h_sst[m].pattern, n_patterns);
+      return fail(e, GREB_E_INVALID, buf);
+    }
+  HIP_TRY(e, hipSetDevice(e->device));
+  // new buffers first; the engine changes only once they are complete
+  DevBuf<float> d_anom, d_weight, d_season;
+  if (n_patterns > 0) {
+    std::vector<float> ones;
+    if (!season) ones.assign((size_t)n_patterns * kNT, 1.f);
+    HIP_STEP(e, who, "hipMalloc / hipMemcpy of anom", d_anom.upload(anom, (size_t)n_patterns * np));
+    if (weight) HIP_STEP(e, who, "hipMalloc / hipMemcpy of weight", d_weight.upload(weight, (size_t)n_patterns * np));
+    HIP_STEP(e, who, "hipMalloc / hipMemcpy of season", d_season.upload(season ? season : ones.data(), (size_t)n_patterns * kNT));
+  }
+  HIP_STEP(e, who, "hipStreamSynchronize", hipStreamSynchronize(e->stream)); // nothing in flight reads the old ones
+  adopt(e->s_anom, d_anom); adopt(e->s_weight, d_weight); adopt(e->s_season, d_season);
+  e->n_sst = n_patterns;
+  return 0;
+}
+
+int greb_engine_set_member_sst(greb_engine* e, const greb_member_sst* s) {
+  const char* who = "set_member_sst: ";
+  if (!e) return fail(nullptr, GREB_E_INVALID, std::string(who) + "no engine (greb_engine is NULL)");
+  if (!s) { // every member {-1, .}: the kernels of an engine without any of this again
+    e->h_sst.clear();
+    e->sst_members = 0;
+    return 0;
+  }
+  const size_t nm = (size_t)e->nm;
+  char buf[200];
+  int prescribed = 0;
+  for (size_t m = 0; m < nm; ++m) {
+    buf[0] = 0;
+    if (s[m].pattern < -1 || s[m].pattern >= e->n_sst)
+      std::snprintf(buf, sizeof(buf), "%smember %zu: pattern %d is outside -1 ... %d (set_sst_tables gave %d patterns)", who, m, s[m].pattern,
+                    e->n_sst - 1, e->n_sst);
+    else if (s[m].pattern >= 0 && !std::isfinite(s[m].amp))
+      std::snprintf(buf, sizeof(buf), "%smember %zu: amp %g is not finite", who, m, (double)s[m].amp);
+    if (buf[0]) return fail(e, GREB_E_INVALID, buf);
+    prescribed += s[m].pattern >= 0;
+  }
+  if (prescribed > 0) {
+    std::vector<MemberSst> w(nm);
+    for (size_t m = 0; m < nm; ++m) // (amp of a member without a pattern is never read: any bits may stand there)
+      w[m] = MemberSst{s[m].pattern, s[m].pattern >= 0 ? s[m].amp : 0.f};
+    HIP_TRY(e, hipSetDevice(e->device));
+    DevBuf<MemberSst> dev; // the new words first; the engine takes them once nothing in flight reads the old ones
+    DevBuf<MemberForcing> neutral; // what the forcing-aware kernels of the launch take when no member is forced
+    HIP_STEP(e, who, "hipMalloc / hipMemcpy of the members' words", dev.upload(w.data(), nm));
+    if (!e->neutral_force_dev) {
+      const std::vector<MemberForcing> n(nm, MemberForcing{-1, 1.f, -1, 1.f});
+      HIP_STEP(e, who, "hipMalloc / hipMemcpy of the neutral forcing words", neutral.upload(n.data(), nm));
+    }
+    HIP_STEP(e, who, "hipStreamSynchronize", hipStreamSynchronize(e->stream));
+    if (neutral) adopt(e->neutral_force_dev, neutral);
+    adopt(e->sst_dev, dev);
+  }
+  e->h_sst.assign(s, s + nm);
+  e->sst_members = prescribed;
+  return 0;
+}
+
 static_assert(GREB_MAX_BOUNDARY_SETS == kMaxBoundarySets, "the set table's size mirrors the ABI");
 
 int greb_engine_add_boundary_set(greb_engine* e, const greb_fields* over, int* set_id) {

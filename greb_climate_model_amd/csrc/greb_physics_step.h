@@ -38,17 +38,33 @@ __device__ __forceinline__ unsigned member_switches(const MemberArgs& a, int m) 
 // Per-member forcing (kVForce variants, scenario phase only; greb_engine_set_member_forcing): the member's four words
 // and what they select from the engine's shared tables, for one model step.  Everything here is block-uniform and read
 // once per step into scalar registers -- nothing of it lives across the circulation sub-steps; what is per point is the
-// pattern's weight quad (PhysIn::fw) and the three operations of forced_co2.
+// pattern's weight quad (PhysIn::fw) and the three operations of forced_co2.  The same launches carry prescribed SST
+// (greb_engine_set_member_sst): the member's two words and its pattern's season factor are read here likewise; what is per
+// point is done in prescribe_sst.
 struct MemberForce {
   const float* space; // the member's CO2 pattern [np]; null: none, CO2 is the member's scalar
   const float* solar; // the member's insolation table [730][ny] (the engine's own where the member names none)
   float season;       // the pattern's seasonal factor of this step
   float ref, scale;   // CO2 where the weight is 0; factor on the insolation
+  // prescribed SST (greb_engine_set_member_sst): what the member's ocean surface is held to in this step
+  const float* sst_anom;   // the member's anomaly pattern [np]; null: the ocean surface is free
+  const float* sst_weight; // its nudging weights [np]; null: 1 everywhere
+  float sst_season, sst_amp; // the pattern's seasonal factor of this step; the member's amplitude
 };
 __device__ __forceinline__ float uniform_f(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
 template <bool FORCE>
 __device__ __forceinline__ MemberForce member_force(const MemberArgs& a, int m, const StepClock& ck) {
-  MemberForce f{nullptr, a.sw_solar, 1.f, 0.f, 1.f};
+  MemberForce f{nullptr, a.sw_solar, 1.f, 0.f, 1.f, nullptr, nullptr, 1.f, 0.f};
+  if (FORCE && a.sst_m) { // (a member without a pattern: this one scalar test per step)
+    const MemberSst w = a.sst_m[m];
+    const int k = __builtin_amdgcn_readfirstlane(w.pattern);
+    if (k >= 0) {
+      f.sst_anom = a.s_anom + (size_t)k * a.np;
+      if (a.s_weight) f.sst_weight = a.s_weight + (size_t)k * a.np;
+      f.sst_season = uniform_f(a.s_season[(size_t)k * kNT + (ck.ityr - 1)]);
+      f.sst_amp = uniform_f(w.amp);
+    }
+  }
   if (FORCE) {
     const MemberForcing w = a.force_m[m];
     const int k = __builtin_amdgcn_readfirstlane(w.co2_pattern), t = __builtin_amdgcn_readfirstlane(w.solar_table);
@@ -68,6 +84,30 @@ __device__ __forceinline__ float forced_co2(const MemberForce& f, float w_space,
   const float part = w * co2;
   const float rest = (1.f - w) * f.ref;
   return part + rest;
+}
+
+// Prescribed SST of one quad (kVForce variants, scenario phase only; include/greb_engine.h: "prescribed SST"): the ocean
+// points (zt < 0) of Ts are blended towards tclp + anom * season * amp by the weight w -- the lerp of forced_co2, whose ends
+// are exact: w = 1 gives the target bit for bit, w = 0 leaves Ts.  Without a weight table the target itself is taken, which
+// is what the lerp gives at w = 1.  plus1: the member also has GREB_X_SST_PLUS1, which acts first (greb.original.model.f90:226)
+// -- it is applied HERE for a prescribed member, and physics_compute leaves it alone.  Called from physics_load, where Ts,
+// zt and tclp are in hand: the anomaly and weight quads die here, PhysIn gains nothing that lives into physics_compute.
+__device__ __forceinline__ void prescribe_sst(const MemberForce& F, bool plus1, const f4& zt, const f4& tclp, const f4& anom, const f4& w,
+                                              f4& Ts) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float t = Ts.v[e];
+    if (plus1) t = tclp.v[e] + 1.0f;
+    const float a = (anom.v[e] * F.sst_season) * F.sst_amp;
+    const float target = tclp.v[e] + a;
+    if (F.sst_weight) {
+      const float part = w.v[e] * target;
+      const float rest = (1.f - w.v[e]) * t;
+      t = part + rest;
+    } else t = target;
+    if (zt.v[e] < 0.0f) Ts.v[e] = t;
+  }
 }
 
 // Boundary sets (kVBound variants, both phases; greb_engine_set_member_boundary): the member's entry of the set table.
@@ -181,6 +221,11 @@ __device__ __forceinline__ PhysIn physics_load_record(const MemberArgs& a, int q
   if (EXP && !FLUX && (xsw & kXSstPlus1)) i.tclp = ld4(at_bytes(GREB_BF(tclim) + offm, bo));
   i.fw = zero4();
   if (FORCE && F.space) i.fw = ld4(at_bytes(F.space, bo));
+  if (FORCE && F.sst_anom) {
+    const bool plus1 = (xsw & kXSstPlus1) != 0;
+    const f4 tclp = plus1 ? i.tclp : ld4(at_bytes(GREB_BF(tclim) + offm, bo));
+    prescribe_sst(F, plus1, i.zt, tclp, ld4(at_bytes(F.sst_anom, bo)), F.sst_weight ? ld4(at_bytes(F.sst_weight, bo)) : zero4(), i.Ts);
+  }
   return i;
 }
 
@@ -223,6 +268,11 @@ __device__ __forceinline__ PhysIn physics_load(const MemberArgs& a, int qd, cons
   if (EXP && !FLUX && (xsw & kXSstPlus1)) i.tclp = ld4(GREB_BF(tclim) + offm + p0);
   i.fw = zero4();
   if (FORCE && F.space) i.fw = ld4(F.space + p0);
+  if (FORCE && F.sst_anom) {
+    const bool plus1 = (xsw & kXSstPlus1) != 0;
+    const f4 tclp = plus1 ? i.tclp : ld4(GREB_BF(tclim) + offm + p0);
+    prescribe_sst(F, plus1, i.zt, tclp, ld4(F.sst_anom + p0), F.sst_weight ? ld4(F.sst_weight + p0) : zero4(), i.Ts);
+  }
   return i;
 }
 
@@ -284,7 +334,8 @@ __device__ __forceinline__ PhysOut physics_compute(const MemberArgs& a, const Ph
     float Ts1 = in.Ts.v[e];
     const float Ta1 = in.Ta.v[e], To1 = in.To.v[e], q1 = in.q.v[e], cap = in.cap.v[e];
     const float zt = in.zt.v[e], gl = in.gl.v[e], ez = in.ez.v[e], tcl = in.tcl.v[e], cld = in.cld.v[e], mld = in.mld.v[e];
-    if (EXP && !FLUX && (xsw & kXSstPlus1) && zt < 0.0f) Ts1 = in.tclp.v[e] + 1.0f; // greb.original.model.f90:226
+    // (a prescribed member's switch has acted in physics_load, before the blend: prescribe_sst)
+    if (EXP && !FLUX && (xsw & kXSstPlus1) && !(FORCE && F.sst_anom) && zt < 0.0f) Ts1 = in.tclp.v[e] + 1.0f; // greb.original.model.f90:226
     // A member without circulation (greb.original.model.f90:553) whose launch transported it with the others -- the band
     // and strip kernels run every member alike -- drops both increments here: +0, which is what its own zero sub-steps
     // give (xTa == Ta1 bit for bit).

@@ -83,7 +83,8 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_derive_create", "greb_derive_destroy", "greb_derive_uses_budget", "greb_derive_apply_dev",
            "greb_engine_run_derived_diag", "greb_engine_run_derived_clim", "greb_engine_run_derived_ens", "greb_engine_run_derived_lin",
            "greb_engine_run_derived_gram", "greb_engine_run_derived_cross", "greb_engine_run_derived_reg",
-           "greb_engine_set_dealing", "greb_member_chunk_table", "greb_member_queue_capacity"]
+           "greb_engine_set_dealing", "greb_member_chunk_table", "greb_member_queue_capacity",
+           "greb_engine_set_sst_tables", "greb_engine_set_member_sst"]
 
 
 def _check(rc: int, h=None):
@@ -485,6 +486,45 @@ class Engine:
             if d:
                 raise GrebError(-1, f"set_member_forcing: unknown key {sorted(d)[0]!r}")
         _check(lib().greb_engine_set_member_forcing(self.h, arr), self.h)
+
+    def set_sst_tables(self, anom, weight=None, season=None):
+        """The prescribed-SST tables every member shares (greb_engine_set_sst_tables; replaces the ones set before):
+        anom [n_patterns][ny][nx] anomalies in K (or None: no patterns), weight [n_patterns][ny][nx] nudging weights in
+        [0, 1] (None: 1 everywhere), season [n_patterns][730] the anomalies' seasonal factor (None: 1 everywhere)."""
+        def arr(x, tail, what):
+            if x is None:
+                return None
+            x = np.ascontiguousarray(x, np.float32)
+            if x.ndim == len(tail):
+                x = x[None]
+            if x.shape[1:] != tail:
+                raise GrebError(-1, f"set_sst_tables: {what} has shape {x.shape}, expected [n]{list(tail)}")
+            return x
+        anom = arr(anom, (self.ny, self.nx), "anom")
+        weight = arr(weight, (self.ny, self.nx), "weight")
+        season = arr(season, (abi.NSTEP_YR,), "season")
+        for x, what in ((weight, "weight"), (season, "season")):
+            if x is not None and (anom is None or len(x) != len(anom)):
+                raise GrebError(-1, f"set_sst_tables: {what} needs one entry per pattern of anom")
+        ptr = lambda x: None if x is None else abi.fptr(x)
+        _check(lib().greb_engine_set_sst_tables(self.h, 0 if anom is None else len(anom), ptr(anom), ptr(weight), ptr(season)), self.h)
+
+    def set_member_sst(self, sst):
+        """One dict per member (greb_engine_set_member_sst), keys pattern (default -1: none, the ocean surface is free)
+        and amp (1); None: no member is prescribed.  Acts in every run* call from the next one; flux_correction ignores it."""
+        if sst is None:
+            _check(lib().greb_engine_set_member_sst(self.h, None), self.h)
+            return
+        sst = list(sst)
+        if len(sst) != self.nm:
+            raise GrebError(-1, f"set_member_sst: {self.nm} entries expected")
+        arr = (abi.GrebMemberSst * self.nm)()
+        for s, d in zip(arr, sst):
+            d = dict(d or {})
+            s.pattern = int(d.pop("pattern", -1)); s.amp = float(d.pop("amp", 1.0))
+            if d:
+                raise GrebError(-1, f"set_member_sst: unknown key {sorted(d)[0]!r}")
+        _check(lib().greb_engine_set_member_sst(self.h, arr), self.h)
 
     def add_boundary_set(self, **fields) -> int:
         """A boundary set (greb_engine_add_boundary_set): the given fields -- keyword names as in greb_fields, arrays

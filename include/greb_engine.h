@@ -813,6 +813,46 @@ typedef struct greb_member_forcing {
  * A member is forced when it names a pattern or a table or its scale is not 1 (greb_engine_describe: "forcing"). */
 int greb_engine_set_member_forcing(greb_engine* e, const greb_member_forcing* f);
 
+/* ---- prescribed SST: anomaly patterns, nudging weights and seasons per member -------------------------
+ * Members of one engine may differ in the ocean surface temperature they are held to: one SST patch per member beside a
+ * fixed-SST control (Green's-function ensembles), SST prescribed in one basin with a buffer zone and a free ocean elsewhere
+ * (pacemaker runs), an anomaly that changes sign through the year, an ocean held at its climatology under changed CO2.
+ * GREB_X_SST_PLUS1 is the one case anomaly = 1 K everywhere.  A few tables shared by the engine, two words per member, all
+ * of it used in the point physics only; members that differ only in this still share one flux-correction set.  For member
+ * m with pattern k >= 0, in the scenario phase, at every point p with z_topo < 0 (the member's own boundary set's field)
+ * and step ityr (1-based), before the step's physics, where greb.original.model.f90:226 acts (fl: one fp32 rounding; no
+ * contraction, in both arithmetic modes):
+ *   a      = fl( fl(anom[k][p] * season[k][ityr-1]) * amp[m] )
+ *   target = fl( tclim_m[slice of the PREVIOUS step][p] + a )      tclim_m: tclim of the member's boundary set; the slice
+ *                                                                  is the switch's: 730 at ityr = 1
+ *   w      = weight[k][p]                                          (no weight table: 1 everywhere)
+ *   Ts     = fl( fl(w * target) + fl( fl(1 - w) * Ts ) )
+ * so that w = 1 gives target bit for bit and w = 0 leaves Ts bit for bit; without a weight table Ts = target.  Land points
+ * are never touched.  A member that also has GREB_X_SST_PLUS1: the switch acts first, the blend on its result.  With
+ * anom = 1 everywhere, no weight table and amp = 1 a member equals a member with GREB_X_SST_PLUS1 bit for bit.
+ * Scope: the scenario phase -- every greb_engine_run* call, whose signatures are unchanged.  greb_engine_flux_correction
+ * ignores it, as it ignores forcing and GREB_X_SST_PLUS1.  A launch with any prescribed member takes the forcing-aware
+ * instantiations of the kernels for all its members (a member without a pattern pays one scalar test per step there); with
+ * no prescribed and no forced member the engine launches exactly the kernels it launches without any of this.
+ * GREB_E_INVALID, with a message that names the offender: n_patterns outside 0 ... GREB_MAX_SST_PATTERNS, anom NULL with
+ * n_patterns > 0, an anomaly, season factor or amplitude that is not finite, a weight that is not finite or lies outside
+ * [0, 1], a pattern index out of range.  A failed call leaves the engine exactly as it was. */
+#define GREB_MAX_SST_PATTERNS 1024
+/* Tables shared by all members; copied to the device; may be called again (replaces them).  Replacing them with fewer
+ * patterns than a member's current SST names is GREB_E_INVALID: change or clear the member SST first. */
+int greb_engine_set_sst_tables(greb_engine* e,
+      int n_patterns, const float* anom   /* [n_patterns][ny][nx], K */,
+                      const float* weight /* [n_patterns][ny][nx] in [0,1]; NULL = 1 everywhere */,
+                      const float* season /* [n_patterns][730], any finite value; NULL = 1 everywhere */);
+typedef struct greb_member_sst {
+  int32_t pattern;  /* -1: none, the ocean surface is free as today; else 0 .. n_patterns-1 */
+  float   amp;      /* multiplies the pattern's anomaly; 0 holds the weighted points at the climatology */
+} greb_member_sst;
+/* s[n_members]; NULL = every member {-1, .}.  Cheap: two words per member.  Takes effect from the next run call.  A member
+ * is prescribed when it names a pattern (greb_engine_describe: "sst": {"patterns", "prescribed_members"}); it is not
+ * counted among the forced members of "forcing". */
+int greb_engine_set_member_sst(greb_engine* e, const greb_member_sst* s);
+
 /* ---- boundary sets: members of one engine on different boundary data --------------------------------
  * Members of one engine may differ in the boundary fields themselves: a changed cloud, wind, soil-moisture or vapour
  * climatology, a removed ice sheet, flat topography, a constant mixed layer -- each beside an unchanged control member.
