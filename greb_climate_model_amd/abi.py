@@ -89,6 +89,15 @@ class GrebMemberSst(C.Structure):
     _fields_ = [("pattern", C.c_int32), ("amp", C.c_float)]
 
 
+MAX_NOISE_PATTERNS = 16  # GREB_MAX_NOISE_PATTERNS: stochastic heat-flux patterns of one engine
+
+
+class GrebMemberNoise(C.Structure):
+    """struct greb_member_noise: a member's noise pattern (-1: none, the member is deterministic), the amplitude on its sigma
+    and the member's 64-bit seed as two words."""
+    _fields_ = [("pattern", C.c_int32), ("amp", C.c_float), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32)]
+
+
 # what a member may NOT change (it feeds data every member shares): greb_engine_create_members rejects a difference
 MEMBER_SHARED = ("pi", "z_air", "z_vapor", "dt", "dt_crcl", "ipx", "ipy", "year0")
 
@@ -134,6 +143,17 @@ def make_fields(inp) -> tuple[GrebFields, list]:
         keep.append(a)
         setattr(f, name, fptr(a))
     return f, keep
+
+
+def noise_prototypes(lib) -> None:
+    """The argument types of the stochastic heat-flux calls (greb_engine_get_noise takes an int64_t step, which ctypes would
+    otherwise pass as an int)."""
+    vp, i32p = C.c_void_p, C.POINTER(C.c_int32)
+    lib.greb_engine_set_noise_tables.argtypes = [vp, C.c_int, c_float_p, c_float_p, i32p, i32p, i32p]
+    lib.greb_engine_set_member_noise.argtypes = [vp, C.POINTER(GrebMemberNoise)]
+    lib.greb_engine_get_noise.argtypes = [vp, C.c_int, C.c_int64, c_float_p]
+    for f in (lib.greb_engine_set_noise_tables, lib.greb_engine_set_member_noise, lib.greb_engine_get_noise):
+        f.restype = C.c_int
 
 
 def ens_prototypes(lib) -> None:

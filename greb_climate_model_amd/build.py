@@ -16,8 +16,8 @@ LIB = os.path.join(PKG, "libgreb_hip.so")
 # the same sources with -DGREB_TUNING: the timing-experiment knobs of tools/ (GREB_DEBUG_SKIP, GREB_DEBUG_NSUB, ...)
 # exist only in this variant; the release library above never reads the environment
 LIB_TUNING = os.path.join(PKG, "libgreb_hip_tuning.so")
-SOURCES = ["greb_engine.cpp", "greb_run.cpp", "greb_plans.cpp", "greb_members.cpp", "greb_batched.cpp", "greb_kernels.hip", "greb_member.hip", "greb_ensemble.hip", "greb_rows.hip", "greb_step_rows.hip", "greb_circ_rows.hip", "greb_strip_order.cpp", "greb_diag.hip", "greb_clim.hip", "greb_ens.hip", "greb_lin.hip", "greb_fluxes.hip", "greb_gram.hip", "greb_cross.hip", "greb_reg.hip", "greb_derive.hip"]
-HEADERS = ["greb_host.h", "greb_device.h", "greb_kernels.h", "greb_stencil.h", "greb_chain6.h", "greb_rows.h", "greb_step_strip.h", "greb_pair.h", "greb_physics_step.h", "greb_diag.h", "greb_clim.h", "greb_ens.h", "greb_lin.h", "greb_fluxes.h", "greb_gram.h", "greb_cross.h", "greb_reg.h", "greb_derive.h", "greb_season.h", "greb_yearwalk.h", "greb_member_grid.h", "greb_member_lds.h","greb_member_deal.h", "greb_member_bulk.h", "greb_member_polar.h", "greb_member_queue.h", os.path.join(ROOT, "include", "greb_engine.h")]
+SOURCES = ["greb_engine.cpp", "greb_run.cpp", "greb_plans.cpp", "greb_members.cpp", "greb_batched.cpp", "greb_kernels.hip", "greb_member.hip", "greb_ensemble.hip", "greb_rows.hip", "greb_step_rows.hip", "greb_circ_rows.hip", "greb_strip_order.cpp", "greb_diag.hip", "greb_clim.hip", "greb_ens.hip", "greb_lin.hip", "greb_fluxes.hip", "greb_gram.hip", "greb_cross.hip", "greb_reg.hip", "greb_derive.hip", "greb_noise.hip"]
+HEADERS = ["greb_host.h", "greb_device.h", "greb_kernels.h", "greb_stencil.h", "greb_chain6.h", "greb_rows.h", "greb_step_strip.h", "greb_pair.h", "greb_physics_step.h", "greb_noise.h", "greb_diag.h", "greb_clim.h", "greb_ens.h", "greb_lin.h", "greb_fluxes.h", "greb_gram.h", "greb_cross.h", "greb_reg.h", "greb_derive.h", "greb_season.h", "greb_yearwalk.h", "greb_member_grid.h", "greb_member_lds.h","greb_member_deal.h", "greb_member_bulk.h", "greb_member_polar.h", "greb_member_queue.h", os.path.join(ROOT, "include", "greb_engine.h")]
 # -O2: measured 1.4 % faster than -O3 on the fused member kernel (3 790 vs 3 735 yr/s), equal elsewhere
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value",
                "-I" + os.path.join(ROOT, "include")]

@@ -127,7 +127,9 @@ static MemberArgs base_args(greb_engine* e) {
 static void apply_forcing(const greb_engine* e, MemberArgs& a) {
   // (the boundary-aware scenario kernels are forcing-aware: without a forced member they get words that force nothing)
   // (so are the kernels of a launch with a prescribed-SST member: its words and tables travel beside the forcing's)
-  if (e->forced_members <= 0 && (e->members_on_sets > 0 || e->sst_members > 0)) a.force_m = e->neutral_force_dev;
+  // (and those of a launch with a noisy member)
+  if (e->forced_members <= 0 && (e->members_on_sets > 0 || e->sst_members > 0 || e->noisy_members > 0)) a.force_m = e->neutral_force_dev;
+  if (e->noisy_members > 0) { a.noise_m = e->noise_dev; a.n_sigma = e->n_sigma; a.n_season = e->n_season; a.n_cells = e->n_cells; }
   if (e->sst_members > 0) { a.sst_m = e->sst_dev; a.s_anom = e->s_anom; a.s_weight = e->s_weight; a.s_season = e->s_season; }
   if (e->forced_members <= 0) return;
   a.force_m = e->force_dev;
@@ -696,7 +698,7 @@ int greb_engine_destroy(greb_engine* e) {
                   e->corr, e->corr_index, e->tab_index, e->tabs, e->phys, e->co2_dev, e->monthly_dev, e->yearly_dev,
                   e->Xa, e->Xb, e->red, e->W2, e->xsw_dev, e->co2_flux_dev, e->diag_out, e->diag_reg, e->clim_out, e->ens_out, e->lin_out, e->gram_out, e->derive_out, e->bsum, e->budget_dev,
                   e->f_space, e->f_season, e->f_solar, e->force_dev, e->bsets_dev, e->bset_dev, e->neutral_force_dev,
-                  e->s_anom, e->s_weight, e->s_season, e->sst_dev, e->deal_queue, e->deal_image, e->deal_status};
+                  e->s_anom, e->s_weight, e->s_season, e->sst_dev, e->n_sigma, e->n_season, e->n_cells, e->noise_dev, e->deal_queue, e->deal_image, e->deal_status};
   for (void* q : ptrs) if (q) (void)hipFree(q);
   for (const auto& b : e->bound) if (b.frec) (void)hipFree(b.frec);
   for (size_t k = 1; k < e->bound.size(); ++k)
@@ -757,6 +759,8 @@ const char* greb_engine_describe(greb_engine* e) {
                 e->n_solar, e->forced_members);
   s += buf;
   std::snprintf(buf, sizeof(buf), ", \"sst\": {\"patterns\": %d, \"prescribed_members\": %d}", e->n_sst, e->sst_members);
+  s += buf;
+  std::snprintf(buf, sizeof(buf), ", \"noise\": {\"patterns\": %d, \"noisy_members\": %d}", e->n_noise, e->noisy_members);
   s += buf;
   std::snprintf(buf, sizeof(buf), ", \"boundary\": {\"sets\": %d, \"members_on_sets\": %d, \"fields\": [", (int)e->bound.size() - 1,
                 e->members_on_sets);

@@ -56,6 +56,13 @@ struct greb_engine {
   std::vector<greb_member_sst> h_sst;                  // [nm], or empty: no member SST set
   greb::MemberSst* sst_dev = nullptr;                  // [nm], current whenever sst_members > 0
   int sst_members = 0;                                 // members that name a pattern
+  // stochastic heat flux (set_noise_tables, set_member_noise): scenario phase only
+  int n_noise = 0;
+  float *n_sigma = nullptr, *n_season = nullptr;       // [n_noise][np], [n_noise][730]
+  int* n_cells = nullptr;                              // [n_noise][kNoiseRows + ny] (greb_noise.h)
+  std::vector<greb_member_noise> h_noise;              // [nm], or empty: no member noise set
+  greb::MemberNoise* noise_dev = nullptr;              // [nm], current whenever noisy_members > 0
+  int noisy_members = 0;                               // members that name a pattern
   // boundary sets (add_boundary_set, set_member_boundary): both phases
   struct BoundSet {
     float* dev[greb::kBoundaryFields] = {}; // the set's thirteen device arrays in BoundarySet's order: its own or the engine's
@@ -72,7 +79,7 @@ struct greb_engine {
                                                        // keeps forcing records, else with the first set
   int* bset_dev = nullptr;                             // [nm], current whenever members_on_sets > 0
   greb::MemberForcing* neutral_force_dev = nullptr;    // [nm] {-1, ., -1, 1}: what a BOUND scenario launch, or one with a
-                                                       // prescribed-SST member, takes when no member is forced
+                                                       // prescribed-SST or noisy member, takes when no member is forced
   float* yearly_dev = nullptr; size_t yearly_cap = 0;
   float* diag_out = nullptr; size_t diag_out_cap = 0; // run_diag: zonal means and annual maps of two years (one per staging slot)
   float* diag_reg = nullptr; size_t diag_reg_cap = 0; // run_diag: the region series of the whole call

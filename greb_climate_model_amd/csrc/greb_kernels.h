@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "greb_device.h"
+#include "greb_noise.h"
 
 namespace greb {
 
@@ -172,6 +173,12 @@ struct MemberArgs {
   const float* s_anom;          // [n_sst][np]  anomalies in K
   const float* s_weight;        // [n_sst][np]  nudging weights in [0, 1]; null: 1 everywhere
   const float* s_season;        // [n_sst][730] the anomalies' seasonal factor (all ones where the caller gave none)
+  // stochastic heat flux (read by the kVForce variants only, beside force_m; scenario phase only: greb_noise.h,
+  // greb_physics_step.h: member_force and physics_load).  Appended likewise.
+  const MemberNoise* noise_m;   // [nm] each member's four words; null: no member of the launch is noisy
+  const float* n_sigma;         // [n_noise][np]  standard deviations in W/m2
+  const float* n_season;        // [n_noise][730] their seasonal factor (all ones where the caller gave none)
+  const int* n_cells;           // [n_noise][kNoiseRows + ny] log2(cell_x), hold, each row's first cell (greb_noise.h)
 };
 
 // The set table on the device: kSetTableEntries BoundarySet, then as many forcing-record pointers (entry 0: the engine's
@@ -188,8 +195,8 @@ enum { kBsw, kBLWsurf, kBLWdown, kBLWabs, kBQsens, kBQlat, kBQlatAir, kBdqEva, k
 // templates over <bool STRICT, unsigned V>: V is a mask of the features compiled in, and a launch takes the instantiation
 // whose features its MemberArgs ask for (select_variant).  A new variant is one entry of kVariants and its branch there.
 // kVFlux: flux-correction phase (:311-364), else scenario; kVExp: honours the experiment switches (xsw, xsw_m);
-// kVBudget: budget output (bsum, brec); kVForce: per-member forcing (force_m) and prescribed SST (sst_m); kVBound: boundary
-// sets (bsets, bset_m)
+// kVBudget: budget output (bsum, brec); kVForce: per-member forcing (force_m), prescribed SST (sst_m) and stochastic
+// heat flux (noise_m); kVBound: boundary sets (bsets, bset_m)
 enum : unsigned { kVFlux = 1, kVExp = 2, kVBudget = 4, kVForce = 8, kVBound = 16 };
 // The flux-correction phase delivers no budget and is not forced; forcing and boundary sets exist in the switch-aware
 // kernels only; a boundary-aware scenario kernel is forcing-aware (without a forced member its launch carries words that
@@ -334,6 +341,9 @@ hipError_t launch_physics_step(const MemberArgs& a, const float* X, float* Xout,
 hipError_t launch_yearly(const float* red, float* yearly, int np, int nx, int ipx, int ipy, int yearly_years,
                          int year_index, int n_members, bool strict, hipStream_t s);
 hipError_t launch_pack_tracers(const float* state, float* X, int np, int n_members, hipStream_t s);
+// greb_noise.hip: N of one member (words w) and one scenario step (0-based) at every point, out [ny][nx] on the device
+hipError_t launch_noise_field(const MemberNoise& w, const float* n_sigma, const float* n_season, const int* n_cells, int nx, int ny,
+                              long long step, float* out, hipStream_t s);
 
 struct PointArgs {
   int nx, ny, np, ityr;

@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256) void physics_step_kernel(MemberArgs a, const f
   const f4 xTa = ld4(X + ((size_t)m * 2) * np + 4 * qd), xq = ld4(X + ((size_t)m * 2 + 1) * np + 4 * qd);
   f4 oTa, oq, tsm;
   physics_quad<STRICT, V>(a, P, m, qd, ck, co2, state, acc, corr, xTa, xq, oTa, oq, tsm, EXP ? member_switches(a, m) : 0u,
-                          member_force<FORCE>(a, m, ck), member_boundary<BOUND>(a, member_bset<BOUND>(a, m)));
+                          member_force<FORCE>(a, m, ck, a.it0), member_boundary<BOUND>(a, member_bset<BOUND>(a, m)));
   st4(Xout + ((size_t)m * 2) * np + 4 * qd, oTa);
   st4(Xout + ((size_t)m * 2 + 1) * np + 4 * qd, oq);
   if (ck.ityr == kNT) st4(red + (size_t)m * np + 4 * qd, tsm);

@@ -463,7 +463,7 @@ __global__ __launch_bounds__(kThreads) void member_kernel(MemberArgs a_launch) {
     // ---- point physics on the OLD state + Euler update (:254-268 / :328-361)
     const Phys P = a.phys[m];
     const float co2 = FLUX ? co2_flux : a.co2[(size_t)m * a.co2_stride + a.co2_year0 + yr_rel]; // :924
-    const MemberForce mf = member_force<FORCE>(a, m, ck);
+    const MemberForce mf = member_force<FORCE>(a, m, ck, it);
     const BoundPtr B = member_boundary<BOUND>(a, bset);
     // FAST: boundary data from the set's forcing record, everything else by scalar base + one 32-bit offset per quad
     constexpr int ROUTE = STRICT ? kRouteArrays : kRouteRecord;

@@ -296,6 +296,130 @@ int greb_engine_set_member_sst(greb_engine* e, const greb_member_sst* s) {
   return 0;
 }
 
+static_assert(sizeof(greb_member_noise) == sizeof(MemberNoise) && sizeof(MemberNoise) == 16, "the kernels read greb_member_noise as it is");
+
+int greb_engine_set_noise_tables(greb_engine* e, int n_patterns, const float* sigma, const float* season, const int32_t* cell_x,
+                                 const int32_t* cell_y, const int32_t* hold) {
+  const char* who = "set_noise_tables: ";
+  if (!e) return fail(nullptr, GREB_E_INVALID, std::string(who) + "no engine (greb_engine is NULL)");
+  if (n_patterns < 0 || n_patterns > GREB_MAX_NOISE_PATTERNS)
+    return fail(e, GREB_E_INVALID, who + ("n_patterns = " + std::to_string(n_patterns)) + " (0 ... " + std::to_string(GREB_MAX_NOISE_PATTERNS) + ")");
+  if (n_patterns > 0 && !sigma) return fail(e, GREB_E_INVALID, std::string(who) + "sigma is NULL with n_patterns > 0");
+  const size_t np = (size_t)e->np, nx = (size_t)e->nx, ny = (size_t)e->ny;
+  char buf[200];
+  std::vector<int> cells((size_t)n_patterns * (kNoiseRows + ny));
+  for (int k = 0; k < n_patterns; ++k) {
+    for (size_t i = 0; i < np; ++i) {
+      const float v = sigma[(size_t)k * np + i];
+      if (!(v >= 0.f && std::isfinite(v))) { // (a NaN fails the comparison)
+        std::snprintf(buf, sizeof(buf), "%ssigma: pattern %d: value %g at row %zu, column %zu is negative or not finite", who, k, (double)v,
+                      i / nx, i % nx);
+        return fail(e, GREB_E_INVALID, buf);
+      }
+    }
+    for (int t = 0; season && t < kNT; ++t) {
+      const float v = season[(size_t)k * kNT + t];
+      if (!(v >= 0.f && std::isfinite(v))) {
+        std::snprintf(buf, sizeof(buf), "%sseason: pattern %d: value %g at step %d is negative or not finite", who, k, (double)v, t + 1);
+        return fail(e, GREB_E_INVALID, buf);
+      }
+    }
+    const int cx = cell_x ? cell_x[k] : 1, cy = cell_y ? cell_y[k] : 1, h = hold ? hold[k] : 1;
+    buf[0] = 0;
+    if (cx != 1 && cx != 2 && cx != 4) std::snprintf(buf, sizeof(buf), "%scell_x: pattern %d: %d is not 1, 2 or 4", who, k, cx);
+    else if (cy < 1 || cy > (int)ny) std::snprintf(buf, sizeof(buf), "%scell_y: pattern %d: %d is outside 1 ... %zu", who, k, cy, ny);
+    else if (h < 1) std::snprintf(buf, sizeof(buf), "%shold: pattern %d: %d is less than 1", who, k, h);
+    if (buf[0]) return fail(e, GREB_E_INVALID, buf);
+    int* c = cells.data() + (size_t)k * (kNoiseRows + ny);
+    c[kNoiseShift] = cx == 1 ? 0 : (cx == 2 ? 1 : 2);
+    c[kNoiseHold] = h;
+    for (size_t j = 0; j < ny; ++j) c[kNoiseRows + j] = (int)((j / (size_t)cy) * (nx / (size_t)cx)); // (nx is a multiple of 4)
+  }
+  for (size_t m = 0; m < e->h_noise.size(); ++m) // the members' current indices must stay inside the new tables
+    if (e->h_noise[m].pattern >= n_patterns) {
+      std::snprintf(buf, sizeof(buf), "%smember %zu is noisy with pattern %d: outside the new %d patterns (change or clear the member "
+                    "noise first)", who, m, e->h_noise[m].pattern, n_patterns);
+      return fail(e, GREB_E_INVALID, buf);
+    }
+  HIP_TRY(e, hipSetDevice(e->device));
+  // new buffers first; the engine changes only once they are complete
+  DevBuf<float> d_sigma, d_season;
+  DevBuf<int> d_cells;
+  if (n_patterns > 0) {
+    std::vector<float> ones;
+    if (!season) ones.assign((size_t)n_patterns * kNT, 1.f);
+    HIP_STEP(e, who, "hipMalloc / hipMemcpy of sigma", d_sigma.upload(sigma, (size_t)n_patterns * np));
+    HIP_STEP(e, who, "hipMalloc / hipMemcpy of season", d_season.upload(season ? season : ones.data(), (size_t)n_patterns * kNT));
+    HIP_STEP(e, who, "hipMalloc / hipMemcpy of the cell words", d_cells.upload(cells.data(), cells.size()));
+  }
+  HIP_STEP(e, who, "hipStreamSynchronize", hipStreamSynchronize(e->stream)); // nothing in flight reads the old ones
+  adopt(e->n_sigma, d_sigma); adopt(e->n_season, d_season); adopt(e->n_cells, d_cells);
+  e->n_noise = n_patterns;
+  return 0;
+}
+
+int greb_engine_set_member_noise(greb_engine* e, const greb_member_noise* s) {
+  const char* who = "set_member_noise: ";
+  if (!e) return fail(nullptr, GREB_E_INVALID, std::string(who) + "no engine (greb_engine is NULL)");
+  if (!s) { // every member {-1, ...}: the kernels of an engine without any of this again
+    e->h_noise.clear();
+    e->noisy_members = 0;
+    return 0;
+  }
+  const size_t nm = (size_t)e->nm;
+  char buf[200];
+  int noisy = 0;
+  for (size_t m = 0; m < nm; ++m) {
+    buf[0] = 0;
+    if (s[m].pattern < -1 || s[m].pattern >= e->n_noise)
+      std::snprintf(buf, sizeof(buf), "%smember %zu: pattern %d is outside -1 ... %d (set_noise_tables gave %d patterns)", who, m, s[m].pattern,
+                    e->n_noise - 1, e->n_noise);
+    else if (s[m].pattern >= 0 && !std::isfinite(s[m].amp))
+      std::snprintf(buf, sizeof(buf), "%smember %zu: amp %g is not finite", who, m, (double)s[m].amp);
+    if (buf[0]) return fail(e, GREB_E_INVALID, buf);
+    noisy += s[m].pattern >= 0;
+  }
+  if (noisy > 0) {
+    std::vector<MemberNoise> w(nm);
+    for (size_t m = 0; m < nm; ++m) // (the other words of a member without a pattern are never read)
+      w[m] = s[m].pattern >= 0 ? MemberNoise{s[m].pattern, s[m].amp, s[m].seed_lo, s[m].seed_hi} : MemberNoise{-1, 0.f, 0u, 0u};
+    HIP_TRY(e, hipSetDevice(e->device));
+    DevBuf<MemberNoise> dev; // the new words first; the engine takes them once nothing in flight reads the old ones
+    DevBuf<MemberForcing> neutral; // what the forcing-aware kernels of the launch take when no member is forced
+    HIP_STEP(e, who, "hipMalloc / hipMemcpy of the members' words", dev.upload(w.data(), nm));
+    if (!e->neutral_force_dev) {
+      const std::vector<MemberForcing> n(nm, MemberForcing{-1, 1.f, -1, 1.f});
+      HIP_STEP(e, who, "hipMalloc / hipMemcpy of the neutral forcing words", neutral.upload(n.data(), nm));
+    }
+    HIP_STEP(e, who, "hipStreamSynchronize", hipStreamSynchronize(e->stream));
+    if (neutral) adopt(e->neutral_force_dev, neutral);
+    adopt(e->noise_dev, dev);
+  }
+  e->h_noise.assign(s, s + nm);
+  e->noisy_members = noisy;
+  return 0;
+}
+
+int greb_engine_get_noise(greb_engine* e, int member, int64_t step, float* out) {
+  const char* who = "get_noise: ";
+  if (!e) return fail(nullptr, GREB_E_INVALID, std::string(who) + "no engine (greb_engine is NULL)");
+  if (!out) return fail(e, GREB_E_INVALID, std::string(who) + "out is NULL");
+  if (member < 0 || member >= e->nm)
+    return fail(e, GREB_E_INVALID, who + ("member " + std::to_string(member)) + " is outside 0 ... " + std::to_string(e->nm - 1));
+  if (step < 0) return fail(e, GREB_E_INVALID, who + ("step " + std::to_string((long long)step)) + " is negative");
+  if (e->h_noise.empty() || e->h_noise[(size_t)member].pattern < 0)
+    return fail(e, GREB_E_INVALID, who + ("member " + std::to_string(member)) + " names no noise pattern (set_member_noise)");
+  const greb_member_noise& s = e->h_noise[(size_t)member];
+  HIP_TRY(e, hipSetDevice(e->device));
+  DevBuf<float> dev;
+  HIP_STEP(e, who, "hipMalloc", dev.alloc((size_t)e->np));
+  HIP_STEP(e, who, "the query kernel", launch_noise_field(MemberNoise{s.pattern, s.amp, s.seed_lo, s.seed_hi}, e->n_sigma, e->n_season,
+                                                          e->n_cells, e->nx, e->ny, (long long)step, dev.get(), e->stream));
+  HIP_STEP(e, who, "hipStreamSynchronize", hipStreamSynchronize(e->stream));
+  HIP_STEP(e, who, "hipMemcpy", hipMemcpy(out, dev.get(), (size_t)e->np * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 static_assert(GREB_MAX_BOUNDARY_SETS == kMaxBoundarySets, "the set table's size mirrors the ABI");
 
 int greb_engine_add_boundary_set(greb_engine* e, const greb_fields* over, int* set_id) {

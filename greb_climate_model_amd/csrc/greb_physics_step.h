@@ -40,7 +40,9 @@ __device__ __forceinline__ unsigned member_switches(const MemberArgs& a, int m) 
 // once per step into scalar registers -- nothing of it lives across the circulation sub-steps; what is per point is the
 // pattern's weight quad (PhysIn::fw) and the three operations of forced_co2.  The same launches carry prescribed SST
 // (greb_engine_set_member_sst): the member's two words and its pattern's season factor are read here likewise; what is per
-// point is done in prescribe_sst.
+// point is done in prescribe_sst.  And stochastic heat flux (greb_engine_set_member_noise): the member's four words, its
+// pattern's season factor and cell words and the step's hold block (`it`: the scenario clock, 1-based) are read here; the
+// Philox state of a quad lives and dies in physics_load (noise_quad).
 struct MemberForce {
   const float* space; // the member's CO2 pattern [np]; null: none, CO2 is the member's scalar
   const float* solar; // the member's insolation table [730][ny] (the engine's own where the member names none)
@@ -50,11 +52,18 @@ struct MemberForce {
   const float* sst_anom;   // the member's anomaly pattern [np]; null: the ocean surface is free
   const float* sst_weight; // its nudging weights [np]; null: 1 everywhere
   float sst_season, sst_amp; // the pattern's seasonal factor of this step; the member's amplitude
+  // stochastic heat flux (greb_engine_set_member_noise, greb_noise.h): what the member's TF of this step is raised by
+  NoiseStep noise;           // noise.sigma null: the member takes no noise
 };
 __device__ __forceinline__ float uniform_f(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
 template <bool FORCE>
-__device__ __forceinline__ MemberForce member_force(const MemberArgs& a, int m, const StepClock& ck) {
-  MemberForce f{nullptr, a.sw_solar, 1.f, 0.f, 1.f, nullptr, nullptr, 1.f, 0.f};
+__device__ __forceinline__ MemberForce member_force(const MemberArgs& a, int m, const StepClock& ck, long long it) {
+  MemberForce f{nullptr, a.sw_solar, 1.f, 0.f, 1.f, nullptr, nullptr, 1.f, 0.f, NoiseStep{}};
+  if (FORCE && a.noise_m) { // (a member without a pattern: this one scalar test per step)
+    const MemberNoise w = a.noise_m[m];
+    if (__builtin_amdgcn_readfirstlane(w.pattern) >= 0)
+      f.noise = noise_step(w, a.n_sigma, a.n_season, a.n_cells, a.np, a.ny, ck.ityr, (unsigned long long)(it - 1));
+  }
   if (FORCE && a.sst_m) { // (a member without a pattern: this one scalar test per step)
     const MemberSst w = a.sst_m[m];
     const int k = __builtin_amdgcn_readfirstlane(w.pattern);
@@ -108,6 +117,15 @@ __device__ __forceinline__ void prescribe_sst(const MemberForce& F, bool plus1, 
     } else t = target;
     if (zt.v[e] < 0.0f) Ts.v[e] = t;
   }
+}
+
+// one fp32 add per element, never contracted with what made its operands
+__device__ __forceinline__ f4 add4_exact(const f4& a, const f4& b) {
+#pragma clang fp contract(off)
+  f4 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) r.v[e] = a.v[e] + b.v[e];
+  return r;
 }
 
 // Boundary sets (kVBound variants, both phases; greb_engine_set_member_boundary): the member's entry of the set table.
@@ -204,6 +222,8 @@ __device__ __forceinline__ PhysIn physics_load_record(const MemberArgs& a, int q
   else {
     i.c0 = ld4(at_bytes(corr + off, bo)); i.c1 = ld4(at_bytes(corr + (size_t)kNT * np + off, bo));
     i.c2 = ld4(at_bytes(corr + (size_t)2 * kNT * np + off, bo));
+    if (FORCE && F.noise.sigma) // TF' = fl(TF + N): the step's flux correction of :258 with the member's noise
+      i.c0 = add4_exact(i.c0, noise_quad(F.noise, *(const int*)at_bytes((const float*)F.noise.rowcell, so), (int)lon4, ld4(at_bytes(F.noise.sigma, bo))));
   }
   i.acc0 = i.acc1 = i.acc2 = i.acc3 = i.acc4 = zero4();
 #ifdef GREB_TUNING
@@ -251,7 +271,13 @@ __device__ __forceinline__ PhysIn physics_load(const MemberArgs& a, int qd, cons
     i.solar = F.solar[(size_t)(ck.ityr - 1) * ny + p0 / nx] * F.scale; // one rounding, then sw = solar * (1 - albedo)
   } else i.solar = a.sw_solar[(size_t)(ck.ityr - 1) * ny + p0 / nx]; // a quad never straddles rows
   if (FLUX) { i.c0 = ld4(GREB_BF(toclim) + p0); i.c1 = ld4(GREB_BF(qclim) + off + p0); i.c2 = zero4(); }
-  else { i.c0 = ld4(corr + off + p0); i.c1 = ld4(corr + (size_t)kNT * np + off + p0); i.c2 = ld4(corr + (size_t)2 * kNT * np + off + p0); }
+  else {
+    i.c0 = ld4(corr + off + p0); i.c1 = ld4(corr + (size_t)kNT * np + off + p0); i.c2 = ld4(corr + (size_t)2 * kNT * np + off + p0);
+    if (FORCE && F.noise.sigma) { // TF' = fl(TF + N): the step's flux correction of :258 with the member's noise
+      const int row = p0 / nx;
+      i.c0 = add4_exact(i.c0, noise_quad(F.noise, F.noise.rowcell[row], p0 - row * nx, ld4(F.noise.sigma + p0)));
+    }
+  }
   i.acc0 = i.acc1 = i.acc2 = i.acc3 = i.acc4 = zero4();
 #ifdef GREB_TUNING
   const bool no_acc = a.dbg & 1; // timing experiments (tools/stamp_member.py, GREB_DEBUG_PHYS)

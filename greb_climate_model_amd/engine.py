@@ -52,6 +52,7 @@ def lib() -> C.CDLL:
         abi.cross_prototypes(L)
         abi.reg_prototypes(L)
         abi.derive_prototypes(L)
+        abi.noise_prototypes(L)
         _lib = L
     return _lib
 
@@ -84,7 +85,8 @@ EXPORTS = ["greb_params_default", "greb_engine_create", "greb_engine_flux_correc
            "greb_engine_run_derived_diag", "greb_engine_run_derived_clim", "greb_engine_run_derived_ens", "greb_engine_run_derived_lin",
            "greb_engine_run_derived_gram", "greb_engine_run_derived_cross", "greb_engine_run_derived_reg",
            "greb_engine_set_dealing", "greb_member_chunk_table", "greb_member_queue_capacity",
-           "greb_engine_set_sst_tables", "greb_engine_set_member_sst"]
+           "greb_engine_set_sst_tables", "greb_engine_set_member_sst",
+           "greb_engine_set_noise_tables", "greb_engine_set_member_noise", "greb_engine_get_noise"]
 
 
 def _check(rc: int, h=None):
@@ -525,6 +527,63 @@ class Engine:
             if d:
                 raise GrebError(-1, f"set_member_sst: unknown key {sorted(d)[0]!r}")
         _check(lib().greb_engine_set_member_sst(self.h, arr), self.h)
+
+    def set_noise_tables(self, sigma, season=None, cell=(1, 1), hold=1):
+        """The stochastic heat-flux tables every member shares (greb_engine_set_noise_tables; replaces the ones set before):
+        sigma [n_patterns][ny][nx] standard deviations in W/m2 (or None: no patterns), season [n_patterns][730] their seasonal
+        factor (None: 1 everywhere), cell (cell_x, cell_y) and hold for all patterns, or one pair / one value per pattern."""
+        if sigma is None:
+            _check(lib().greb_engine_set_noise_tables(self.h, 0, None, None, None, None, None), self.h)
+            return
+        sigma = np.ascontiguousarray(sigma, np.float32)
+        if sigma.ndim == 2:
+            sigma = sigma[None]
+        if sigma.shape[1:] != (self.ny, self.nx):
+            raise GrebError(-1, f"set_noise_tables: sigma has shape {sigma.shape}, expected [n]{[self.ny, self.nx]}")
+        n = len(sigma)
+        if season is not None:
+            season = np.ascontiguousarray(season, np.float32)
+            if season.ndim == 1:
+                season = season[None]
+            if season.shape != (n, abi.NSTEP_YR):
+                raise GrebError(-1, f"set_noise_tables: season has shape {season.shape}, expected {[n, abi.NSTEP_YR]}")
+        cell = np.asarray(cell, np.int32)
+        if cell.ndim == 1:
+            cell = np.broadcast_to(cell, (n, 2))
+        hold = np.broadcast_to(np.asarray(hold, np.int32), (n,)) if np.ndim(hold) == 0 else np.asarray(hold, np.int32)
+        if cell.shape != (n, 2) or hold.shape != (n,):
+            raise GrebError(-1, "set_noise_tables: cell needs one (cell_x, cell_y) and hold one value, for all patterns or per pattern")
+        cx, cy, hold = (np.ascontiguousarray(a, np.int32) for a in (cell[:, 0], cell[:, 1], hold))
+        iptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        _check(lib().greb_engine_set_noise_tables(self.h, n, abi.fptr(sigma), None if season is None else abi.fptr(season), iptr(cx), iptr(cy),
+                                                  iptr(hold)), self.h)
+
+    def set_member_noise(self, noise):
+        """One dict per member (greb_engine_set_member_noise), keys pattern (default -1: none, the member is deterministic),
+        amp (1) and seed (0; a 64-bit integer, noise.seeds makes distinct ones); None: no member is noisy.  Acts in every run*
+        call from the next one; flux_correction ignores it."""
+        if noise is None:
+            _check(lib().greb_engine_set_member_noise(self.h, None), self.h)
+            return
+        noise = list(noise)
+        if len(noise) != self.nm:
+            raise GrebError(-1, f"set_member_noise: {self.nm} entries expected")
+        arr = (abi.GrebMemberNoise * self.nm)()
+        for s, d in zip(arr, noise):
+            d = dict(d or {})
+            seed = int(d.pop("seed", 0)) & 0xFFFFFFFFFFFFFFFF
+            s.pattern = int(d.pop("pattern", -1)); s.amp = float(d.pop("amp", 1.0))
+            s.seed_lo, s.seed_hi = seed & 0xFFFFFFFF, seed >> 32
+            if d:
+                raise GrebError(-1, f"set_member_noise: unknown key {sorted(d)[0]!r}")
+        _check(lib().greb_engine_set_member_noise(self.h, arr), self.h)
+
+    def noise(self, member: int, step: int) -> np.ndarray:
+        """The heat flux N [ny][nx] in W/m2 that noisy member `member` takes at scenario step `step` (0-based, any step >= 0;
+        greb_engine_get_noise): evaluated on the device by the function the step kernels call."""
+        out = np.empty((self.ny, self.nx), np.float32)
+        _check(lib().greb_engine_get_noise(self.h, int(member), int(step), abi.fptr(out)), self.h)
+        return out
 
     def add_boundary_set(self, **fields) -> int:
         """A boundary set (greb_engine_add_boundary_set): the given fields -- keyword names as in greb_fields, arrays

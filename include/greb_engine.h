@@ -853,6 +853,63 @@ typedef struct greb_member_sst {
  * counted among the forced members of "forcing". */
 int greb_engine_set_member_sst(greb_engine* e, const greb_member_sst* s);
 
+/* ---- stochastic heat flux: surface heat-flux noise per member, reproducible by seed --------------------
+ * Members of one engine may differ in nothing but their weather: an initial-condition ensemble, a signal-to-noise figure
+ * for the spread, range, quantile, mode, crossing and regression outputs, Hasselmann's stochastic climate model (weather
+ * noise in the surface heat flux, integrated by the mixed layer into red SST variability).  The noise is generated where
+ * it is used, in the point physics: a few tables shared by the engine, four words per member; members that differ only in
+ * this still share one flux-correction set.  A member's realisation is a pure function of its 64-bit seed and the scenario
+ * step -- not of the member index, the engine size, the workgroup that integrates it or how the years are split into run
+ * calls.  For member m with pattern k >= 0, at point (j, i) (row, longitude; 0-based) and scenario step n -- the engine's
+ * scenario clock, counted 0-based since creation, running on across run* calls and not advanced by flux_correction:
+ *   cell  = (j / cell_y[k]) * (nx / cell_x[k]) + i / cell_x[k]               integer division
+ *   b     = n / hold[k]                                                       64 bit
+ *   (w0,w1,w2,w3) = Philox4x32-10( counter = (cell >> 1, low32(b), high32(b), 0), key = (seed_lo[m], seed_hi[m]) )
+ *   (wa, wb) = cell even ? (w0, w1) : (w2, w3)
+ *   S     = (wa & 0xffff) + (wa >> 16) + (wb & 0xffff) + (wb >> 16)           0 ... 262140, exact
+ *   z     = fl( fl(float(S) - 131070.0f) * C ),  C = 0x37DDB3D7 as fp32 (2.6428997e-05 = fl(sqrt(3 / (65536^2 - 1))))
+ *   N     = fl( fl( fl(sigma[k][p] * season[k][ityr-1]) * amp[m] ) * z )      W/m2
+ *   TF'   = fl( TF + N )
+ * (fl: one fp32 rounding; no contraction, in both arithmetic modes).  TF' takes the place of the step's flux correction in
+ * the scenario update of Tsurf (src/greb.f90:258): a heat flux into the surface layer at every point where sigma is not 0,
+ * land included; nothing else of the update changes.  Philox4x32-10 is the published function (multipliers 0xD2511F53,
+ * 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85); integer operations only.  z is a sum of four 16-bit uniforms: mean 0,
+ * variance 1, |z| <= 3.4641, excess kurtosis -0.3 -- deliberately not Gaussian: no log or cos whose bits would differ
+ * between libraries, and the mixed layer sums hundreds of deviates in any case.  cell_x, cell_y give the noise a spatial
+ * scale (the last cell row may be short), hold a persistence (the deviate is held for `hold` steps; 6 is three days).  The
+ * pattern index is not part of the counter: two members with the same seed on different sigma maps see the same weather,
+ * scaled (common random numbers).
+ * Scope: the scenario phase -- every greb_engine_run* call, whose signatures are unchanged.  greb_engine_flux_correction
+ * ignores it.  The noise is not a budget term (GREB_NBUDGET stays 13): the flux terms of a noisy member are those of its
+ * noisy state.  A launch with any noisy member takes the forcing-aware instantiations of the kernels for all its members (a
+ * member without a pattern pays one scalar test per step there); with no noisy, prescribed or forced member the engine
+ * launches exactly the kernels it launches without any of this.
+ * GREB_E_INVALID, with a message that names the offender: n_patterns outside 0 ... GREB_MAX_NOISE_PATTERNS, sigma NULL with
+ * n_patterns > 0, a sigma or season factor that is negative or not finite, cell_x not 1, 2 or 4, cell_y outside 1 ... ny,
+ * hold < 1, a pattern index out of range, an amplitude that is not finite.  A failed call leaves the engine exactly as it
+ * was. */
+#define GREB_MAX_NOISE_PATTERNS 16
+/* Tables shared by all members; copied to the device; may be called again (replaces them).  Replacing them with fewer
+ * patterns than a member's current noise names is GREB_E_INVALID: change or clear the member noise first. */
+int greb_engine_set_noise_tables(greb_engine* e,
+      int n_patterns, const float* sigma     /* [n_patterns][ny][nx] W/m2, finite, >= 0 */,
+                      const float* season    /* [n_patterns][730] finite, >= 0; NULL = 1 everywhere */,
+                      const int32_t* cell_x  /* [n_patterns] 1, 2 or 4; NULL = 1 */,
+                      const int32_t* cell_y  /* [n_patterns] 1 ... ny; NULL = 1 */,
+                      const int32_t* hold    /* [n_patterns] >= 1; NULL = 1 */);
+typedef struct greb_member_noise {
+  int32_t  pattern;           /* -1: none, the member is deterministic as today; else 0 .. n_patterns-1 */
+  float    amp;               /* multiplies the pattern's sigma; 0 takes the noise path and adds +-0 */
+  uint32_t seed_lo, seed_hi;  /* the member's 64-bit seed: the Philox key */
+} greb_member_noise;
+/* s[n_members]; NULL = every member {-1, ...}.  Cheap: four words per member.  Takes effect from the next run call.  A
+ * member is noisy when it names a pattern (greb_engine_describe: "noise": {"patterns", "noisy_members"}); it is not
+ * counted among the forced members of "forcing" or the prescribed members of "sst". */
+int greb_engine_set_member_noise(greb_engine* e, const greb_member_noise* s);
+/* N of the formula above for member `member` (which must name a pattern) at scenario step `step` (>= 0; any step, also
+ * one the clock has not reached), out[ny][nx]: evaluated on the device by the function the step kernels call. */
+int greb_engine_get_noise(greb_engine* e, int member, int64_t step, float* out);
+
 /* ---- boundary sets: members of one engine on different boundary data --------------------------------
  * Members of one engine may differ in the boundary fields themselves: a changed cloud, wind, soil-moisture or vapour
  * climatology, a removed ice sheet, flat topography, a constant mixed layer -- each beside an unchanged control member.
